@@ -7,12 +7,19 @@ HighIntensityDehazeModel(96) on a synthetic foggy batch + L1 loss + backward + A
 N > 1, the RCCL gradient all-reduce).  fp32 arithmetic (fp32 MFMA) end to end.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement) carrying `roofline` (dominant kernel =
-the MFMA gather convolution, timed live with HIP events on the launch stream) and `cpu_baseline`
-(the CPU oracle timed on a bounded sample on the host cores).
+Rank 0 prints ONE JSON line.  A plain run only sets up, warms up, times the K steps and prints the headline
+(`metric`, `value`, `unit`, `ms_per_step`, ...).  `--full` adds everything else, as separate legs after the
+timed steps: `roofline` (dominant kernel = the MFMA gather convolution, timed live with HIP events on the
+launch stream inside the timed region), `hbm_kernels`, the PSNR / parity checks against the CPU oracle,
+`cpu_baseline` (the CPU oracle timed on a bounded sample on the host cores), `forward_eval` and `split_bf16x3`.
+
+`--dump-outputs DIR` writes what the last timed step computed as float32 .npy files (see dump_outputs).
+The inputs and initial weights are seeded, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -407,6 +414,44 @@ def forward_eval(model, hazy, args, H):
             "hbm_kernels": hbm_family_table(ks, reps)}
 
 
+DUMP_SAMPLE = 1 << 21    # elements kept of an output larger than this (fixed seeded sample): 8 MiB per float32 file
+DUMP_SEED = 0
+
+
+def _dump_sample(x):
+    """x flattened to float32 on the host; above DUMP_SAMPLE elements a fixed seeded sample of it, in index order (the same
+    indices for the same number of elements, so two builds are compared element for element)."""
+    x = x.detach().reshape(-1).float()
+    if x.numel() > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        idx = torch.randperm(x.numel(), generator=g)[:DUMP_SAMPLE].sort().values
+        x = x[idx.to(x.device)]
+    return x.cpu().numpy()
+
+
+def dump_outputs(outdir, model, out, loss):
+    """What the caller of the timed step receives from its last execution, float32 (about 24 MiB in all):
+      loss.npy           the L1 loss, shape (1,)
+      output.npy         the model output (N x 3 x H x W), DUMP_SAMPLE-element seeded sample of the flattened tensor
+      grads.npy          the parameter gradients, concatenated in named_parameters() order, sampled likewise
+      params.npy         the parameters after the step (after the Adam update unless --no-adam), sampled likewise
+      bn_buffers.npy     the BatchNorm running statistics after the step, concatenated in named_buffers() order, whole"""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    params = list(model.parameters())
+    arrays = {
+        "loss": loss.detach().reshape(1).float().cpu().numpy(),
+        "output": _dump_sample(out),
+        "grads": _dump_sample(torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
+                                         for p in params])),
+        "params": _dump_sample(torch.cat([p.detach().reshape(-1) for p in params])),
+        "bn_buffers": torch.cat([b.detach().reshape(-1).float() for b in model.buffers()
+                                 if b.is_floating_point()]).cpu().numpy(),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 BF16_MFMA_PEAK_TFLOPS = 2500.0   # MI355X_MICROARCH.md: dense bf16 MFMA peak
 
 
@@ -458,14 +503,23 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="images per GPU")
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-forward-eval", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: per-kernel roofline / HBM figures, "
+                         "PSNR and parity against the CPU oracle, the CPU baseline, forward_eval, split_bf16x3")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity on its frame")
+    ap.add_argument("--no-forward-eval", action="store_true", help="with --full: skip forward_eval")
     ap.add_argument("--workload", default="complex",
                     choices=["complex", "complex_fullloss", "complex_eval", "config2", "config3", "config4", "config5", "config5_dehaze"],
                     help="complex = headline (BASELINE.json metric); config2/3/4 = the other BASELINE.json configs")
     ap.add_argument("--no-adam", action="store_true")
-    ap.add_argument("--no-split", action="store_true", help="skip the opt-in bf16 x 3 contraction leg (split_bf16x3)")
+    ap.add_argument("--no-split", action="store_true", help="with --full: skip the opt-in bf16 x 3 contraction leg (split_bf16x3)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "complex":
+        ap.error("--dump-outputs applies to the headline workload (--workload complex)")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -523,7 +577,7 @@ def main():
             sync.finish()
         if opt is not None:
             opt.step()
-        return loss
+        return loss, out
 
     for _ in range(args.warmup):
         step()
@@ -538,15 +592,16 @@ def main():
         sync.begin_selfcheck()
         step()
         selfcheck = sync.selfcheck_result(list(model.parameters()))
-    # timed region: exactly K steps between barrier + synchronize on both sides
-    timer = H.KernelTimer(set(CONV_FAMILIES) | set(HBM_FAMILIES))
+    # timed region: exactly K steps between barrier + synchronize on both sides (--full: with the per-kernel HIP events of
+    # the roofline leg recorded inside it)
+    timer = H.KernelTimer(set(CONV_FAMILIES) | set(HBM_FAMILIES)) if args.full else None
     H.TIMER = timer
     if world > 1 or forced:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, out = step()
     torch.cuda.synchronize()
     if world > 1 or forced:
         dist.barrier()
@@ -557,28 +612,10 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, out, loss)
+
     if rank == 0:
-        per = conv_family_table(timer.summary())
-        dom = max(per, key=lambda k_: per[k_]["seconds"])   # dominant kernel = most time inside the timed region
-        d0 = per[dom]
-        traffic, traffic_src = pmc_traffic(dom)
-        roofline = {"bound": "mfma", "kernel": d0["kernel"], "achieved": d0["achieved"], "peak": F32_MFMA_PEAK_TFLOPS,
-                    "unit": "TFLOP/s", "frac": d0["achieved"] / F32_MFMA_PEAK_TFLOPS, "traffic": traffic,
-                    "traffic_unit": "HBM bytes per launch (2*FETCH_SIZE + WRITE_SIZE)", "traffic_source": traffic_src,
-                    "launches": d0["launches"], "avg_launch_ms": d0["avg_launch_ms"],
-                    "flops_per_launch_avg": d0["flops_exec_per_launch_avg"],
-                    "algorithmic_tflops": d0["algorithmic"],
-                    "note": "achieved = executed MFMA FLOPs / HIP-event time over the timed region; traffic comes from the "
-                            "committed rocprofv3 --pmc passes over this same command (rocprofv3 cannot run inside bench.py)",
-                    "other_kernels": {k_: {kk: v for kk, v in per[k_].items() if kk != "flops_exec_per_launch_avg"}
-                                      for k_ in per if k_ != dom},
-                    "conv_seconds_per_step": sum(v["seconds"] for v in per.values()) / max(1, args.steps)}
-        hbm_kernels = hbm_family_table(timer.summary(), args.steps)
-        psnr_small, max_abs_small = psnr_check(model, device)
-        cpu_line, sample, parity = None, None, None
-        if not args.no_cpu_baseline and world == 1:
-            cpu_line, sample = cpu_baseline(args.height, args.width, host_threads())
-            parity = headline_parity(sample, device)
         backend = dist.get_backend() if (world > 1 or forced) else None
         coll = "" if (world == 1 and not forced) else (" + RCCL grad all-reduce (flat buckets, overlapped with backward)" if backend == "nccl"
                                       else f" + {backend} grad all-reduce (single-GPU rehearsal backend, NOT RCCL)")
@@ -595,27 +632,12 @@ def main():
                        "per_gpu_batch": args.batch, "global_batch": world * args.batch,
                        "height": args.height, "width": args.width, "parallelism": f"dp{world}",
                        "dist_backend": backend},
-            # PSNR vs the CPU reference on the HEADLINE frame (train mode, 512x1024); the small eval frame of rounds 1-3 stays
-            # under its own key (and is what these keys fall back to when the CPU leg is skipped)
-            "psnr_db_vs_cpu_oracle": parity["psnr_db"] if parity else (psnr_small if psnr_small != float("inf") else 999.0),
-            "max_abs_vs_cpu_oracle": parity["max_abs"] if parity else max_abs_small,
-            "abs_loss_diff_vs_cpu_oracle": parity["abs_loss_diff"] if parity else None,
-            "parity_frame": parity["frame"] if parity else "1x3x128x256 eval-mode forward (CPU leg skipped)",
-            "parity_detail": parity,
-            "psnr_db_small_eval_frame": psnr_small if psnr_small != float("inf") else 999.0,
-            "max_abs_small_eval_frame": max_abs_small,
             "loss": float(loss.detach()),
-            "roofline": roofline,
-            "hbm_kernels": hbm_kernels,
         }
-        if not args.no_forward_eval:
-            result["forward_eval"] = forward_eval(model, hazy, args, H)
-        if cpu_line is not None:
-            result["cpu_baseline"] = cpu_line
+        if args.full:
+            result.update(full_legs(args, world, model, step, hazy, timer, H, device))
         if selfcheck is not None:
             result["ddp_selfcheck"] = selfcheck
-        if world == 1 and not args.no_split:
-            result["split_bf16x3"] = split_bf16x3(step, model, args, H, sample, device)
         print(json.dumps(result))
     if selfcheck is not None and not selfcheck["ok"]:
         if world > 1 or forced:
@@ -626,6 +648,51 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
 
+
+def full_legs(args, world, model, step, hazy, timer, H, device):
+    """--full: the per-kernel figures of the timed region, then the legs that take runs of their own (PSNR / parity against
+    the CPU oracle, the CPU baseline, forward_eval, split_bf16x3).  Returns the keys they add to the result line."""
+    per = conv_family_table(timer.summary())
+    dom = max(per, key=lambda k_: per[k_]["seconds"])   # dominant kernel = most time inside the timed region
+    d0 = per[dom]
+    traffic, traffic_src = pmc_traffic(dom)
+    roofline = {"bound": "mfma", "kernel": d0["kernel"], "achieved": d0["achieved"], "peak": F32_MFMA_PEAK_TFLOPS,
+                "unit": "TFLOP/s", "frac": d0["achieved"] / F32_MFMA_PEAK_TFLOPS, "traffic": traffic,
+                "traffic_unit": "HBM bytes per launch (2*FETCH_SIZE + WRITE_SIZE)", "traffic_source": traffic_src,
+                "launches": d0["launches"], "avg_launch_ms": d0["avg_launch_ms"],
+                "flops_per_launch_avg": d0["flops_exec_per_launch_avg"],
+                "algorithmic_tflops": d0["algorithmic"],
+                "note": "achieved = executed MFMA FLOPs / HIP-event time over the timed region; traffic comes from the "
+                        "committed rocprofv3 --pmc passes over this same command (rocprofv3 cannot run inside bench.py)",
+                "other_kernels": {k_: {kk: v for kk, v in per[k_].items() if kk != "flops_exec_per_launch_avg"}
+                                  for k_ in per if k_ != dom},
+                "conv_seconds_per_step": sum(v["seconds"] for v in per.values()) / max(1, args.steps)}
+    hbm_kernels = hbm_family_table(timer.summary(), args.steps)
+    psnr_small, max_abs_small = psnr_check(model, device)
+    cpu_line, sample, parity = None, None, None
+    if not args.no_cpu_baseline and world == 1:
+        cpu_line, sample = cpu_baseline(args.height, args.width, host_threads())
+        parity = headline_parity(sample, device)
+    result = {
+        # PSNR vs the CPU reference on the HEADLINE frame (train mode, 512x1024); the small eval frame of rounds 1-3 stays
+        # under its own key (and is what these keys fall back to when the CPU leg is skipped)
+        "psnr_db_vs_cpu_oracle": parity["psnr_db"] if parity else (psnr_small if psnr_small != float("inf") else 999.0),
+        "max_abs_vs_cpu_oracle": parity["max_abs"] if parity else max_abs_small,
+        "abs_loss_diff_vs_cpu_oracle": parity["abs_loss_diff"] if parity else None,
+        "parity_frame": parity["frame"] if parity else "1x3x128x256 eval-mode forward (CPU leg skipped)",
+        "parity_detail": parity,
+        "psnr_db_small_eval_frame": psnr_small if psnr_small != float("inf") else 999.0,
+        "max_abs_small_eval_frame": max_abs_small,
+        "roofline": roofline,
+        "hbm_kernels": hbm_kernels,
+    }
+    if not args.no_forward_eval:
+        result["forward_eval"] = forward_eval(model, hazy, args, H)
+    if cpu_line is not None:
+        result["cpu_baseline"] = cpu_line
+    if world == 1 and not args.no_split:
+        result["split_bf16x3"] = split_bf16x3(step, model, args, H, sample, device)
+    return result
 
 if __name__ == "__main__":
     main()

@@ -5,7 +5,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 A=$1; B=$2; REPS=${3:-2}
 for rep in $(seq 1 $REPS); do
 for L in $A $B; do
-  ADH_LIB_PATH=$L python3 $R/bench.py --no-cpu-baseline --no-forward-eval --steps 5 --warmup 2 2>/dev/null | tail -1 > /tmp/ab_bench.json
+  ADH_LIB_PATH=$L python3 $R/bench.py --full --no-cpu-baseline --no-forward-eval --steps 5 --warmup 2 2>/dev/null | tail -1 > /tmp/ab_bench.json
   python3 - "$L" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab_bench.json"))
