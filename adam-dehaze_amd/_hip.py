@@ -17,6 +17,7 @@ _LIB_PATH = os.environ.get("ADH_LIB_PATH") or os.path.join(os.path.dirname(os.pa
 _lib: Optional[C.CDLL] = None
 
 ACT_NONE, ACT_RELU = 0, 1
+ACT_RELU6, ACT_HARDSWISH, ACT_HARDSIGMOID = 4, 5, 6      # MobileNetV2 / V3 (include/adam_dehaze_hip.h)
 
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 
@@ -199,6 +200,15 @@ _SIGNATURES = {
     "adh_global_avgpool_bwd": [vp, vp, i32, i32, i32, vp, i32],
     "adh_bilinear": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32],
     "adh_bilinear_bwd": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32],
+    "adh_dwconv_pack_weights": [vp, vp, PL, vp],
+    "adh_dwconv_num_blocks": [i64, i32],
+    "adh_dwconv_fwd": [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, i32, vp],
+    "adh_dwconv_dgrad": [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32],
+    "adh_dwconv_wgrad_num_blocks": [i64, i32],
+    "adh_dwconv_wgrad": [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, i32, vp, i32],
+    "adh_channel_scale": [vp, vp, i32, vp, i32, i32, i32, vp, i32],
+    "adh_channel_scale_bwd_num_blocks": [i32, i32],
+    "adh_channel_scale_bwd": [vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, i32, vp, i32, vp],
 }
 
 # functions that return a count / size rather than a status code
@@ -206,7 +216,7 @@ _VALUE_FUNCS = {"adh_version", "adh_conv_fewout_supported", "adh_conv_fewin_supp
                 "adh_conv_wino32_num_blocks", "adh_conv_wgrad_wino_groups", "adh_conv_wgrad_wino32_groups", "adh_conv_wgrad_wino32_classes", "adh_conv_wgrad_wino32_tiles", "adh_conv_wgrad_wino43_groups", "adh_conv_wgrad_wino43_strips", "adh_conv_wgrad_small_slabs", "adh_conv_wgrad_stem_slabs", "adh_conv_stem_num_blocks", "adh_conv_wgrad_slabs", "adh_conv_wgrad_groups", "adh_conv_lds_bytes", "adh_conv_num_blocks", "adh_bn_bwd_num_blocks",
                 "adh_cbam_pool_num_blocks", "adh_cbam_bwd_b_num_blocks", "adh_head_blend_bwd_num_blocks",
                 "adh_reduce_num_blocks", "adh_lpips_layer_num_blocks", "adh_adam_chunk_elems", "adh_nms_words", "adh_augment_num_blocks", "adh_psnr_num_blocks", "adh_cbam_bwd_d_scratch_floats",
-                "adh_ssim_num_blocks"}
+                "adh_ssim_num_blocks", "adh_dwconv_num_blocks", "adh_dwconv_wgrad_num_blocks", "adh_channel_scale_bwd_num_blocks"}
 
 _ERRORS = {-1: "ADH_E_ARG (bad argument: shape / alignment / null pointer)",
            -2: "ADH_E_LAUNCH (hip kernel launch failed)",

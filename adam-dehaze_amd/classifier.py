@@ -7,8 +7,14 @@ state_dict keys (`backbone.*`, `classifier.{1,4}.*`).  Backbones built here:
                         [3, 4, 6, 3], feature_dim 2048, classifier.py:31-33)  -- forward and backward
   densenet121          (the north-star's HDEN backbone; the reference itself raises for this name,
                         classifier.py:69: build-side extension)             -- forward (eval) only
-Every other name raises ValueError like the reference does for unknown backbones (efficientnet /
-mobilenet need timm / torchvision, which are not part of this build).  `pretrained=True` cannot
+  mobilenet_v2 / mobilenet_v3_large / mobilenet_v3_small  (classifier.py:50-66; torchvision's architectures restated
+                        with its key names under backbone.features.*, classifier = Identity; feature_dim 1280 / 960 / 576)
+                        -- forward and backward: depthwise convolutions on depthwise.hip, ReLU6 / Hardswish /
+                        Hardsigmoid in the BatchNorm passes, squeeze-excitation through global_avgpool, 1x1 convs and
+                        channel_scale; V3's BatchNorms use eps 1e-3, momentum 0.01 as torchvision's do
+Every other name raises ValueError like the reference does for unknown backbones (efficientnet needs
+timm, which is not part of this build).  DenseFeatureExtractor stays resnet18 / resnet34 only (its
+mobilenet_v2 form is not built).  `pretrained=True` cannot
 download weights offline: a warning is printed and torchvision's random initialisation is used;
 real checkpoints load through `load_state_dict` (key names match torchvision).
 PARITY UNPINNED for the backbones (no torchvision here): checked against the CPU oracle only.
@@ -17,6 +23,7 @@ from __future__ import annotations
 
 import math
 import warnings
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -202,6 +209,164 @@ class _DenseNet121(nn.Module):
         return eng.global_avgpool(h)
 
 
+def _make_divisible(v, divisor=8):
+    """torchvision.models._utils._make_divisible (min_value = divisor)."""
+    new_v = max(divisor, int(v + divisor / 2) // divisor * divisor)
+    if new_v < 0.9 * v:
+        new_v += divisor
+    return new_v
+
+
+class _CNA(Seq):
+    """torchvision Conv2dNormActivation: Conv2d(k, stride, padding (k-1)/2, groups, bias=False) -> BatchNorm2d -> act
+    (keys .0.weight, .1.*).  groups == C runs on the depthwise kernels."""
+
+    def __init__(self, cin, cout, k, stride, act, depthwise=False, eps=1e-5, momentum=0.1):
+        conv = _tv_conv(1 if depthwise else cin, cout, k)
+        super().__init__([(0, conv), (1, BNParams(cout, eps=eps, momentum=momentum))])
+        self.k, self.stride, self.act, self.depthwise = k, stride, act, depthwise
+
+    def run(self, eng: Engine, x: Act, tr: bool, residual: Optional[Act] = None) -> Act:
+        w, bn = self.at(0).weight, self.at(1).state()
+        if self.depthwise:
+            return eng.dwconv(x, w, bn, k=self.k, stride=self.stride, act=self.act, training=tr)
+        return eng.conv(x, w, None, bn, k=self.k, stride=self.stride, pad=(self.k - 1) // 2, act=self.act, residual=residual,
+                        training=tr)
+
+
+class _InvertedResidualV2(nn.Module):
+    """torchvision.models.mobilenetv2.InvertedResidual: keys conv.{0..3} (expand ratio t != 1) / conv.{0..2} (t == 1)."""
+
+    def __init__(self, cin, cout, stride, t):
+        super().__init__()
+        hidden = cin * t
+        items, i = [], 0
+        if t != 1:
+            items.append((0, _CNA(cin, hidden, 1, 1, H.ACT_RELU6)))
+            i = 1
+        items.append((i, _CNA(hidden, hidden, 3, stride, H.ACT_RELU6, depthwise=True)))
+        items.append((i + 1, _tv_conv(hidden, cout, 1)))
+        items.append((i + 2, BNParams(cout)))
+        self.conv = Seq(items)
+        self.first = i
+        self.use_res = stride == 1 and cin == cout
+
+    def run(self, eng: Engine, x: Act, tr: bool) -> Act:
+        h = x
+        if self.first:
+            h = self.conv.at(0).run(eng, h, tr)
+        h = self.conv.at(self.first).run(eng, h, tr)
+        proj, bn = self.conv.at(self.first + 1), self.conv.at(self.first + 2)
+        return eng.conv(h, proj.weight, None, bn.state(), k=1, stride=1, pad=0, relu=False,
+                        residual=x if self.use_res else None, training=tr)
+
+
+MOBILENET_V2_SETTING = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2),
+                        (6, 320, 1, 1))
+
+
+class _MobileNetV2(nn.Module):
+    """torchvision.models.mobilenet_v2 with classifier = Identity: features -> adaptive avg pool -> flatten."""
+
+    def __init__(self):
+        super().__init__()
+        items = [(0, _CNA(3, 32, 3, 2, H.ACT_RELU6))]
+        cin = 32
+        for t, c, n, s_ in MOBILENET_V2_SETTING:
+            for i in range(n):
+                items.append((len(items), _InvertedResidualV2(cin, c, s_ if i == 0 else 1, t)))
+                cin = c
+        items.append((len(items), _CNA(cin, 1280, 1, 1, H.ACT_RELU6)))
+        self.features = Seq(items)
+        self.nfeatures = len(items)
+
+    def run(self, eng: Engine, x8: Act, tr: bool) -> Act:
+        h = x8
+        for i in range(self.nfeatures):
+            h = self.features.at(i).run(eng, h, tr)
+        return eng.global_avgpool(h)
+
+
+class _SqueezeExcitation(nn.Module):
+    """torchvision.ops.SqueezeExcitation(exp, squeeze, ReLU, Hardsigmoid): x * hardsigmoid(fc2(relu(fc1(avgpool(x)))))."""
+
+    def __init__(self, c, sq):
+        super().__init__()
+        self.fc1 = ConvParams(c, sq, 1, bias=True)
+        self.fc2 = ConvParams(sq, c, 1, bias=True)
+        for fc in (self.fc1, self.fc2):
+            nn.init.kaiming_normal_(fc.weight, mode="fan_out")
+            nn.init.zeros_(fc.bias)
+
+    def run(self, eng: Engine, x: Act) -> Act:
+        p = eng.global_avgpool(x)
+        h = eng.conv(p, self.fc1.weight, self.fc1.bias, None, k=1, stride=1, pad=0, relu=True)
+        h = eng.conv(h, self.fc2.weight, self.fc2.bias, None, k=1, stride=1, pad=0, relu=False)
+        return eng.channel_scale(x, eng.activation(h, H.ACT_HARDSIGMOID))
+
+
+_V3_EPS, _V3_MOMENTUM = 1e-3, 0.01
+# (in, k, exp, out, SE, act, stride): torchvision.models.mobilenetv3._mobilenet_v3_conf
+MOBILENET_V3_LARGE = ((16, 3, 16, 16, False, "RE", 1), (16, 3, 64, 24, False, "RE", 2), (24, 3, 72, 24, False, "RE", 1),
+                      (24, 5, 72, 40, True, "RE", 2), (40, 5, 120, 40, True, "RE", 1), (40, 5, 120, 40, True, "RE", 1),
+                      (40, 3, 240, 80, False, "HS", 2), (80, 3, 200, 80, False, "HS", 1), (80, 3, 184, 80, False, "HS", 1),
+                      (80, 3, 184, 80, False, "HS", 1), (80, 3, 480, 112, True, "HS", 1), (112, 3, 672, 112, True, "HS", 1),
+                      (112, 5, 672, 160, True, "HS", 2), (160, 5, 960, 160, True, "HS", 1), (160, 5, 960, 160, True, "HS", 1))
+MOBILENET_V3_SMALL = ((16, 3, 16, 16, True, "RE", 2), (16, 3, 72, 24, False, "RE", 2), (24, 3, 88, 24, False, "RE", 1),
+                      (24, 5, 96, 40, True, "HS", 2), (40, 5, 240, 40, True, "HS", 1), (40, 5, 240, 40, True, "HS", 1),
+                      (40, 5, 120, 48, True, "HS", 1), (48, 5, 144, 48, True, "HS", 1), (48, 5, 288, 96, True, "HS", 2),
+                      (96, 5, 576, 96, True, "HS", 1), (96, 5, 576, 96, True, "HS", 1))
+
+
+class _InvertedResidualV3(nn.Module):
+    """torchvision.models.mobilenetv3.InvertedResidual: keys block.{0..}: [expand CNA], depthwise CNA, [SE], project CNA."""
+
+    def __init__(self, cin, k, exp, cout, se, act, stride):
+        super().__init__()
+        a = H.ACT_HARDSWISH if act == "HS" else H.ACT_RELU
+        bn = dict(eps=_V3_EPS, momentum=_V3_MOMENTUM)
+        items = []
+        if exp != cin:
+            items.append((len(items), _CNA(cin, exp, 1, 1, a, **bn)))
+        items.append((len(items), _CNA(exp, exp, k, stride, a, depthwise=True, **bn)))
+        if se:
+            items.append((len(items), _SqueezeExcitation(exp, _make_divisible(exp // 4, 8))))
+        items.append((len(items), _CNA(exp, cout, 1, 1, H.ACT_NONE, **bn)))
+        self.block = Seq(items)
+        self.nparts = len(items)
+        self.use_res = stride == 1 and cin == cout
+
+    def run(self, eng: Engine, x: Act, tr: bool) -> Act:
+        h = x
+        for i in range(self.nparts - 1):
+            part = self.block.at(i)
+            h = part.run(eng, h) if isinstance(part, _SqueezeExcitation) else part.run(eng, h, tr)
+        return self.block.at(self.nparts - 1).run(eng, h, tr, residual=x if self.use_res else None)
+
+
+class _MobileNetV3(nn.Module):
+    """torchvision.models.mobilenet_v3_large / _small with classifier = Identity (the reference replaces it): features ->
+    adaptive avg pool -> flatten; V3's own Linear / Hardswish head has no keys here."""
+
+    def __init__(self, setting):
+        super().__init__()
+        bn = dict(eps=_V3_EPS, momentum=_V3_MOMENTUM)
+        items = [(0, _CNA(3, 16, 3, 2, H.ACT_HARDSWISH, **bn))]
+        for cfg in setting:
+            items.append((len(items), _InvertedResidualV3(*cfg)))
+        last = setting[-1][3]
+        items.append((len(items), _CNA(last, 6 * last, 1, 1, H.ACT_HARDSWISH, **bn)))
+        self.features = Seq(items)
+        self.nfeatures = len(items)
+        self.out_channels = 6 * last
+
+    def run(self, eng: Engine, x8: Act, tr: bool) -> Act:
+        h = x8
+        for i in range(self.nfeatures):
+            h = self.features.at(i).run(eng, h, tr)
+        return eng.global_avgpool(h)
+
+
 class _ClassifierFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module, record, x, masks, *params):
@@ -253,6 +418,12 @@ class FogIntensityClassifier(nn.Module):
                 raise ValueError(f"Unsupported ResNet variant: {model_name}")
         elif model_name == "densenet121":
             self.backbone, self.feature_dim = _DenseNet121(), 1024
+        elif model_name == "mobilenet_v2":
+            self.backbone, self.feature_dim = _MobileNetV2(), 1280
+        elif model_name == "mobilenet_v3_large":
+            self.backbone, self.feature_dim = _MobileNetV3(MOBILENET_V3_LARGE), 960
+        elif model_name == "mobilenet_v3_small":
+            self.backbone, self.feature_dim = _MobileNetV3(MOBILENET_V3_SMALL), 576
         else:
             raise ValueError(f"Unsupported model: {model_name}")
         if pretrained:

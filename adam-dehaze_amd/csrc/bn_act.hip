@@ -295,6 +295,9 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
             if (act == ADH_ACT_RELU) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) w[j] = fmaxf(w[j], 0.f);
+            } else if (act != ADH_ACT_NONE) {   // ReLU6 / Hardswish / Hardsigmoid (MobileNet)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) w[j] = adh_act_fwd(act, w[j]);
             }
             if (q < P) __builtin_nontemporal_store(w, reinterpret_cast<f32x4*>(out + q * out_cs + c));
         }
@@ -306,6 +309,7 @@ extern "C" int adh_bn_apply(void* stream, const float* y, int y_cs, const float*
                             uint8_t* mask_bits) {
     if (!y || !scale || !shift || !out || P < 1 || C < 4 || (C & 3) || (y_cs & 3) || (out_cs & 3) || (res_cs & 3))
         return ADH_E_ARG;
+    if (!adh_act_host_valid(act)) return ADH_E_ARG;
     const int CQ = C / 4;
     if (mask_bits && ((CQ & 1) || act != ADH_ACT_RELU)) return ADH_E_ARG;   // nibble pairs: an even number of quads per pixel
     hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_blocks(P, CQ, EW_MAXBLK_APPLY)), dim3(256), 0, (hipStream_t)stream, y, y_cs, scale, shift,
@@ -382,6 +386,9 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
                             const float ov = mask_ss ? fmaf(yy[u][j], msc[j], msh[j]) : o[u][j];
                             gg[j] = ov > 0.f ? gg[j] : 0.f;
                         }
+                    } else if (act != ADH_ACT_NONE) {   // the derivative at the pre-activation (mask_ss is required)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) gg[j] = adh_act_bwd(act, fmaf(yy[u][j], msc[j], msh[j]), gg[j]);
                     }
                     sg += gg;
                     sgx += gg * ((yy[u] - mu) * is);
@@ -411,6 +418,7 @@ extern "C" int adh_bn_bwd_reduce(void* stream, const float* g_out, int g_cs, con
     if (!g_out || !y || !mean || !invstd || !partials || P < 1 || C < 4 || (C & 3) || C > 4096) return ADH_E_ARG;
     if (act == ADH_ACT_RELU && !out && !mask_ss && !mask_bits) return ADH_E_ARG;
     if (mask_bits && (((C / 4) & 1) || act != ADH_ACT_RELU)) return ADH_E_ARG;
+    if (!adh_act_host_valid(act) || (act > ADH_ACT_RELU && !mask_ss)) return ADH_E_ARG;
     hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(adh_bn_bwd_num_blocks(P, C)), dim3(256), 0, (hipStream_t)stream, g_out,
                        g_cs, out, out_cs, act, y, y_cs, mean, invstd, partials, P, C, mask_ss, mask_bits);
     return adh_check_launch();
@@ -515,7 +523,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
             g[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g_out + q * g_cs + c));
             if (mask_bits) mb[u] = mask_bits[(q * CQ + (c >> 2)) >> 1] >> (4 * ((c >> 2) & 1));
             else if (act == ADH_ACT_RELU && !mask_ss) o[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(out + q * out_cs + c));
-            if (training) yy[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(y + q * y_cs + c));
+            if (training || mask_ss) yy[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(y + q * y_cs + c));
         }
 #pragma unroll
         for (int u = 0; u < EW_UNROLL; ++u) {
@@ -531,6 +539,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                         const float ov = mask_ss ? fmaf(yy[u][j], msc[j], msh[j]) : o[u][j];
                         gg[j] = ov > 0.f ? gg[j] : 0.f;
                     }
+                } else if (act != ADH_ACT_NONE) {   // the derivative at the pre-activation (mask_ss is required)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) gg[j] = adh_act_bwd(act, fmaf(yy[u][j], msc[j], msh[j]), gg[j]);
                 }
                 if (g_res) __builtin_nontemporal_store(gg, reinterpret_cast<f32x4*>(g_res + q * gres_cs + c));
                 f32x4 r;
@@ -548,7 +559,9 @@ extern "C" int adh_bn_bwd_apply(void* stream, const float* g_out, int g_cs, cons
                                 const float* mask_ss, const uint8_t* mask_bits) {
     if (!g_out || !coef || !g_y || P < 1 || C < 4 || (C & 3)) return ADH_E_ARG;
     if (training && (!y || !mean || !invstd)) return ADH_E_ARG;
-    if (mask_ss && !(training && act == ADH_ACT_RELU)) return ADH_E_ARG;
+    // mask_ss: the pre-activation fma(y, scale, shift) -- train-mode ReLU, and every MobileNet activation in either mode
+    if (mask_ss && (!y || act == ADH_ACT_NONE)) return ADH_E_ARG;
+    if (!adh_act_host_valid(act) || (act > ADH_ACT_RELU && !mask_ss)) return ADH_E_ARG;
     if (act == ADH_ACT_RELU && !out && !mask_ss && !mask_bits) return ADH_E_ARG;
     if (mask_bits && (((C / 4) & 1) || act != ADH_ACT_RELU)) return ADH_E_ARG;
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_blocks(P, C / 4, EW_MAXBLK_BWD)), dim3(256), 0, (hipStream_t)stream, g_out, g_cs, out, out_cs, act,

@@ -94,7 +94,8 @@ def _layout_key(L: WLayout) -> tuple:
 # all-reduce can start while the rest of the backward pass is still running.
 # ---------------------------------------------------------------------------------------------------------------------
 # Test hook (tests/_util.py: kink_matched): when a dict, every fused conv(+BN)+ReLU op stores its post-activation output
-# under id(weight), so a test can replay the ReLU masks this implementation actually used in the float64 oracle.
+# under id(weight), so a test can replay the ReLU masks this implementation actually used in the float64 oracle.  ReLU6
+# layers (Engine.conv / Engine.dwconv) store theirs too: their derivative mask is 0 < out < 6.
 RELU_CAPTURE: Optional[Dict[int, torch.Tensor]] = None
 # test hook (tests/_util.py kink_matched): {id(AttentionBlock fc.0.weight): (global max-pool arg-max [N, C], per-pixel channel
 # arg-max [N, H*W])} of every attention block run while it is a dict -- the other two kinks of the network besides the ReLUs
@@ -148,13 +149,16 @@ def new_act(N, Hh, Ww, C, device, alloc_C: Optional[int] = None, zero: bool = Fa
 
 
 class BNState:
-    """Parameters/buffers of one BatchNorm2d, by reference to the owning module's tensors."""
-    __slots__ = ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")
+    """Parameters/buffers of one BatchNorm2d, by reference to the owning module's tensors, and its eps / momentum
+    (torchvision's MobileNetV3 uses 1e-3 / 0.01)."""
+    __slots__ = ("weight", "bias", "running_mean", "running_var", "num_batches_tracked", "eps", "momentum")
 
-    def __init__(self, weight, bias, running_mean, running_var, num_batches_tracked):
+    def __init__(self, weight, bias, running_mean, running_var, num_batches_tracked, eps: float = BN_EPS,
+                 momentum: float = BN_MOMENTUM):
         self.weight, self.bias = weight, bias
         self.running_mean, self.running_var = running_mean, running_var
         self.num_batches_tracked = num_batches_tracked
+        self.eps, self.momentum = eps, momentum
 
 
 _SLAB_BUDGET = 1 << 30      # bytes of split-accumulation slab a weight-gradient launch may write (and its reduce kernel read)
@@ -769,10 +773,13 @@ class Engine:
 
     def conv(self, x: Act, w: torch.Tensor, b: Optional[torch.Tensor], bn: Optional[BNState], *, kind: str = "conv",
              k: int = 3, stride: int = 1, pad: int = 1, relu: bool = True, residual: Optional[Act] = None,
-             training: bool = False, out: Optional[torch.Tensor] = None, out_alloc_C: Optional[int] = None) -> Act:
+             training: bool = False, out: Optional[torch.Tensor] = None, out_alloc_C: Optional[int] = None,
+             act: Optional[int] = None) -> Act:
         """ConvBlock / ConvTranspose+BN+ReLU / bare Conv2d as one fused op
         (base_model.py:4-24,26-41; medium_intensity.py:52-56).  `residual` is added after BN and before the
-        ReLU (ResidualBlock tail).  `out`: optional preallocated [N,OH,OW,>=Cout] view to write into."""
+        ReLU (ResidualBlock tail).  `out`: optional preallocated [N,OH,OW,>=Cout] view to write into.
+        `act`: an H.ACT_* code, default from `relu`; ReLU6 / Hardswish / Hardsigmoid (MobileNet) need a BatchNorm and no
+        residual, and run through adh_bn_apply after the raw conv in both modes."""
         if kind == "conv":
             Cout = w.shape[0]
             OH = (x.Hh + 2 * pad - k) // stride + 1
@@ -781,7 +788,11 @@ class Engine:
             Cout = w.shape[1]
             OH, OW = x.Hh * 2, x.Ww * 2
         N = x.N
-        act_code = H.ACT_RELU if relu else H.ACT_NONE
+        act_code = act if act is not None else (H.ACT_RELU if relu else H.ACT_NONE)
+        relu = act_code == H.ACT_RELU
+        if act_code not in (H.ACT_NONE, H.ACT_RELU):
+            assert act_code in (H.ACT_RELU6, H.ACT_HARDSWISH, H.ACT_HARDSIGMOID) and bn is not None and residual is None, \
+                "MobileNet activations run after a BatchNorm, without a residual"
         if out is None:
             # channel allocation is a multiple of 8 (zero padded) so the tensor can feed the MFMA kernels
             ac = out_alloc_C if out_alloc_C is not None else _round_up(Cout, 8)
@@ -804,12 +815,12 @@ class Engine:
                 sums = torch.empty(2 * Cout + 1, device=self.device, dtype=torch.float64)
                 H.call("adh_bn_partial_sums", stats.data_ptr(), nblk, NcP, Cout, float(P), sums.data_ptr())
                 SYNC_BN(sums)
-                H.call("adh_bn_finalize_sums", sums.data_ptr(), Cout, bn.weight.data_ptr(), bn.bias.data_ptr(), BN_EPS,
-                       BN_MOMENTUM, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                H.call("adh_bn_finalize_sums", sums.data_ptr(), Cout, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.eps,
+                       bn.momentum, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                        mean.data_ptr(), invstd.data_ptr(), H.ptr(bn.num_batches_tracked))
             else:
                 H.call("adh_bn_finalize", stats.data_ptr(), nblk, NcP, Cout, float(P), bn.weight.data_ptr(),
-                       bn.bias.data_ptr(), BN_EPS, BN_MOMENTUM, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+                       bn.bias.data_ptr(), bn.eps, bn.momentum, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
                        scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), H.ptr(bn.num_batches_tracked))
             # residual + ReLU (ResidualBlock tail): the backward ReLU mask cannot be recomputed from y alone; keep it as one
             # bit per element (1/32 of `out`) written by this pass instead of reading `out` twice in the backward pass
@@ -823,9 +834,22 @@ class Engine:
         elif bn is not None:
             scale, shift = self._f(Cout), self._f(Cout)
             H.call("adh_bn_fold_eval", Cout, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                   bn.running_var.data_ptr(), BN_EPS, H.ptr(b), scale.data_ptr(), shift.data_ptr())
-            self._run_gather(plans, x, out, Cout, w, scale=scale, shift=shift, residual=res_t, act=act_code)
-            saved = ("eval", scale)
+                   bn.running_var.data_ptr(), bn.eps, H.ptr(b), scale.data_ptr(), shift.data_ptr())
+            if act_code in (H.ACT_NONE, H.ACT_RELU):
+                self._run_gather(plans, x, out, Cout, w, scale=scale, shift=shift, residual=res_t, act=act_code)
+                saved = ("eval", scale)
+            else:
+                # the MFMA conv epilogues know NONE / RELU only: the raw conv, then the folded BN + activation in one pass (the
+                # two passes train mode takes); y is kept for the derivative at the pre-activation
+                assert res_t is None, "a MobileNet activation after a residual add is not a layer of any supported network"
+                y = self._f(N, OH, OW, _round_up(Cout, 4))
+                self._run_gather(plans, x, y, Cout, w)
+                ss = self._f(2, _round_up(Cout, 4), zero=True)
+                ss[0, :Cout].copy_(scale)
+                ss[1, :Cout].copy_(shift)
+                H.call("adh_bn_apply", y.data_ptr(), y.stride(2), ss[0].data_ptr(), ss[1].data_ptr(), None, 0, act_code,
+                       out.data_ptr(), out.stride(2), P, Cout, None, work=4.0 * P * Cout * 2)
+                saved = ("eval_act", y, ss)
         else:
             self._run_gather(plans, x, out, Cout, w, shift=b, residual=res_t, act=act_code)
             saved = ("plain",)
@@ -833,17 +857,17 @@ class Engine:
         o = Act(out, Cout)
         if self.record and saved[0] == "train" and relu and residual is None and USE_BN_FUSED_REDUCE and SYNC_BN is None:
             o.bn_src = (saved[1], saved[4], saved[2])
-        if RELU_CAPTURE is not None and relu:
+        if RELU_CAPTURE is not None and act_code in (H.ACT_RELU, H.ACT_RELU6):
             RELU_CAPTURE[id(w)] = out
         if self.record:
             # the parameters _conv_backward will produce a gradient for (must mirror its add_param_grad calls)
             bn_grads = bn is not None and (training or bn.weight.requires_grad or bn.bias.requires_grad)
             self.use_param(w if (w.requires_grad or self.alias.get(id(w)) is not None) else None, b,
                            bn.weight if bn_grads else None, bn.bias if bn_grads else None)
-            self.tape.append(lambda: self._conv_backward(x, w, b, bn, kind, k, stride, pad, relu, residual, o, saved))
+            self.tape.append(lambda: self._conv_backward(x, w, b, bn, kind, k, stride, pad, act_code, residual, o, saved))
         return o
 
-    def _conv_backward(self, x: Act, w, b, bn, kind, k, stride, pad, relu, residual, o: Act, saved):
+    def _conv_backward(self, x: Act, w, b, bn, kind, k, stride, pad, act_code, residual, o: Act, saved):
         g = o.grad
         o.grad = None
         if g is None:
@@ -852,7 +876,7 @@ class Engine:
         C4 = _round_up(Cout, 4)
         N, OH, OW = o.N, o.Hh, o.Ww
         P = N * OH * OW
-        act_code = H.ACT_RELU if relu else H.ACT_NONE
+        relu = act_code == H.ACT_RELU
         mode = saved[0]
         C8 = _round_up(Cout, 8)
         g_y = self._f(N, OH, OW, C8, zero=(C8 != C4))   # padded channels must be finite zeros (dgrad reads them)
@@ -863,7 +887,7 @@ class Engine:
             _, y, mean, invstd, ss, mbits = saved
             # without a residual the ReLU mask is recomputed from y (fma(y, scale, shift) > 0, the forward expression):
             # the two backward passes then read two tensors each instead of three
-            mask_ss = ss.data_ptr() if (relu and residual is None) else None
+            mask_ss = ss.data_ptr() if (act_code != H.ACT_NONE and residual is None) else None
             fused = o.bn_partial if (o.bn_partial is not None and o.bn_partial[3] is g and SYNC_BN is None) else None
             o.bn_partial = None
             if fused is None:
@@ -902,6 +926,10 @@ class Engine:
             self.add_param_grad(bn.bias, dbeta[:Cout])
             if b is not None:   # a bias feeding train-mode BN has an exactly zero gradient
                 self.add_param_grad(b, self._f(Cout, zero=True))
+        elif mode == "eval_act":
+            self._bn_act_eval_backward(g, saved[1], saved[2], bn, act_code, g_y, P, Cout)
+            if b is not None:
+                self.add_param_grad(b, self._channel_sum(g_y, Cout))
         else:
             coef = self._f(3, C4, zero=True)
             if mode == "eval":
@@ -1145,12 +1173,206 @@ class Engine:
         N, Hh, Ww, Cc = x.N, x.Hh, x.Ww, x.C
         scale, shift = self._f(Cc), self._f(Cc)
         H.call("adh_bn_fold_eval", Cc, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-               bn.running_var.data_ptr(), BN_EPS, None, scale.data_ptr(), shift.data_ptr())
+               bn.running_var.data_ptr(), bn.eps, None, scale.data_ptr(), shift.data_ptr())
         if out is None:
             out = self._f(N, Hh, Ww, Cc)
         H.call("adh_bn_apply", x.t.data_ptr(), x.cs, scale.data_ptr(), shift.data_ptr(), None, 0, H.ACT_RELU,
                out.data_ptr(), out.stride(2), x.pixels, Cc, None)
         return Act(out, Cc)
+
+    # ------------------------------------------------------------------ MobileNetV2 / V3 (torchvision) building blocks
+    def _bn_act_eval_backward(self, g: torch.Tensor, y: torch.Tensor, ss: torch.Tensor, bn: BNState, act_code: int,
+                              g_y: torch.Tensor, P: int, Cc: int):
+        """Backward of out = act(y * scale + shift) with frozen BatchNorm statistics (scale / shift = ss[0] / ss[1], folded
+        from the running estimates): g_y = scale * act'(z) * g, and d-gamma / d-beta when the BN parameters train."""
+        C4 = _round_up(Cc, 4)
+        coef = self._f(3, C4, zero=True)
+        coef[0].copy_(ss[0])
+        mask_ss = ss.data_ptr() if act_code != H.ACT_NONE else None
+        H.call("adh_bn_bwd_apply", g.data_ptr(), g.stride(2), None, 0, act_code, y.data_ptr(), y.stride(2), None, None,
+               coef.data_ptr(), 0, g_y.data_ptr(), g_y.stride(2), None, 0, P, C4, mask_ss, None)
+        if not (bn.weight.requires_grad or bn.bias.requires_grad):
+            return
+        # xhat = (y - running_mean) * invstd; adh_bn_fold_eval without gamma / beta gives invstd as its scale
+        mean4, inv4, junk = self._f(C4, zero=True), self._f(C4, zero=True), self._f(C4)
+        mean4[:Cc].copy_(bn.running_mean)
+        H.call("adh_bn_fold_eval", Cc, None, None, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.eps, None,
+               inv4.data_ptr(), junk.data_ptr())
+        nblk = H.value("adh_bn_bwd_num_blocks", P, C4)
+        partial = self._f(nblk, 2, C4)
+        H.call("adh_bn_bwd_reduce", g.data_ptr(), g.stride(2), None, 0, act_code, y.data_ptr(), y.stride(2), mean4.data_ptr(),
+               inv4.data_ptr(), partial.data_ptr(), P, C4, mask_ss, None)
+        dgamma, dbeta, scratch = self._f(C4), self._f(C4), self._f(3, C4)
+        H.call("adh_bn_bwd_finalize", partial.data_ptr(), nblk, C4, float(P), None, inv4.data_ptr(), dgamma.data_ptr(),
+               dbeta.data_ptr(), 0, scratch.data_ptr())
+        self.add_param_grad(bn.weight, dgamma[:Cc])
+        self.add_param_grad(bn.bias, dbeta[:Cc])
+
+    def dwconv(self, x: Act, w: torch.Tensor, bn: BNState, *, k: int, stride: int, act: int, training: bool) -> Act:
+        """Depthwise Conv2d(C, C, k, stride, (k-1)//2, groups=C, bias=False) -> BatchNorm2d -> act: torchvision's
+        Conv2dNormActivation with groups == C (MobileNetV2 / V3).  Train mode: raw y + per-block statistics from the
+        depthwise kernel, adh_bn_finalize, adh_bn_apply.  Eval mode: the folded BN and the activation in the kernel's
+        epilogue (with gradients: the raw y is kept and adh_bn_apply runs as a pass of its own)."""
+        N, Hh, Ww, Cc = x.N, x.Hh, x.Ww, x.C
+        assert tuple(w.shape) == (Cc, 1, k, k) and Cc % 4 == 0, "depthwise weight must be [C,1,k,k], C % 4 == 0"
+        pad = (k - 1) // 2
+        OH, OW = (Hh + 2 * pad - k) // stride + 1, (Ww + 2 * pad - k) // stride + 1
+        P = N * OH * OW
+        wp = self._packed("adh_dwconv_pack_weights", w, WLayout(1, Cc, k, k, 0, 0, 0, 0, 0), k * k * Cc)
+        ac = _round_up(Cc, 8)
+        out = self._f(N, OH, OW, ac, zero=(ac != Cc))
+        # algorithmic bytes of one depthwise launch: read x once, write y once
+        dw_bytes = 4.0 * (N * Hh * Ww + P) * Cc
+        ss = self._f(2, Cc)
+        if training:
+            y = self._f(N, OH, OW, Cc)
+            nblk = H.value("adh_dwconv_num_blocks", P, Cc)
+            stats = self._f(nblk, 2, Cc)
+            H.call("adh_dwconv_fwd", x.t.data_ptr(), x.cs, N, Hh, Ww, Cc, k, stride, wp.data_ptr(), y.data_ptr(), Cc, OH, OW,
+                   None, None, H.ACT_NONE, stats.data_ptr(), work=dw_bytes)
+            mean, invstd = self._f(Cc), self._f(Cc)
+            if SYNC_BN is not None:
+                sums = torch.empty(2 * Cc + 1, device=self.device, dtype=torch.float64)
+                H.call("adh_bn_partial_sums", stats.data_ptr(), nblk, Cc, Cc, float(P), sums.data_ptr())
+                SYNC_BN(sums)
+                H.call("adh_bn_finalize_sums", sums.data_ptr(), Cc, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.eps,
+                       bn.momentum, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), ss[0].data_ptr(), ss[1].data_ptr(),
+                       mean.data_ptr(), invstd.data_ptr(), H.ptr(bn.num_batches_tracked))
+            else:
+                H.call("adh_bn_finalize", stats.data_ptr(), nblk, Cc, Cc, float(P), bn.weight.data_ptr(), bn.bias.data_ptr(),
+                       bn.eps, bn.momentum, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), ss[0].data_ptr(),
+                       ss[1].data_ptr(), mean.data_ptr(), invstd.data_ptr(), H.ptr(bn.num_batches_tracked))
+            H.call("adh_bn_apply", y.data_ptr(), Cc, ss[0].data_ptr(), ss[1].data_ptr(), None, 0, act, out.data_ptr(), ac, P, Cc,
+                   None, work=8.0 * P * Cc)
+            saved = ("train", y, mean, invstd)
+        else:
+            H.call("adh_bn_fold_eval", Cc, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                   bn.running_var.data_ptr(), bn.eps, None, ss[0].data_ptr(), ss[1].data_ptr())
+            if self.record:
+                y = self._f(N, OH, OW, Cc)
+                H.call("adh_dwconv_fwd", x.t.data_ptr(), x.cs, N, Hh, Ww, Cc, k, stride, wp.data_ptr(), y.data_ptr(), Cc, OH,
+                       OW, None, None, H.ACT_NONE, None, work=dw_bytes)
+                H.call("adh_bn_apply", y.data_ptr(), Cc, ss[0].data_ptr(), ss[1].data_ptr(), None, 0, act, out.data_ptr(), ac,
+                       P, Cc, None, work=8.0 * P * Cc)
+                saved = ("eval", y)
+            else:
+                H.call("adh_dwconv_fwd", x.t.data_ptr(), x.cs, N, Hh, Ww, Cc, k, stride, wp.data_ptr(), out.data_ptr(), ac,
+                       OH, OW, ss[0].data_ptr(), ss[1].data_ptr(), act, None, work=dw_bytes)
+        o = Act(out, Cc)
+        if RELU_CAPTURE is not None and act in (H.ACT_RELU, H.ACT_RELU6):
+            RELU_CAPTURE[id(w)] = out
+        # a weight gradient is produced for trainable weights and for reshaped views registered in `alias` (as in conv)
+        w_grad = w.requires_grad or self.alias.get(id(w)) is not None
+        if self.record:
+            bn_grads = training or bn.weight.requires_grad or bn.bias.requires_grad
+            self.use_param(w if w_grad else None, bn.weight if bn_grads else None, bn.bias if bn_grads else None)
+
+            def bwd():
+                g = o.grad
+                o.grad = None
+                if g is None:
+                    return
+                g_y = self._f(N, OH, OW, Cc)
+                y = saved[1]
+                if saved[0] == "train":
+                    _, _, mean, invstd = saved
+                    mask_ss = ss.data_ptr() if act != H.ACT_NONE else None
+                    nblk_b = H.value("adh_bn_bwd_num_blocks", P, Cc)
+                    partial = self._f(nblk_b, 2, Cc)
+                    H.call("adh_bn_bwd_reduce", g.data_ptr(), g.stride(2), None, 0, act, y.data_ptr(), Cc, mean.data_ptr(),
+                           invstd.data_ptr(), partial.data_ptr(), P, Cc, mask_ss, None, work=8.0 * P * Cc)
+                    dgamma, dbeta = self.grad_buffer(bn.weight), self.grad_buffer(bn.bias)
+                    coef = self._f(3, Cc)
+                    if SYNC_BN is not None:
+                        loc = torch.empty(2 * Cc + 1, device=self.device, dtype=torch.float64)
+                        H.call("adh_bn_partial_sums", partial.data_ptr(), nblk_b, Cc, Cc, float(P), loc.data_ptr())
+                        glob = loc.clone()
+                        SYNC_BN(glob)
+                        H.call("adh_bn_bwd_finalize_sums", loc.data_ptr(), glob.data_ptr(), Cc, bn.weight.data_ptr(),
+                               invstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), 0, coef.data_ptr())
+                    else:
+                        H.call("adh_bn_bwd_finalize", partial.data_ptr(), nblk_b, Cc, float(P), bn.weight.data_ptr(),
+                               invstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), 0, coef.data_ptr())
+                    H.call("adh_bn_bwd_apply", g.data_ptr(), g.stride(2), None, 0, act, y.data_ptr(), Cc, mean.data_ptr(),
+                           invstd.data_ptr(), coef.data_ptr(), 1, g_y.data_ptr(), Cc, None, 0, P, Cc, mask_ss, None,
+                           work=12.0 * P * Cc)
+                    self.add_param_grad(bn.weight, dgamma)
+                    self.add_param_grad(bn.bias, dbeta)
+                else:
+                    self._bn_act_eval_backward(g, y, ss, bn, act, g_y, P, Cc)
+                if w_grad:
+                    nblk_w = H.value("adh_dwconv_wgrad_num_blocks", P, Cc)
+                    partial_w = self._f(nblk_w * k * k * Cc)
+                    dw = self.grad_buffer(w)
+                    H.call("adh_dwconv_wgrad", x.t.data_ptr(), x.cs, N, Hh, Ww, Cc, k, stride, g_y.data_ptr(), Cc, OH, OW,
+                           partial_w.data_ptr(), nblk_w, dw.data_ptr(), 0, work=dw_bytes)
+                    self.add_param_grad(w, dw)
+                if x.needs_grad:
+                    if x.grad is None:
+                        gx = self._f(N, Hh, Ww, _round_up(Cc, 4))
+                        H.call("adh_dwconv_dgrad", g_y.data_ptr(), Cc, N, OH, OW, Cc, k, stride, wp.data_ptr(), gx.data_ptr(),
+                               gx.stride(2), Hh, Ww, 0, work=dw_bytes)
+                        x.grad = gx
+                    else:   # the input has another consumer (a residual): accumulate in place
+                        x.bn_partial = None
+                        H.call("adh_dwconv_dgrad", g_y.data_ptr(), Cc, N, OH, OW, Cc, k, stride, wp.data_ptr(),
+                               x.grad.data_ptr(), x.grad.stride(2), Hh, Ww, 1, work=dw_bytes)
+            self.tape.append(bwd)
+        return o
+
+    def activation(self, x: Act, act: int) -> Act:
+        """act(x) as a pass of its own (the squeeze-excitation gate, Hardsigmoid): adh_bn_apply with scale 1, shift 0."""
+        N, Hh, Ww, Cc = x.N, x.Hh, x.Ww, x.C
+        C4 = _round_up(Cc, 4)
+        ss = self._f(2, C4, zero=True)
+        ss[0].fill_(1.0)
+        out = self._f(N, Hh, Ww, C4)
+        H.call("adh_bn_apply", x.t.data_ptr(), x.cs, ss[0].data_ptr(), ss[1].data_ptr(), None, 0, act, out.data_ptr(), C4,
+               x.pixels, C4, None)
+        o = Act(out, Cc)
+        if self.record:
+            def bwd():
+                g = o.grad
+                o.grad = None
+                if g is None or not x.needs_grad:
+                    return
+                gx = self._f(N, Hh, Ww, C4)
+                coef = self._f(3, C4, zero=True)
+                coef[0].fill_(1.0)
+                H.call("adh_bn_bwd_apply", g.data_ptr(), g.stride(2), None, 0, act, x.t.data_ptr(), x.cs, None, None,
+                       coef.data_ptr(), 0, gx.data_ptr(), C4, None, 0, x.pixels, C4,
+                       ss.data_ptr() if act != H.ACT_NONE else None, None)
+                self.accum(x, gx)
+            self.tape.append(bwd)
+        return o
+
+    def channel_scale(self, x: Act, s: Act) -> Act:
+        """x[n,p,c] * s[n,c] (squeeze-excitation, torchvision SqueezeExcitation.forward); s is a [N,1,1,C] map."""
+        N, Hh, Ww, Cc = x.N, x.Hh, x.Ww, x.C
+        HW = Hh * Ww
+        assert s.C == Cc and s.N == N and s.pixels == N and s.cs == s.t.shape[3] and s.t.shape[3] >= Cc and Cc % 4 == 0
+        st = s.t.reshape(N, -1)[:, :Cc].contiguous()
+        out = self._f(N, Hh, Ww, Cc)
+        H.call("adh_channel_scale", x.t.data_ptr(), x.cs, st.data_ptr(), N, HW, Cc, out.data_ptr(), Cc,
+               work=8.0 * N * HW * Cc)
+        o = Act(out, Cc)
+        if self.record:
+            def bwd():
+                g = o.grad
+                o.grad = None
+                if g is None:
+                    return
+                nblk = H.value("adh_channel_scale_bwd_num_blocks", HW, Cc)
+                partial = self._f(N * nblk * Cc)
+                gs = self._f(N, 1, 1, Cc)
+                gx = self._f(N, Hh, Ww, Cc) if x.needs_grad else None
+                H.call("adh_channel_scale_bwd", g.data_ptr(), g.stride(2), x.t.data_ptr(), x.cs, st.data_ptr(), N, HW, Cc,
+                       H.ptr(gx), Cc, partial.data_ptr(), nblk, gs.data_ptr(), work=(12.0 if gx is not None else 8.0) * N * HW * Cc)
+                self.accum(s, gs)
+                if gx is not None:
+                    self.accum(x, gx)
+            self.tape.append(bwd)
+        return o
 
     def mul_mask(self, x: Act, mask: torch.Tensor) -> Act:
         """x * mask (dropout with a pre-drawn, pre-scaled mask of x's shape and strides)."""

@@ -37,10 +37,12 @@ class ConvParams(nn.Module):
 
 
 class BNParams(nn.Module):
-    """BatchNorm2d parameters and running statistics (eps 1e-5, momentum 0.1)."""
+    """BatchNorm2d parameters and running statistics (eps 1e-5, momentum 0.1 unless given: torchvision's MobileNetV3
+    uses 1e-3 / 0.01).  eps / momentum are plain attributes, as on nn.BatchNorm2d: not part of the state_dict."""
 
-    def __init__(self, c: int):
+    def __init__(self, c: int, eps: float = 1e-5, momentum: float = 0.1):
         super().__init__()
+        self.eps, self.momentum = eps, momentum
         self.weight = nn.Parameter(torch.ones(c))
         self.bias = nn.Parameter(torch.zeros(c))
         self.register_buffer("running_mean", torch.zeros(c))
@@ -48,7 +50,8 @@ class BNParams(nn.Module):
         self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
 
     def state(self) -> BNState:
-        return BNState(self.weight, self.bias, self.running_mean, self.running_var, self.num_batches_tracked)
+        return BNState(self.weight, self.bias, self.running_mean, self.running_var, self.num_batches_tracked, self.eps,
+                       self.momentum)
 
     def forward(self, *a, **k):
         raise RuntimeError("parameter container: compute runs through the HIP engine")

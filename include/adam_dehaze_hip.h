@@ -36,6 +36,9 @@ extern "C" {
 #define ADH_ACT_RELU 1
 #define ADH_ACT_SIGMOID 2
 #define ADH_ACT_TANH 3
+#define ADH_ACT_RELU6 4        /* min(max(z, 0), 6)                (MobileNetV2)                          */
+#define ADH_ACT_HARDSWISH 5    /* z * relu6(z + 3) / 6             (MobileNetV3)                          */
+#define ADH_ACT_HARDSIGMOID 6  /* relu6(z + 3) / 6                 (MobileNetV3 squeeze-excitation gate)  */
 
 /* Gather-form convolution descriptor shared by the forward / dgrad / wgrad kernels.
  * Virtual output grid VH x VW; virtual pixel (vy,vx) reads input pixel
@@ -304,7 +307,9 @@ int adh_bn_apply(void* stream, const float* y, int y_cs, const float* scale, con
  * (nblk = adh_bn_bwd_num_blocks(P)). */
 int adh_bn_bwd_num_blocks(int64_t P, int C);
 /* mask_ss (optional, act == RELU, no residual): {scale[C], shift[C]} of the forward pass -- the ReLU mask is then
- * recomputed as fma(y, scale, shift) > 0, exactly the forward expression, and `out` is not read (one tensor pass less). */
+ * recomputed as fma(y, scale, shift) > 0, exactly the forward expression, and `out` is not read (one tensor pass less).
+ * ADH_ACT_RELU6 / HARDSWISH / HARDSIGMOID (adh_bn_apply, adh_bn_bwd_reduce, adh_bn_bwd_apply; no residual) require mask_ss:
+ * their derivative is taken at the pre-activation z = fma(y, scale, shift), in eval mode (training == 0) as well. */
 int adh_bn_bwd_reduce(void* stream, const float* g_out, int g_cs, const float* out, int out_cs, int act,
                       const float* y, int y_cs, const float* mean, const float* invstd,
                       float* partials, int64_t P, int C, const float* mask_ss, const uint8_t* mask_bits);
@@ -544,6 +549,36 @@ int adh_psnr(void* stream, const float* pred, const float* target, int N, int64_
 int adh_ssim_num_blocks(int H, int W);
 int adh_ssim_gray(void* stream, const float* pred_nchw, const float* target_nchw, int N, int H, int W, float data_range,
                   double* partial, int nblk, float* ssim);
+
+/* ---- Depthwise convolution and squeeze-excitation (torchvision MobileNetV2 / V3; depthwise.hip) ------------------------
+ * Conv2d(C, C, k, stride, padding (k-1)/2, groups=C, bias=False) on NHWC fp32 activations with channel strides x_cs /
+ * out_cs; C % 4 == 0, C <= 4096, k in {3, 5}, stride in {1, 2}.  Weights are packed once per weight version:
+ * adh_dwconv_pack_weights reads w[C][1][k][k] with L->Nc = C, L->KHt = L->KWt = k (other fields unused) and writes
+ * wp[k*k][C]. */
+int adh_dwconv_pack_weights(void* stream, const float* w, const adh_wlayout* L, float* wp);
+/* pixel blocks of a forward launch over P = N*OH*OW output pixels: the rows of its statistics, stats[nblk][2][C] */
+int adh_dwconv_num_blocks(int64_t P, int C);
+/* y = dwconv(x).  stats != NULL (train mode): y is stored raw and stats[b][0][c] / stats[b][1][c] = sum y / sum y^2 over
+ * pixel block b, the layout adh_bn_finalize / adh_bn_partial_sums read (pitch C).  scale / shift != NULL (eval mode):
+ * out = act(y * scale[c] + shift[c]) instead (act: any ADH_ACT_* code but SIGMOID / TANH). */
+int adh_dwconv_fwd(void* stream, const float* x, int x_cs, int N, int IH, int IW, int C, int k, int stride, const float* wp,
+                   float* out, int out_cs, int OH, int OW, const float* scale, const float* shift, int act, float* stats);
+/* gx = data gradient of the depthwise conv given g = dL/dy [N][OH][OW] (a gather: no atomics); gx is overwritten, or
+ * accumulated into when accumulate != 0 */
+int adh_dwconv_dgrad(void* stream, const float* g, int g_cs, int N, int OH, int OW, int C, int k, int stride,
+                     const float* wp, float* gx, int gx_cs, int IH, int IW, int accumulate);
+/* weight gradient dw[C][1][k][k]: per-block partials[nblk][k*k][C] (nblk = adh_dwconv_wgrad_num_blocks), then a
+ * fixed-order reduce -- bit-reproducible run to run */
+int adh_dwconv_wgrad_num_blocks(int64_t P, int C);
+int adh_dwconv_wgrad(void* stream, const float* x, int x_cs, int N, int IH, int IW, int C, int k, int stride,
+                     const float* g, int g_cs, int OH, int OW, float* partials, int nblk, float* dw, int accumulate);
+/* squeeze-excitation channel scale: out[n][p][c] = x[n][p][c] * s[n][c] over HW pixels per image */
+int adh_channel_scale(void* stream, const float* x, int x_cs, const float* s, int N, int HW, int C, float* out, int out_cs);
+/* its backward: gx = g * s (skipped when gx is NULL) and gs[n][c] = sum_p g * x through partials[N][nblk][C]
+ * (nblk = adh_channel_scale_bwd_num_blocks) and a fixed-order reduce */
+int adh_channel_scale_bwd_num_blocks(int HW, int C);
+int adh_channel_scale_bwd(void* stream, const float* g, int g_cs, const float* x, int x_cs, const float* s, int N, int HW,
+                          int C, float* gx, int gx_cs, float* partials, int nblk, float* gs);
 
 #ifdef __cplusplus
 }
