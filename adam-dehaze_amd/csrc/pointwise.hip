@@ -623,7 +623,8 @@ extern "C" int adh_axpby_strided(void* stream, float* dst, int dst_cs, const flo
 }
 
 // MaxPool2d(k, stride, pad) (medium_intensity.py:145,150; high_intensity.py:162,165; torchvision resnet/densenet
-// stem pool k3 s2 p1); idx = winning input pixel, first on ties (scan order = ATen's)
+// stem pool k3 s2 p1); idx = winning input pixel, first on ties (scan order = ATen's).  Known difference: ATen propagates a
+// NaN anywhere in a window; this kernel keeps a NaN only when it is the window's first element.
 __global__ __launch_bounds__(256) void maxpool_kernel(const float* __restrict__ x, int x_cs, int H, int W, int CQ, int k,
                                                       int stride, int pad, int OH, int OW, float* __restrict__ out,
                                                       int out_cs, int32_t* __restrict__ idx) {
@@ -813,33 +814,71 @@ extern "C" int adh_bilinear(void* stream, const float* x, int x_cs, int N, int H
     return adh_check_launch();
 }
 
-// adjoint (scatter with fp32 atomics; gx must be zero-initialised by the caller)
+// output indices o whose (i0, i1) pair may contain input index i: the source map inverted at i - 1 and i + 1, widened by two
+// for fp32 rounding (every output whose source clamps to 0 pairs inputs 0 and 1); the caller keeps only the candidates for
+// which bilin_src reproduces the pairing
+__device__ __forceinline__ void bilin_cover(int i, int in, int out, int align, int& lo, int& hi) {
+    if (align && in == 1) {             // every output reads input 0
+        lo = 0;
+        hi = out - 1;
+        return;
+    }
+    float a, b;
+    if (align) {
+        const float isc = (float)(out - 1) / (float)(in - 1);
+        a = (float)(i - 1) * isc;
+        b = (float)(i + 1) * isc;
+    } else {
+        const float isc = (float)out / (float)in;
+        a = ((float)i - 0.5f) * isc - 0.5f;
+        b = ((float)i + 1.5f) * isc - 0.5f;
+    }
+    lo = i <= 1 ? 0 : (int)fmaxf(floorf(a) - 2.f, 0.f);
+    hi = (int)fminf(ceilf(b) + 2.f, (float)(out - 1));
+}
+
+// weight of input index i in output o along one axis: the forward's (1 - l1) and l1 exactly (both when i0 = i1 = i)
+__device__ __forceinline__ float bilin_weight(int o, int i, int in, int out, int align) {
+    int i0, i1;
+    float l1;
+    bilin_src(o, in, out, align, i0, i1, l1);
+    return (i0 == i ? 1.f - l1 : 0.f) + (i1 == i ? l1 : 0.f);
+}
+
+// adjoint in gather form: every input element sums, in a fixed order (output rows, then columns, ascending), the outputs whose
+// (y0, y1) x (x0, x1) footprint contains it -- deterministic, no atomics; writes every element of gx it owns (no zero-fill)
 __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* __restrict__ g, int g_cs, int H, int W, int C, int OH,
                                                            int OW, int align, float* __restrict__ gx, int gx_cs) {
     const int n = blockIdx.y;
-    const int64_t total = (int64_t)OH * OW * C;
-    float* gxn = gx + (size_t)n * H * W * gx_cs;
+    const int64_t total = (int64_t)H * W * C;
+    const float* gn = g + (size_t)n * OH * OW * g_cs;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t op = t / C;
-        const int c = (int)(t - op * C);
-        const int oy = (int)(op / OW), ox = (int)(op - (int64_t)oy * OW);
-        int y0, y1, x0, x1;
-        float ly, lx;
-        bilin_src(oy, H, OH, align, y0, y1, ly);
-        bilin_src(ox, W, OW, align, x0, x1, lx);
-        const float hy = 1.f - ly, hx = 1.f - lx;
-        const float gv = g[((size_t)n * OH * OW + op) * g_cs + c];
-        atomicAdd(gxn + ((size_t)y0 * W + x0) * gx_cs + c, gv * hy * hx);
-        atomicAdd(gxn + ((size_t)y0 * W + x1) * gx_cs + c, gv * hy * lx);
-        atomicAdd(gxn + ((size_t)y1 * W + x0) * gx_cs + c, gv * ly * hx);
-        atomicAdd(gxn + ((size_t)y1 * W + x1) * gx_cs + c, gv * ly * lx);
+        const int64_t ip = t / C;
+        const int c = (int)(t - ip * C);
+        const int iy = (int)(ip / W), ix = (int)(ip - (int64_t)iy * W);
+        int oy_lo, oy_hi, ox_lo, ox_hi;
+        bilin_cover(iy, H, OH, align, oy_lo, oy_hi);
+        bilin_cover(ix, W, OW, align, ox_lo, ox_hi);
+        float v = 0.f;
+        for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+            const float wy = bilin_weight(oy, iy, H, OH, align);
+            if (wy == 0.f) continue;
+            const float* grow = gn + (size_t)oy * OW * g_cs + c;
+            float rs = 0.f;
+            for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+                const float wx = bilin_weight(ox, ix, W, OW, align);
+                if (wx != 0.f) rs += wx * grow[(size_t)ox * g_cs];
+            }
+            v += wy * rs;
+        }
+        gx[((size_t)n * H * W + ip) * gx_cs + c] = v;
     }
 }
 
 extern "C" int adh_bilinear_bwd(void* stream, const float* g, int g_cs, int N, int H, int W, int C, int OH, int OW,
                                 int align_corners, float* gx, int gx_cs) {
-    if (!g || !gx || C < 1) return ADH_E_ARG;
-    hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)OH * OW * C, 256), 4096), N), dim3(256), 0,
+    if (!g || !gx || C < 1 || H < 1 || W < 1 || OH < 1 || OW < 1) return ADH_E_ARG;
+    hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)H * W * C, 256), 4096), N), dim3(256), 0,
                        (hipStream_t)stream, g, g_cs, H, W, C, OH, OW, align_corners, gx, gx_cs);
     return adh_check_launch();
 }

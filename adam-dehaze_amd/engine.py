@@ -1123,7 +1123,7 @@ class Engine:
                 o.grad = None
                 if g is None or not x.needs_grad:
                     return
-                gx = self._f(N, Hh, Ww, Cc, zero=True)
+                gx = self._f(N, Hh, Ww, Cc)
                 H.call("adh_bilinear_bwd", g.data_ptr(), g.stride(2), N, Hh, Ww, Cc, OH, OW, int(align_corners),
                        gx.data_ptr(), Cc)
                 self.accum(x, gx)
@@ -1410,8 +1410,9 @@ class Engine:
                 if g is None:
                     return
                 nb = H.value("adh_head_blend_bwd_num_blocks", N, Hh, Ww)
-                g_r = self._f(N, Hh, Ww, r.t.shape[3])
-                g_gd = self._f(N, Hh, Ww, gd.t.shape[3]) if gd else None
+                # the kernel writes r.cs / gd.cs floats per pixel (zeros past channel 3 / 1): size by the pixel strides
+                g_r = self._f(N, Hh, Ww, r.cs)
+                g_gd = self._f(N, Hh, Ww, gd.cs) if gd else None
                 ga_partial = self._f(nb) if mode == 0 else None
                 H.call("adh_head_blend_bwd", mode, g.data_ptr(), x_img.data_ptr(), r.t.data_ptr(), r.cs,
                        H.ptr(gd.t if gd else None), gd.cs if gd else 0, H.ptr(alpha), N, Hh, Ww, g_r.data_ptr(),
