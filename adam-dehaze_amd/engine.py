@@ -832,23 +832,30 @@ class Engine:
                    work=4.0 * P * Cout * (3 if res_t is not None else 2))     # bytes: read y (+ residual), write out
             saved = ("train", y, mean, invstd, ss, mbits)
         elif bn is not None:
-            scale, shift = self._f(Cout), self._f(Cout)
-            H.call("adh_bn_fold_eval", Cout, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                   bn.running_var.data_ptr(), bn.eps, H.ptr(b), scale.data_ptr(), shift.data_ptr())
-            if act_code in (H.ACT_NONE, H.ACT_RELU):
+            # frozen statistics with trainable gamma / beta (fine-tuning under module.eval()): d-gamma needs
+            # xhat = (y - running_mean) * invstd, which the block output cannot give back where gamma == 0, so the raw conv
+            # output y is kept, as for the MobileNet activations
+            bn_trains = self.record and (bn.weight.requires_grad or bn.bias.requires_grad)
+            if act_code in (H.ACT_NONE, H.ACT_RELU) and not bn_trains:
+                scale, shift = self._f(Cout), self._f(Cout)
+                H.call("adh_bn_fold_eval", Cout, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                       bn.running_var.data_ptr(), bn.eps, H.ptr(b), scale.data_ptr(), shift.data_ptr())
                 self._run_gather(plans, x, out, Cout, w, scale=scale, shift=shift, residual=res_t, act=act_code)
                 saved = ("eval", scale)
             else:
-                # the MFMA conv epilogues know NONE / RELU only: the raw conv, then the folded BN + activation in one pass (the
-                # two passes train mode takes); y is kept for the derivative at the pre-activation
-                assert res_t is None, "a MobileNet activation after a residual add is not a layer of any supported network"
+                # the MFMA conv epilogues know NONE / RELU only: the raw conv (+ its bias), then the folded BN (+ residual) +
+                # activation in one pass (the two passes train mode takes); y is kept for xhat and the derivative at the
+                # pre-activation
+                assert res_t is None or act_code in (H.ACT_NONE, H.ACT_RELU), \
+                    "a MobileNet activation after a residual add is not a layer of any supported network"
                 y = self._f(N, OH, OW, _round_up(Cout, 4))
-                self._run_gather(plans, x, y, Cout, w)
+                self._run_gather(plans, x, y, Cout, w, shift=b)
                 ss = self._f(2, _round_up(Cout, 4), zero=True)
-                ss[0, :Cout].copy_(scale)
-                ss[1, :Cout].copy_(shift)
-                H.call("adh_bn_apply", y.data_ptr(), y.stride(2), ss[0].data_ptr(), ss[1].data_ptr(), None, 0, act_code,
-                       out.data_ptr(), out.stride(2), P, Cout, None, work=4.0 * P * Cout * 2)
+                H.call("adh_bn_fold_eval", Cout, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                       bn.running_var.data_ptr(), bn.eps, None, ss[0].data_ptr(), ss[1].data_ptr())
+                H.call("adh_bn_apply", y.data_ptr(), y.stride(2), ss[0].data_ptr(), ss[1].data_ptr(), H.ptr(res_t),
+                       res_t.stride(2) if res_t is not None else 0, act_code, out.data_ptr(), out.stride(2), P, Cout, None,
+                       work=4.0 * P * Cout * (3 if res_t is not None else 2))
                 saved = ("eval_act", y, ss)
         else:
             self._run_gather(plans, x, out, Cout, w, shift=b, residual=res_t, act=act_code)
@@ -927,7 +934,9 @@ class Engine:
             if b is not None:   # a bias feeding train-mode BN has an exactly zero gradient
                 self.add_param_grad(b, self._f(Cout, zero=True))
         elif mode == "eval_act":
-            self._bn_act_eval_backward(g, saved[1], saved[2], bn, act_code, g_y, P, Cout)
+            # with a residual the ReLU mask cannot be recomputed from y: it is read from the block output
+            self._bn_act_eval_backward(g, saved[1], saved[2], bn, act_code, g_y, P, Cout,
+                                       out=o if residual is not None else None, g_res=g_res)
             if b is not None:
                 self.add_param_grad(b, self._channel_sum(g_y, Cout))
         else:
@@ -939,32 +948,6 @@ class Engine:
             H.call("adh_bn_bwd_apply", g.data_ptr(), g.stride(2), o.t.data_ptr(), o.cs, act_code, None, 0, None, None,
                    coef.data_ptr(), 0, g_y.data_ptr(), g_y.stride(2), H.ptr(g_res),
                    g_res.stride(2) if g_res is not None else 0, P, C4, None, None)
-            if mode == "eval" and (bn.weight.requires_grad or bn.bias.requires_grad):
-                # frozen-statistics BN (fine-tuning under module.eval()): dbeta = sum(g'), dgamma = sum(g' * xhat) with
-                # xhat = (out_pre - beta) / gamma recovered from the block output (where the ReLU mask is off g' is 0 and
-                # xhat does not matter); the train-mode reduction kernels do the sums
-                pre = o.t
-                if residual is not None:     # out_pre = out - residual (rare path: one extra pass)
-                    pre = o.t[..., :C4].clone() if o.t.shape[3] >= C4 and o.t[..., :C4].is_contiguous() else None
-                    if pre is None:
-                        pre = self._f(N, OH, OW, C4)
-                        H.call("adh_axpby_strided", pre.data_ptr(), C4, o.t.data_ptr(), o.cs, P, C4, 0.0, 1.0)
-                    H.call("adh_axpby_strided", pre.data_ptr(), pre.stride(2), residual.t.data_ptr(), residual.cs, P, C4,
-                           1.0, -1.0)
-                vmean, vinv = self._f(C4), self._f(C4)
-                H.call("adh_bn_eval_bwd_vectors", Cout, C4, bn.weight.data_ptr(), bn.bias.data_ptr(), vmean.data_ptr(),
-                       vinv.data_ptr())
-                nblk = H.value("adh_bn_bwd_num_blocks", P, C4)
-                partial = self._f(nblk, 2, C4)
-                H.call("adh_bn_bwd_reduce", g.data_ptr(), g.stride(2), o.t.data_ptr(), o.cs, act_code, pre.data_ptr(),
-                       pre.stride(2), vmean.data_ptr(), vinv.data_ptr(), partial.data_ptr(), P, C4, None, None)
-                dgamma, dbeta, scratch = self._f(C4), self._f(C4), self._f(3, C4)
-                ones = self._f(C4)
-                ones.fill_(1.0)
-                H.call("adh_bn_bwd_finalize", partial.data_ptr(), nblk, C4, float(P), ones.data_ptr(), ones.data_ptr(),
-                       dgamma.data_ptr(), dbeta.data_ptr(), 0, scratch.data_ptr())
-                self.add_param_grad(bn.weight, dgamma[:Cout])
-                self.add_param_grad(bn.bias, dbeta[:Cout])
             if b is not None:
                 self.add_param_grad(b, self._channel_sum(g_y, Cout))
         if g_res is not None:
@@ -1182,15 +1165,20 @@ class Engine:
 
     # ------------------------------------------------------------------ MobileNetV2 / V3 (torchvision) building blocks
     def _bn_act_eval_backward(self, g: torch.Tensor, y: torch.Tensor, ss: torch.Tensor, bn: BNState, act_code: int,
-                              g_y: torch.Tensor, P: int, Cc: int):
-        """Backward of out = act(y * scale + shift) with frozen BatchNorm statistics (scale / shift = ss[0] / ss[1], folded
-        from the running estimates): g_y = scale * act'(z) * g, and d-gamma / d-beta when the BN parameters train."""
+                              g_y: torch.Tensor, P: int, Cc: int, out: Optional[Act] = None,
+                              g_res: Optional[torch.Tensor] = None):
+        """Backward of out = act(y * scale + shift (+ residual)) with frozen BatchNorm statistics (scale / shift =
+        ss[0] / ss[1], folded from the running estimates): g_y = scale * act'(z) * g, g_res = act'(z) * g, and d-gamma /
+        d-beta when the BN parameters train.  `out`: the block output of a residual tail (NONE / RELU), whose ReLU mask is
+        read from it."""
         C4 = _round_up(Cc, 4)
         coef = self._f(3, C4, zero=True)
         coef[0].copy_(ss[0])
-        mask_ss = ss.data_ptr() if act_code != H.ACT_NONE else None
-        H.call("adh_bn_bwd_apply", g.data_ptr(), g.stride(2), None, 0, act_code, y.data_ptr(), y.stride(2), None, None,
-               coef.data_ptr(), 0, g_y.data_ptr(), g_y.stride(2), None, 0, P, C4, mask_ss, None)
+        mask_ss = ss.data_ptr() if (act_code != H.ACT_NONE and out is None) else None
+        o_ptr, o_cs = (out.t.data_ptr(), out.cs) if out is not None else (None, 0)
+        H.call("adh_bn_bwd_apply", g.data_ptr(), g.stride(2), o_ptr, o_cs, act_code, y.data_ptr(), y.stride(2), None, None,
+               coef.data_ptr(), 0, g_y.data_ptr(), g_y.stride(2), H.ptr(g_res), g_res.stride(2) if g_res is not None else 0,
+               P, C4, mask_ss, None)
         if not (bn.weight.requires_grad or bn.bias.requires_grad):
             return
         # xhat = (y - running_mean) * invstd; adh_bn_fold_eval without gamma / beta gives invstd as its scale
@@ -1200,7 +1188,7 @@ class Engine:
                inv4.data_ptr(), junk.data_ptr())
         nblk = H.value("adh_bn_bwd_num_blocks", P, C4)
         partial = self._f(nblk, 2, C4)
-        H.call("adh_bn_bwd_reduce", g.data_ptr(), g.stride(2), None, 0, act_code, y.data_ptr(), y.stride(2), mean4.data_ptr(),
+        H.call("adh_bn_bwd_reduce", g.data_ptr(), g.stride(2), o_ptr, o_cs, act_code, y.data_ptr(), y.stride(2), mean4.data_ptr(),
                inv4.data_ptr(), partial.data_ptr(), P, C4, mask_ss, None)
         dgamma, dbeta, scratch = self._f(C4), self._f(C4), self._f(3, C4)
         H.call("adh_bn_bwd_finalize", partial.data_ptr(), nblk, C4, float(P), None, inv4.data_ptr(), dgamma.data_ptr(),
