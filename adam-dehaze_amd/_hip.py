@@ -208,6 +208,12 @@ _SIGNATURES = {
     "adh_channel_scale": [vp, vp, i32, vp, i32, i32, i32, vp, i32],
     "adh_channel_scale_bwd_num_blocks": [i32, i32],
     "adh_channel_scale_bwd": [vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, i32, vp, i32, vp],
+    "adh_bn_slice_stats_num_blocks": [i64, i32],
+    "adh_bn_slice_stats": [vp, vp, i32, i64, i32, vp],
+    "adh_bn_slice_moments": [vp, vp, i32, i32, i32, f64, vp, vp],
+    "adh_bn_fold_moments": [vp, i32, vp, vp, f64, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp],
+    "adh_avgpool2_bwd": [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32],
+    "adh_bn_preact_bwd_accum": [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, i32, i64, i32, i32],
 }
 
 # functions that return a count / size rather than a status code
@@ -215,7 +221,8 @@ _VALUE_FUNCS = {"adh_version", "adh_conv_fewout_supported", "adh_conv_fewin_supp
                 "adh_conv_wino32_num_blocks", "adh_conv_wgrad_wino_groups", "adh_conv_wgrad_wino32_groups", "adh_conv_wgrad_wino32_classes", "adh_conv_wgrad_wino32_tiles", "adh_conv_wgrad_wino43_groups", "adh_conv_wgrad_wino43_strips", "adh_conv_wgrad_small_slabs", "adh_conv_wgrad_stem_slabs", "adh_conv_stem_num_blocks", "adh_conv_wgrad_slabs", "adh_conv_wgrad_groups", "adh_conv_lds_bytes", "adh_conv_num_blocks", "adh_bn_bwd_num_blocks",
                 "adh_cbam_pool_num_blocks", "adh_cbam_bwd_b_num_blocks", "adh_head_blend_bwd_num_blocks",
                 "adh_reduce_num_blocks", "adh_lpips_layer_num_blocks", "adh_adam_chunk_elems", "adh_nms_words", "adh_augment_num_blocks", "adh_psnr_num_blocks", "adh_cbam_bwd_d_scratch_floats",
-                "adh_ssim_num_blocks", "adh_dwconv_num_blocks", "adh_dwconv_wgrad_num_blocks", "adh_channel_scale_bwd_num_blocks"}
+                "adh_ssim_num_blocks", "adh_dwconv_num_blocks", "adh_dwconv_wgrad_num_blocks", "adh_channel_scale_bwd_num_blocks",
+                "adh_bn_slice_stats_num_blocks"}
 
 _ERRORS = {-1: "ADH_E_ARG (bad argument: shape / alignment / null pointer)",
            -2: "ADH_E_LAUNCH (hip kernel launch failed)",

@@ -6,7 +6,10 @@ state_dict keys (`backbone.*`, `classifier.{1,4}.*`).  Backbones built here:
   resnet18 / resnet34 / resnet50  (reference default: resnet18, classifier.py:24-36; resnet50: Bottleneck
                         [3, 4, 6, 3], feature_dim 2048, classifier.py:31-33)  -- forward and backward
   densenet121          (the north-star's HDEN backbone; the reference itself raises for this name,
-                        classifier.py:69: build-side extension)             -- forward (eval) only
+                        classifier.py:69: build-side extension)             -- forward and backward: every block's features
+                        in one buffer written in place; train-mode pre-activation BatchNorm statistics taken once per
+                        channel and folded per layer, input gradients added into one gradient buffer per block
+                        (densenet.hip)
   mobilenet_v2 / mobilenet_v3_large / mobilenet_v3_small  (classifier.py:50-66; torchvision's architectures restated
                         with its key names under backbone.features.*, classifier = Identity; feature_dim 1280 / 960 / 576)
                         -- forward and backward: depthwise convolutions on depthwise.hip, ReLU6 / Hardswish /
@@ -179,7 +182,7 @@ class _DenseNet121(nn.Module):
 
     def run(self, eng: Engine, x8: Act, tr: bool) -> Act:
         if tr or eng.record:
-            raise RuntimeError("densenet121 backbone is forward-only (eval mode, no gradients) in this build")
+            return self._run_grad(eng, x8, tr)
         f = self.features
         h = eng.conv(x8, f.conv0.weight, None, f.norm0.state(), k=7, stride=2, pad=3, relu=True, training=False)
         h = eng.maxpool(h, 3, 2, 1)
@@ -206,6 +209,47 @@ class _DenseNet121(nn.Module):
                 h = eng.avgpool(a, 2)
                 c //= 2
         h = eng.bn_relu_eval(h, f.norm5.state())
+        return eng.global_avgpool(h)
+
+    def _run_grad(self, eng: Engine, x8: Act, tr: bool) -> Act:
+        """Train mode (batch statistics) or eval mode with gradients (frozen statistics, trainable gamma / beta).  Each block
+        buffer has one gradient buffer that every reader of a channel slice adds into (Engine.bn_relu_preact); in train mode
+        the per-channel batch moments are taken once per channel -- the block input by one reduce, each growth slice in its
+        conv2's epilogue -- and every norm1 / transition norm / norm5 folds its own gamma / beta from them."""
+        f = self.features
+        h = eng.conv(x8, f.conv0.weight, None, f.norm0.state(), k=7, stride=2, pad=3, relu=True, training=tr)
+        h = eng.maxpool(h, 3, 2, 1)
+        c = 64
+        for bi, nl in enumerate(DENSENET121_BLOCKS, start=1):
+            block = getattr(f, f"denseblock{bi}")
+            N, Hh, Ww = h.N, h.Hh, h.Ww
+            total = c + 32 * nl
+            buf = eng._f(N, Hh, Ww, total)
+            sink = {"g": None, "C": total}
+            eng.dense_input(h, buf, sink)
+            moments = None
+            if tr:
+                moments = tuple(torch.empty(total, device=buf.device, dtype=torch.float64) for _ in range(2))
+                eng.dense_moments(Act(buf[..., :c], c), moments, 0)
+            for li in range(1, nl + 1):
+                layer = getattr(block, f"denselayer{li}")
+                a = eng.bn_relu_preact(Act(buf[..., :c], c), layer.norm1.state(), tr, moments, sink)
+                b = eng.conv(a, layer.conv1.weight, None, layer.norm2.state(), k=1, stride=1, pad=0, relu=True, training=tr)
+                stats = [] if tr else None
+                o = eng.conv(b, layer.conv2.weight, None, None, k=3, stride=1, pad=1, relu=False, out=buf[..., c:c + 32],
+                             stats=stats)
+                eng.dense_output(o, sink, c)
+                if tr:
+                    eng.dense_moments(o, moments, c, partials=stats[0])
+                c += 32
+            h = Act(buf, c)
+            if bi < 4:
+                tr_ = getattr(f, f"transition{bi}")
+                a = eng.bn_relu_preact(h, tr_.norm.state(), tr, moments, sink)
+                a = eng.conv(a, tr_.conv.weight, None, None, k=1, stride=1, pad=0, relu=False)
+                h = eng.avgpool(a, 2)
+                c //= 2
+        h = eng.bn_relu_preact(h, f.norm5.state(), tr, moments, sink)
         return eng.global_avgpool(h)
 
 

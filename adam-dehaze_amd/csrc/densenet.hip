@@ -1,0 +1,264 @@
+// DenseNet121 training passes (torchvision densenet.py _DenseLayer / _Transition / norm5), gfx950.
+// A dense block keeps all of its features in one NHWC buffer [N,H,W,c0 + 32 L] written in place; every layer's norm1 is a
+// pre-activation BatchNorm + ReLU over the channel slice [0, c) of that buffer (channel stride = the buffer's width).
+// Train-mode batch statistics are per channel and do not depend on the layer, so they are taken once per channel --
+// the block input by adh_bn_slice_stats, each 32-channel growth slice by its conv2's epilogue -- kept as fp64 moments of the
+// whole buffer, and every BatchNorm only folds its own gamma / beta (adh_bn_fold_moments).  The backward pass adds each
+// layer's input gradient into the one gradient buffer of the block (adh_bn_preact_bwd_accum).  Streaming kernels: 16 B per
+// lane, a channel quad per thread, per-block partial sums reduced in a fixed order (bit-reproducible).
+#include "common.h"
+
+// ---------------------------------------------------------------------------------------------
+// statistics of a strided channel slice: partials[b][0][c] = sum x, partials[b][1][c] = sum x^2 over pixel block b
+// (the layout adh_bn_finalize / adh_bn_partial_sums / adh_bn_slice_moments read, pitch C)
+// ---------------------------------------------------------------------------------------------
+#define SS_PPB 512     // pixels per block (as adh_bn_bwd_reduce)
+#define SS_UNROLL 4
+
+extern "C" int adh_bn_slice_stats_num_blocks(int64_t P, int C) {
+    (void)C;
+    return P < 1 ? ADH_E_ARG : adh_ceil_div(P, SS_PPB);
+}
+
+__global__ __launch_bounds__(256) void bn_slice_stats_kernel(const float* __restrict__ x, int x_cs, int64_t P, int C,
+                                                             float* __restrict__ partials) {
+    __shared__ f32x4 red[2][256];
+    for (int cbase = 0; cbase < C; cbase += 1024) {     // channel groups of <= 1024 (256 quads, one per thread)
+        const int CQ = (C - cbase < 1024 ? C - cbase : 1024) / 4;
+        const int R = 256 / CQ;                          // pixel rows handled concurrently
+        const int cq = threadIdx.x % CQ;
+        const int prow = threadIdx.x / CQ;
+        const int c = cbase + cq * 4;
+        f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = s;
+        if (prow < R) {
+            const int64_t p0 = (int64_t)blockIdx.x * SS_PPB;
+            const int64_t p1 = p0 + SS_PPB < P ? p0 + SS_PPB : P;
+            for (int64_t p = p0 + prow; p < p1; p += SS_UNROLL * R) {
+                f32x4 v[SS_UNROLL];
+#pragma unroll
+                for (int u = 0; u < SS_UNROLL; ++u) {
+                    const int64_t r = p + u * R < p1 ? p + u * R : p;
+                    v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + r * x_cs + c));
+                }
+#pragma unroll
+                for (int u = 0; u < SS_UNROLL; ++u)
+                    if (p + u * R < p1) {
+                        s += v[u];
+                        q += v[u] * v[u];
+                    }
+            }
+        }
+        red[0][threadIdx.x] = s;
+        red[1][threadIdx.x] = q;
+        __syncthreads();
+        if (threadIdx.x < CQ) {
+            f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a;
+            for (int r = 0; r < R; ++r) {
+                a += red[0][r * CQ + threadIdx.x];
+                b += red[1][r * CQ + threadIdx.x];
+            }
+            *reinterpret_cast<f32x4*>(partials + ((size_t)blockIdx.x * 2 + 0) * C + c) = a;
+            *reinterpret_cast<f32x4*>(partials + ((size_t)blockIdx.x * 2 + 1) * C + c) = b;
+        }
+        __syncthreads();   // the next channel group reuses `red`
+    }
+}
+
+extern "C" int adh_bn_slice_stats(void* stream, const float* x, int x_cs, int64_t P, int C, float* partials) {
+    if (!x || !partials || P < 1 || C < 4 || (C & 3) || C > 4096 || x_cs < C || (x_cs & 3)) return ADH_E_ARG;
+    hipLaunchKernelGGL(bn_slice_stats_kernel, dim3(adh_bn_slice_stats_num_blocks(P, C)), dim3(256), 0, (hipStream_t)stream, x,
+                       x_cs, P, C, partials);
+    return adh_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------
+// partials[nblk][2][pitch] (sum, sum of squares) -> fp64 mean[c] and biased variance var[c] (fixed-order fp64 reduce)
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void bn_slice_moments_kernel(const float* __restrict__ partials, int nblk, int pitch, int C,
+                                                                double count, double* __restrict__ mean,
+                                                                double* __restrict__ var) {
+    __shared__ double red[2][32][33];
+    const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
+    const int c = blockIdx.x * 32 + cx;
+    double s0 = 0.0, s1 = 0.0, q0 = 0.0, q1 = 0.0;
+    if (c < C) {
+        int b = ry;
+        for (; b + 32 < nblk; b += 64) {
+            s0 += (double)partials[((size_t)b * 2 + 0) * pitch + c];
+            q0 += (double)partials[((size_t)b * 2 + 1) * pitch + c];
+            s1 += (double)partials[((size_t)(b + 32) * 2 + 0) * pitch + c];
+            q1 += (double)partials[((size_t)(b + 32) * 2 + 1) * pitch + c];
+        }
+        for (; b < nblk; b += 32) {
+            s0 += (double)partials[((size_t)b * 2 + 0) * pitch + c];
+            q0 += (double)partials[((size_t)b * 2 + 1) * pitch + c];
+        }
+    }
+    red[0][ry][cx] = s0 + s1;
+    red[1][ry][cx] = q0 + q1;
+    __syncthreads();
+    if (ry == 0 && c < C) {
+        double S = 0.0, Q = 0.0;
+        for (int r = 0; r < 32; ++r) {
+            S += red[0][r][cx];
+            Q += red[1][r][cx];
+        }
+        const double m = S / count;
+        const double v = Q / count - m * m;
+        mean[c] = m;
+        var[c] = v < 0.0 ? 0.0 : v;
+    }
+}
+
+extern "C" int adh_bn_slice_moments(void* stream, const float* partials, int nblk, int pitch, int C, double count, double* mean,
+                                    double* var) {
+    if (!partials || !mean || !var || nblk < 1 || C < 1 || pitch < C || count <= 0) return ADH_E_ARG;
+    hipLaunchKernelGGL(bn_slice_moments_kernel, dim3(adh_ceil_div(C, 32)), dim3(1024), 0, (hipStream_t)stream, partials, nblk,
+                       pitch, C, count, mean, var);
+    return adh_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------
+// one BatchNorm2d of the block from the shared moments: scale / shift / mean / invstd and nn.BatchNorm2d's buffer update
+// (momentum, unbiased running variance, num_batches_tracked += 1) -- adh_bn_finalize's arithmetic after its reduce
+// ---------------------------------------------------------------------------------------------
+__global__ void bn_fold_moments_kernel(int C, const double* __restrict__ mean, const double* __restrict__ var, double count,
+                                       const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                       float momentum, float* running_mean, float* running_var, float* scale, float* shift,
+                                       float* save_mean, float* save_invstd, int64_t* num_batches_tracked) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const double m = mean[c], v = var[c];
+    const double invstd = 1.0 / sqrt(v + (double)eps);
+    const float gm = gamma ? gamma[c] : 1.f;
+    const float bt = beta ? beta[c] : 0.f;
+    scale[c] = (float)(gm * invstd);
+    shift[c] = (float)(bt - m * gm * invstd);
+    if (save_mean) save_mean[c] = (float)m;
+    if (save_invstd) save_invstd[c] = (float)invstd;
+    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
+    if (running_var) {
+        const double unbiased = count > 1.0 ? v * count / (count - 1.0) : v;
+        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+    }
+    if (num_batches_tracked && c == 0) *num_batches_tracked += 1;
+}
+
+extern "C" int adh_bn_fold_moments(void* stream, int C, const double* mean, const double* var, double count, const float* gamma,
+                                   const float* beta, float eps, float momentum, float* running_mean, float* running_var,
+                                   float* scale, float* shift, float* save_mean, float* save_invstd,
+                                   int64_t* num_batches_tracked) {
+    if (C < 1 || !mean || !var || !scale || !shift || count <= 0) return ADH_E_ARG;
+    hipLaunchKernelGGL(bn_fold_moments_kernel, dim3(adh_ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, C, mean, var, count,
+                       gamma, beta, eps, momentum, running_mean, running_var, scale, shift, save_mean, save_invstd,
+                       num_batches_tracked);
+    return adh_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------
+// AvgPool2d(2, 2) backward with F.avg_pool2d's floor: gx[n][iy][ix] = g[n][iy/2][ix/2] / 4 for iy < 2 OH, ix < 2 OW, and 0
+// in the dropped last row / column of an odd H / W.  accumulate != 0: gx += instead of gx =.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void avgpool2_bwd_kernel(const float* __restrict__ g, int g_cs, int H, int W, int CQ,
+                                                           float* __restrict__ gx, int gx_cs, int accumulate) {
+    const int n = blockIdx.y;
+    const int OH = H >> 1, OW = W >> 1;
+    const int64_t total = (int64_t)H * W * CQ;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t ip = t / CQ;
+        const int c = (int)(t - ip * CQ) * 4;
+        const int iy = (int)(ip / W), ix = (int)(ip - (int64_t)iy * W);
+        const int oy = iy >> 1, ox = ix >> 1;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (oy < OH && ox < OW)
+            v = *reinterpret_cast<const f32x4*>(g + ((size_t)n * OH * OW + (size_t)oy * OW + ox) * g_cs + c) * 0.25f;
+        f32x4* d = reinterpret_cast<f32x4*>(gx + ((size_t)n * H * W + ip) * gx_cs + c);
+        if (accumulate) v += *d;
+        *d = v;
+    }
+}
+
+extern "C" int adh_avgpool2_bwd(void* stream, const float* g, int g_cs, int N, int H, int W, int C, float* gx, int gx_cs,
+                                int accumulate) {
+    if (!g || !gx || N < 1 || H < 2 || W < 2 || C < 4 || (C & 3) || g_cs < C || gx_cs < C || (g_cs & 3) || (gx_cs & 3))
+        return ADH_E_ARG;
+    hipLaunchKernelGGL(avgpool2_bwd_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)H * W * (C / 4), 256), 4096), N), dim3(256), 0,
+                       (hipStream_t)stream, g, g_cs, H, W, C / 4, gx, gx_cs, accumulate);
+    return adh_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------
+// pre-activation BatchNorm + ReLU backward into the block's gradient buffer:
+//   m = [fma(x, scale, shift) > 0] (the forward expression, from x and the layer's folded scale / shift = ss[0] / ss[1])
+//   training:  dx = coef0 * (m dA - coef1 - (x - mean) * invstd * coef2)   (coef = adh_bn_bwd_finalize's [3][C] output:
+//              gamma * invstd, mean(m dA), mean(m dA xhat))
+//   frozen statistics: dx = coef0 * m dA   (coef0 = the folded scale)
+//   dbuf[p][c] += dx (accumulate != 0) or = dx, at dbuf's channel stride
+// ---------------------------------------------------------------------------------------------
+#define PB_MAXBLK (256 * 32)   // the three-stream grid cap adh_bn_bwd_apply measured fastest
+#define PB_UNROLL 8
+
+__global__ __launch_bounds__(256) void bn_preact_bwd_accum_kernel(const float* __restrict__ dA, int dA_cs,
+                                                                  const float* __restrict__ x, int x_cs,
+                                                                  const float* __restrict__ ss, const float* __restrict__ mean,
+                                                                  const float* __restrict__ invstd,
+                                                                  const float* __restrict__ coef, int training,
+                                                                  float* __restrict__ dbuf, int dbuf_cs, int64_t P, int C,
+                                                                  int accumulate) {
+    const int CQ = C / 4;
+    const int64_t t = blockIdx.x * (int64_t)256 + threadIdx.x;
+    const int64_t pstep = (int64_t)gridDim.x * 256 / CQ;
+    int64_t p = t / CQ;
+    const int c = (int)(t - p * CQ) * 4;
+    const f32x4 k0 = *reinterpret_cast<const f32x4*>(coef + c);
+    const f32x4 msc = *reinterpret_cast<const f32x4*>(ss + c);
+    const f32x4 msh = *reinterpret_cast<const f32x4*>(ss + C + c);
+    f32x4 mg = {0.f, 0.f, 0.f, 0.f}, kx = mg, mu = mg;
+    if (training) {
+        mg = *reinterpret_cast<const f32x4*>(coef + C + c);
+        mu = *reinterpret_cast<const f32x4*>(mean + c);
+        kx = *reinterpret_cast<const f32x4*>(invstd + c) * *reinterpret_cast<const f32x4*>(coef + 2 * C + c);
+    }
+    for (; p < P; p += PB_UNROLL * pstep) {
+        f32x4 g[PB_UNROLL], xx[PB_UNROLL], d[PB_UNROLL];
+#pragma unroll
+        for (int u = 0; u < PB_UNROLL; ++u) {
+            const int64_t q = p + u * pstep < P ? p + u * pstep : p;
+            g[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(dA + q * dA_cs + c));
+            xx[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + q * x_cs + c));
+            if (accumulate) d[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(dbuf + q * dbuf_cs + c));
+        }
+#pragma unroll
+        for (int u = 0; u < PB_UNROLL; ++u) {
+            const int64_t q = p + u * pstep;
+            if (q < P) {
+                f32x4 gg = g[u];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) gg[j] = fmaf(xx[u][j], msc[j], msh[j]) > 0.f ? gg[j] : 0.f;
+                f32x4 r = training ? k0 * (gg - mg - (xx[u] - mu) * kx) : k0 * gg;
+                if (accumulate) r += d[u];
+                __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(dbuf + q * dbuf_cs + c));
+            }
+        }
+    }
+}
+
+extern "C" int adh_bn_preact_bwd_accum(void* stream, const float* dA, int dA_cs, const float* x, int x_cs, const float* ss,
+                                       const float* mean, const float* invstd, const float* coef, int training, float* dbuf,
+                                       int dbuf_cs, int64_t P, int C, int accumulate) {
+    if (!dA || !x || !ss || !coef || !dbuf || P < 1 || C < 4 || (C & 3) || dA_cs < C || x_cs < C || dbuf_cs < C ||
+        ((dA_cs | x_cs | dbuf_cs) & 3))
+        return ADH_E_ARG;
+    if (training && (!mean || !invstd)) return ADH_E_ARG;
+    const int CQ = C / 4;
+    int g = CQ, r = 256;   // blocks: a multiple of CQ / gcd(CQ, 256), so that a thread keeps one channel quad
+    while (r) { const int t = g % r; g = r; r = t; }
+    const int mult = CQ / g;
+    int64_t want = (P * CQ + 256 * PB_UNROLL - 1) / (256 * PB_UNROLL);
+    if (want > PB_MAXBLK) want = PB_MAXBLK;
+    int64_t blocks = (want + mult - 1) / mult * mult;
+    if (blocks < mult) blocks = mult;
+    hipLaunchKernelGGL(bn_preact_bwd_accum_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dA, dA_cs, x, x_cs,
+                       ss, mean, invstd, coef, training, dbuf, dbuf_cs, P, C, accumulate);
+    return adh_check_launch();
+}

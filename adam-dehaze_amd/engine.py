@@ -774,12 +774,15 @@ class Engine:
     def conv(self, x: Act, w: torch.Tensor, b: Optional[torch.Tensor], bn: Optional[BNState], *, kind: str = "conv",
              k: int = 3, stride: int = 1, pad: int = 1, relu: bool = True, residual: Optional[Act] = None,
              training: bool = False, out: Optional[torch.Tensor] = None, out_alloc_C: Optional[int] = None,
-             act: Optional[int] = None) -> Act:
+             act: Optional[int] = None, stats: Optional[list] = None) -> Act:
         """ConvBlock / ConvTranspose+BN+ReLU / bare Conv2d as one fused op
         (base_model.py:4-24,26-41; medium_intensity.py:52-56).  `residual` is added after BN and before the
         ReLU (ResidualBlock tail).  `out`: optional preallocated [N,OH,OW,>=Cout] view to write into.
         `act`: an H.ACT_* code, default from `relu`; ReLU6 / Hardswish / Hardsigmoid (MobileNet) need a BatchNorm and no
-        residual, and run through adh_bn_apply after the raw conv in both modes."""
+        residual, and run through adh_bn_apply after the raw conv in both modes.
+        `stats`: a list, for a bare convolution (no BatchNorm, bias, residual or activation): the launch's epilogue also
+        writes the per-block sums of its output and (partials [nblk][2][pitch], nblk, pitch) is appended (DenseNet's conv2,
+        whose output is a growth slice of the block buffer)."""
         if kind == "conv":
             Cout = w.shape[0]
             OH = (x.Hh + 2 * pad - k) // stride + 1
@@ -857,6 +860,11 @@ class Engine:
                        res_t.stride(2) if res_t is not None else 0, act_code, out.data_ptr(), out.stride(2), P, Cout, None,
                        work=4.0 * P * Cout * (3 if res_t is not None else 2))
                 saved = ("eval_act", y, ss)
+        elif stats is not None:
+            assert b is None and res_t is None and act_code == H.ACT_NONE, "stats are taken of a bare convolution only"
+            partials, nblk = self._run_gather(plans, x, out, Cout, w, want_stats=True)
+            stats.append((partials, nblk, partials.shape[2]))
+            saved = ("plain",)
         else:
             self._run_gather(plans, x, out, Cout, w, shift=b, residual=res_t, act=act_code)
             saved = ("plain",)
@@ -1144,15 +1152,30 @@ class Engine:
         return o
 
     def avgpool(self, x: Act, k: int) -> Act:
-        assert not self.record, "avgpool backward is not implemented (DenseNet121 runs forward-only)"
+        """AvgPool2d(k, stride k) with floor (torchvision densenet transition); its backward exists for k = 2."""
+        assert not self.record or k == 2, "avgpool backward is implemented for the 2x2 pool only"
         N, Hh, Ww, Cc = x.N, x.Hh, x.Ww, x.C
         out = self._f(N, Hh // k, Ww // k, Cc)
         H.call("adh_avgpool", x.t.data_ptr(), x.cs, N, Hh, Ww, Cc, k, out.data_ptr(), Cc)
-        return Act(out, Cc)
+        o = Act(out, Cc)
+        if self.record:
+            def bwd():
+                g = o.grad
+                o.grad = None
+                if g is None or not x.needs_grad:
+                    return
+                C4 = _round_up(Cc, 4)
+                gx = self._f(N, Hh, Ww, C4)
+                H.call("adh_avgpool2_bwd", g.data_ptr(), g.stride(2), N, Hh, Ww, C4, gx.data_ptr(), C4, 0,
+                       work=4.0 * (N * Hh * Ww + g.shape[0] * g.shape[1] * g.shape[2]) * Cc)   # bytes: read g, write gx
+                self.accum(x, gx)
+            self.tape.append(bwd)
+        return o
 
     def bn_relu_eval(self, x: Act, bn: BNState, out: Optional[torch.Tensor] = None) -> Act:
-        """Stand-alone eval-mode BatchNorm + ReLU (DenseNet's pre-activation norm layers)."""
-        assert not self.record, "pre-activation BN backward is not implemented (DenseNet121 runs forward-only)"
+        """Stand-alone eval-mode BatchNorm + ReLU (DenseNet's pre-activation norm layers), no gradients; with gradients or in
+        train mode: bn_relu_preact."""
+        assert not self.record, "bn_relu_eval records no backward: use bn_relu_preact"
         N, Hh, Ww, Cc = x.N, x.Hh, x.Ww, x.C
         scale, shift = self._f(Cc), self._f(Cc)
         H.call("adh_bn_fold_eval", Cc, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
@@ -1162,6 +1185,115 @@ class Engine:
         H.call("adh_bn_apply", x.t.data_ptr(), x.cs, scale.data_ptr(), shift.data_ptr(), None, 0, H.ACT_RELU,
                out.data_ptr(), out.stride(2), x.pixels, Cc, None)
         return Act(out, Cc)
+
+    # ------------------------------------------------------------------ DenseNet121 training (densenet.hip)
+    # A dense block's features live in one buffer [N,H,W,total] written in place; its gradient is one buffer of the same shape,
+    # `sink['g']`, that every consumer of a channel slice adds into (the transition / norm5, which read every channel, write it
+    # first).  Train-mode statistics are per channel and shared by every BatchNorm over the buffer: `moments` = fp64
+    # (mean[total], var[total]) filled slice by slice as the block is written.
+    def dense_moments(self, x: Act, moments: Tuple[torch.Tensor, torch.Tensor], c0: int,
+                      partials: Optional[Tuple[torch.Tensor, int, int]] = None):
+        """moments[.][c0 : c0 + x.C] = batch mean / biased variance of the channel slice x: from `partials` (a conv epilogue's
+        per-block sums, Engine.conv(stats=...)) or by one adh_bn_slice_stats pass over x."""
+        Cc, P = x.C, x.pixels
+        if partials is None:
+            nblk = H.value("adh_bn_slice_stats_num_blocks", P, Cc)
+            part = self._f(nblk, 2, Cc)
+            H.call("adh_bn_slice_stats", x.t.data_ptr(), x.cs, P, Cc, part.data_ptr(), work=4.0 * P * Cc)   # bytes: read x
+            partials = (part, nblk, Cc)
+        part, nblk, pitch = partials
+        mean, var = moments
+        H.call("adh_bn_slice_moments", part.data_ptr(), nblk, pitch, Cc, float(P), mean[c0:].data_ptr(), var[c0:].data_ptr())
+
+    def dense_input(self, h: Act, buf: torch.Tensor, sink: dict) -> None:
+        """Copy the block input into buf[..., :h.C]; its gradient is that slice of the block's gradient buffer."""
+        H.call("adh_axpby_strided", buf.data_ptr(), buf.stride(2), h.t.data_ptr(), h.cs, h.pixels, h.C, 0.0, 1.0)
+        if self.record:
+            def bwd():
+                if sink["g"] is not None:
+                    self.accum(h, sink["g"][..., :h.C])
+            self.tape.append(bwd)
+
+    def dense_output(self, o: Act, sink: dict, c0: int) -> None:
+        """`o` was written into buf[..., c0 : c0 + o.C]: before its producer's backward runs, hand it that slice of the block's
+        gradient buffer (complete by then: every later reader of the slice comes later on the tape)."""
+        if self.record:
+            def bwd():
+                if sink["g"] is not None:
+                    o.grad = sink["g"][..., c0:c0 + o.C]
+            self.tape.append(bwd)
+
+    def bn_relu_preact(self, x: Act, bn: BNState, training: bool, moments: Optional[Tuple[torch.Tensor, torch.Tensor]],
+                       sink: dict) -> Act:
+        """DenseNet's pre-activation BatchNorm + ReLU over x = buf[..., :C] of a dense block, in train mode or with gradients
+        (the no-grad eval pass is bn_relu_eval).  training: the batch statistics of `moments`, folded with this layer's gamma /
+        beta (adh_bn_fold_moments, with nn.BatchNorm2d's running-buffer update); else the running statistics (frozen BN with
+        trainable gamma / beta).  The output is materialised (the 1x1 convolution's weight gradient reads it).  Backward:
+        adh_bn_bwd_reduce of (dA, x) with the ReLU mask recomputed from x, adh_bn_bwd_finalize, then adh_bn_preact_bwd_accum
+        adds d(loss)/dx into sink['g'][..., :C] at the buffer's channel stride."""
+        N, Hh, Ww, Cc = x.N, x.Hh, x.Ww, x.C
+        P = x.pixels
+        assert Cc % 4 == 0 and x.cs % 4 == 0, "pre-activation BatchNorm needs whole channel quads"
+        if training and SYNC_BN is not None:
+            raise NotImplementedError("synchronised BatchNorm is not implemented for DenseNet's pre-activation BatchNorm")
+        ss = self._f(2, Cc)
+        mean = invstd = None
+        if training:
+            mean, invstd = self._f(Cc), self._f(Cc)
+            H.call("adh_bn_fold_moments", Cc, moments[0].data_ptr(), moments[1].data_ptr(), float(P), bn.weight.data_ptr(),
+                   bn.bias.data_ptr(), bn.eps, bn.momentum, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+                   ss[0].data_ptr(), ss[1].data_ptr(), mean.data_ptr(), invstd.data_ptr(), H.ptr(bn.num_batches_tracked))
+        else:
+            H.call("adh_bn_fold_eval", Cc, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                   bn.running_var.data_ptr(), bn.eps, None, ss[0].data_ptr(), ss[1].data_ptr())
+        out = self._f(N, Hh, Ww, Cc)
+        H.call("adh_bn_apply", x.t.data_ptr(), x.cs, ss[0].data_ptr(), ss[1].data_ptr(), None, 0, H.ACT_RELU, out.data_ptr(), Cc,
+               P, Cc, None, work=8.0 * P * Cc)                                   # bytes: read x, write out
+        o = Act(out, Cc)
+        if RELU_CAPTURE is not None:
+            RELU_CAPTURE[id(bn.weight)] = out
+        if not self.record:
+            return o
+        bn_grads = training or bn.weight.requires_grad or bn.bias.requires_grad
+        self.use_param(bn.weight if bn_grads else None, bn.bias if bn_grads else None)
+
+        def bwd():
+            g = o.grad
+            o.grad = None
+            if g is None:
+                return
+            dbuf, acc = sink["g"], 1
+            if dbuf is None:   # the first writer of the block's gradient: store, and zero what it does not cover
+                dbuf, acc = self._f(N, Hh, Ww, sink["C"]), 0
+                if Cc < sink["C"]:
+                    dbuf[..., Cc:].zero_()
+                sink["g"] = dbuf
+            coef = ss       # frozen statistics: dx = scale * m * dA (only row 0 is read)
+            if bn_grads:
+                if training:
+                    mu, inv = mean, invstd
+                else:       # xhat from the running statistics: adh_bn_fold_eval without gamma / beta gives invstd as its scale
+                    mu, inv, junk = bn.running_mean.contiguous(), self._f(Cc), self._f(Cc)
+                    H.call("adh_bn_fold_eval", Cc, None, None, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.eps,
+                           None, inv.data_ptr(), junk.data_ptr())
+                nblk = H.value("adh_bn_bwd_num_blocks", P, Cc)
+                partial = self._f(nblk, 2, Cc)
+                H.call("adh_bn_bwd_reduce", g.data_ptr(), g.stride(2), None, 0, H.ACT_RELU, x.t.data_ptr(), x.cs, mu.data_ptr(),
+                       inv.data_ptr(), partial.data_ptr(), P, Cc, ss.data_ptr(), None, work=8.0 * P * Cc)   # bytes: dA, x
+                dgamma, dbeta = self.grad_buffer(bn.weight), self.grad_buffer(bn.bias)
+                fin = self._f(3, Cc)
+                H.call("adh_bn_bwd_finalize", partial.data_ptr(), nblk, Cc, float(P), bn.weight.data_ptr() if training else None,
+                       inv.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), 0, fin.data_ptr())
+                if training:
+                    coef = fin
+            H.call("adh_bn_preact_bwd_accum", g.data_ptr(), g.stride(2), x.t.data_ptr(), x.cs, ss.data_ptr(), H.ptr(mean),
+                   H.ptr(invstd), coef.data_ptr(), int(training), dbuf.data_ptr(), dbuf.stride(2), P, Cc, acc,
+                   work=4.0 * P * Cc * (4 if acc else 3))                        # bytes: dA, x (, dbuf), write dbuf
+            if bn_grads:
+                self.add_param_grad(bn.weight, dgamma)
+                self.add_param_grad(bn.bias, dbeta)
+        self.tape.append(bwd)
+        return o
 
     # ------------------------------------------------------------------ MobileNetV2 / V3 (torchvision) building blocks
     def _bn_act_eval_backward(self, g: torch.Tensor, y: torch.Tensor, ss: torch.Tensor, bn: BNState, act_code: int,

@@ -812,3 +812,136 @@ def evaluate_detection(config, test_loader=None, steps: int = 1, score_threshold
                 if hm != 0:
                     print(f"  Improvement: {(dmap - hm) / hm * 100:.2f}%")
     return results
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Stand-alone fog-intensity classifier training (/root/reference training/train_classifier.py:13-226): Adam with the
+# classifier section's lr / weight_decay, ReduceLROnPlateau(min, 0.5, patience 5) on the validation loss, cross-entropy,
+# best-by-validation-accuracy checkpoint with the reference's keys, checkpoint_epoch_{5k}.pth, best model reloaded at the end.
+# Accuracy and the 3 x 3 confusion matrix are counted on the device (one host read per validation pass).
+# ---------------------------------------------------------------------------------------------------------------------
+CLASS_NAMES = ("low", "medium", "high")
+
+
+def classification_report3(cm) -> str:
+    """sklearn.metrics.classification_report(target_names=['low', 'medium', 'high'], digits=2) of a confusion matrix
+    (rows = true class, columns = prediction); undefined precision / recall / F1 (0 / 0) are reported as 0 as sklearn does."""
+    cm = torch.as_tensor(cm, dtype=torch.float64).cpu()
+    tp, support, predicted = cm.diag(), cm.sum(1), cm.sum(0)
+    precision = torch.where(predicted > 0, tp / predicted.clamp(min=1), torch.zeros_like(tp))
+    recall = torch.where(support > 0, tp / support.clamp(min=1), torch.zeros_like(tp))
+    f1 = torch.where(precision + recall > 0, 2 * precision * recall / (precision + recall).clamp(min=1e-300), torch.zeros_like(tp))
+    total = float(support.sum())
+    w = support / max(total, 1.0)
+    width = max(len(n) for n in CLASS_NAMES + ("weighted avg",))
+    lines = [f"{'':>{width}} {'precision':>9} {'recall':>9} {'f1-score':>9} {'support':>9}", ""]
+    for i, name in enumerate(CLASS_NAMES):
+        lines.append(f"{name:>{width}} {float(precision[i]):9.2f} {float(recall[i]):9.2f} {float(f1[i]):9.2f} {int(support[i]):9d}")
+    lines.append("")
+    acc = float(tp.sum()) / max(total, 1.0)
+    lines.append(f"{'accuracy':>{width}} {'':>9} {'':>9} {acc:9.2f} {int(total):9d}")
+    lines.append(f"{'macro avg':>{width}} {float(precision.mean()):9.2f} {float(recall.mean()):9.2f} {float(f1.mean()):9.2f} "
+                 f"{int(total):9d}")
+    lines.append(f"{'weighted avg':>{width}} {float((precision * w).sum()):9.2f} {float((recall * w).sum()):9.2f} "
+                 f"{float((f1 * w).sum()):9.2f} {int(total):9d}")
+    return "\n".join(lines) + "\n"
+
+
+def _classifier_pass(model, loader: Iterable[Dict], device, optimizer=None) -> Dict:
+    """One pass over `loader`: a training epoch when `optimizer` is given, else a no-grad evaluation.  Returns the mean
+    batch loss, the confusion matrix (numpy int64 [3, 3], rows = truth) and the sample count."""
+    from .loss import cross_entropy3
+    loss_sum = torch.zeros((), device=device, dtype=torch.float32)
+    cm = torch.zeros(9, device=device, dtype=torch.int64)
+    nb = 0
+    with torch.set_grad_enabled(optimizer is not None):
+        for batch in loader:
+            x = batch["hazy"].to(device)
+            y = batch["intensity"].to(device)
+            if optimizer is not None:
+                optimizer.zero_grad()
+            logits, _ = model(x)
+            loss = cross_entropy3(logits, y)
+            if optimizer is not None:
+                loss.backward()
+                optimizer.step()
+            loss_sum += loss.detach().reshape(())
+            cm += torch.bincount(y * 3 + logits.detach().argmax(1), minlength=9)
+            nb += 1
+    cmh = cm.view(3, 3).cpu().numpy()
+    return {"loss": float(loss_sum) / max(nb, 1), "confusion_matrix": cmh, "count": int(cmh.sum())}
+
+
+def _accuracy(cm) -> float:
+    total = int(cm.sum())
+    return 100.0 * int(cm.trace()) / total if total else 0.0
+
+
+def train_classifier(config, train_loader=None, val_loader=None, steps: int = 4, epochs: Optional[int] = None,
+                     val_steps: int = 2):
+    """training/train_classifier.py:13-185.  Without loaders: `steps` / `val_steps` batches of synthetic foggy frames per
+    epoch (labels = fog level).  Single process only (data-parallel classifier training is not built)."""
+    world, rank = _world_rank()
+    if world > 1:
+        raise RuntimeError("train_classifier runs in a single process; data-parallel classifier training is not implemented")
+    device = torch.device(config["device"])
+    cc = config["classifier"]
+    model = create_classifier(config).to(device)
+    optimizer = Adam(list(model.parameters()), lr=cc["learning_rate"], weight_decay=cc["weight_decay"])
+    scheduler = ReduceLROnPlateau(optimizer, mode="min", factor=0.5, patience=5)
+    ck_dir = cc["checkpoint_dir"]
+    os.makedirs(ck_dir, exist_ok=True)
+    epochs = cc["epochs"] if epochs is None else epochs
+    if train_loader is None or val_loader is None:
+        _warn_synthetic(config, "train_classifier", rank)
+    bs, size = config["dataset"]["batch_size"], config["dataset"]["img_size"]
+
+    def loader_for(ld, epoch, nsteps, seed_off):
+        if ld is None:
+            return synthetic_loader(bs, size, nsteps, seed=config["seed"] + seed_off + epoch, device=device)
+        return ld(epoch) if callable(ld) else ld
+
+    best_acc = -1.0      # (the reference starts at 0.0 and writes nothing if every epoch scores 0 %, then fails to reload)
+    best_path = os.path.join(ck_dir, "best_model.pth")
+    for epoch in range(epochs):
+        model.train()
+        tr = _classifier_pass(model, loader_for(train_loader, epoch, steps, 0), device, optimizer)
+        model.eval()
+        val = _classifier_pass(model, loader_for(val_loader, 0, val_steps, 500000), device)   # a fixed validation set
+        val_acc = _accuracy(val["confusion_matrix"])
+        scheduler.step(val["loss"])
+        print(f"Epoch {epoch + 1}/{epochs}:")
+        print(f"  Train Loss: {tr['loss']:.4f}, Train Acc: {_accuracy(tr['confusion_matrix']):.2f}%")
+        print(f"  Val Loss: {val['loss']:.4f}, Val Acc: {val_acc:.2f}%")
+        print(f"Confusion Matrix:\n{val['confusion_matrix']}")
+        print(f"Classification Report:\n{classification_report3(val['confusion_matrix'])}")
+        ck = {"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
+              "val_acc": val_acc, "val_loss": val["loss"]}
+        if val_acc > best_acc:
+            best_acc = val_acc
+            save_checkpoint_atomic(ck, best_path)
+            print(f"Saved best model with validation accuracy: {val_acc:.2f}%")
+        if (epoch + 1) % 5 == 0:
+            save_checkpoint_atomic(ck, os.path.join(ck_dir, f"checkpoint_epoch_{epoch + 1}.pth"))
+    if os.path.exists(best_path):
+        model.load_state_dict(torch.load(best_path, map_location="cpu")["model_state_dict"])
+    return model
+
+
+def evaluate_classifier(model, config, test_loader=None, steps: int = 2) -> Dict:
+    """training/train_classifier.py:187-226: accuracy (%), confusion matrix and the per-class report on the test split
+    (synthetic frames without a loader)."""
+    device = torch.device(config["device"])
+    model = model.to(device).eval()
+    if test_loader is None:
+        _warn_synthetic(config, "evaluate_classifier", _world_rank()[1])
+        test_loader = synthetic_loader(config["dataset"]["batch_size"], config["dataset"]["img_size"], steps,
+                                       seed=config["seed"] + 900000, device=device)
+    res = _classifier_pass(model, test_loader, device)
+    cm = res["confusion_matrix"]
+    acc = _accuracy(cm)
+    report = classification_report3(cm)
+    print(f"Test Accuracy: {acc:.2f}%")
+    print(f"Confusion Matrix:\n{cm}")
+    print(f"Classification Report:\n{report}")
+    return {"accuracy": acc, "confusion_matrix": cm, "classification_report": report}

@@ -575,6 +575,33 @@ int adh_channel_scale_bwd_num_blocks(int HW, int C);
 int adh_channel_scale_bwd(void* stream, const float* g, int g_cs, const float* x, int x_cs, const float* s, int N, int HW,
                           int C, float* gx, int gx_cs, float* partials, int nblk, float* gs);
 
+/* ---- DenseNet121 training (torchvision densenet.py; densenet.hip) ---------------------------------------------------------
+ * A dense block's features live in one NHWC buffer written in place; norm1 of each layer is a pre-activation BatchNorm + ReLU
+ * over the channel slice [0, c) of it.  Batch statistics are per channel, shared by every layer: taken once per channel into
+ * fp64 moments, then folded per layer with its own gamma / beta.
+ * adh_bn_slice_stats: partials[nblk][2][C] = (sum x, sum x^2) of pixel block b of x[P][x_cs] (channels [0, C), C % 4 == 0,
+ * C <= 4096; nblk = adh_bn_slice_stats_num_blocks), the layout adh_bn_finalize reads. */
+int adh_bn_slice_stats_num_blocks(int64_t P, int C);
+int adh_bn_slice_stats(void* stream, const float* x, int x_cs, int64_t P, int C, float* partials);
+/* fixed-order fp64 reduce of such partials (pitch >= C): mean[c] and biased variance var[c] over `count` pixels */
+int adh_bn_slice_moments(void* stream, const float* partials, int nblk, int pitch, int C, double count, double* mean,
+                         double* var);
+/* one train-mode BatchNorm2d from the moments: scale / shift (gamma * invstd, beta - mean * gamma * invstd), save_mean /
+ * save_invstd, and the running-buffer update of adh_bn_finalize (any of the outputs after shift may be NULL) */
+int adh_bn_fold_moments(void* stream, int C, const double* mean, const double* var, double count, const float* gamma,
+                        const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* scale,
+                        float* shift, float* save_mean, float* save_invstd, int64_t* num_batches_tracked);
+/* adjoint of AvgPool2d(2, 2) with floor: gx = g[iy/2][ix/2] / 4 inside the pooled area, 0 in a dropped odd row / column;
+ * accumulate != 0 adds into gx */
+int adh_avgpool2_bwd(void* stream, const float* g, int g_cs, int N, int H, int W, int C, float* gx, int gx_cs, int accumulate);
+/* pre-activation BN + ReLU backward: m = [fma(x, ss[0], ss[1]) > 0] (ss = the forward's folded scale / shift, pitch C);
+ * training: dx = coef[0] * (m dA - coef[1] - (x - mean) * invstd * coef[2]) with coef = adh_bn_bwd_finalize's output for the
+ * sums of adh_bn_bwd_reduce(dA, x, mask_ss = ss); frozen statistics (training == 0): dx = coef[0] * m dA.
+ * dbuf[p][c] += dx (accumulate != 0) or = dx, at channel stride dbuf_cs */
+int adh_bn_preact_bwd_accum(void* stream, const float* dA, int dA_cs, const float* x, int x_cs, const float* ss,
+                            const float* mean, const float* invstd, const float* coef, int training, float* dbuf, int dbuf_cs,
+                            int64_t P, int C, int accumulate);
+
 #ifdef __cplusplus
 }
 #endif

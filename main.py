@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Entry point with the reference's command line (/root/reference main.py:29-56): the modes that lie on
-the hot path run on the HIP engine; the others (dataset preprocessing, classifier training, detection
-evaluation) are outside this build's scope and say so.
+the hot path run on the HIP engine; dataset preprocessing is outside this build's scope and says so.
 
     python main.py --mode train_joint --config config/config.yaml
+    python main.py --mode train_classifier                         # fog-intensity classifier: train, then evaluate
     python main.py --mode train_joint --resume                     # continue from the latest checkpoint
     torchrun --nproc-per-node 8 main.py --mode train_joint        # data-parallel over RCCL
 
@@ -61,6 +61,14 @@ def main():
     if args.seed:
         config["seed"] = args.seed
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.mode == "train_classifier":
+        # refused before any process group or device is touched
+        if world > 1:
+            raise SystemExit("--mode train_classifier runs in a single process: data-parallel classifier training is not "
+                             "implemented.  Run it without torchrun (WORLD_SIZE=1).")
+        if args.resume is not None:
+            raise SystemExit("--resume is not supported for --mode train_classifier: the classifier stage always trains from "
+                             "scratch (drop --resume).")
     if world > 1:
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -97,16 +105,22 @@ def main():
             raise SystemExit(f"--resume {args.resume} is a '{resume_owner}' checkpoint, but --mode {args.mode} runs only the "
                              f"stage(s) {', '.join(stages)}: nothing would resume from it (and training from scratch would "
                              "overwrite best_model.pth).  Pick the matching --mode, or drop --resume.")
-    if args.mode == "train_joint":
+    if args.mode == "train_classifier":
+        # main.py:100-104 of the reference: train, then evaluate on the test split
+        print("Training fog intensity classifier...")
+        from training.train_classifier import evaluate_classifier, train_classifier
+        classifier = train_classifier(config, epochs=args.epochs)
+        evaluate_classifier(classifier, config)
+    elif args.mode == "train_joint":
         T.train_joint_model(config, epochs=args.epochs, resume=resume_for("joint"))
     elif args.mode == "train_dehazing":
         for level in ("low", "medium", "high"):   # train_dehazing.py:216-232
             T.train_dehazing_model(config, level, epochs=args.epochs or 30, resume=resume_for(level))
     elif args.mode == "train_all":
         # main.py:121-139 of the reference: classifier -> dehazing branches -> joint -> evaluation.  Step 1 (stand-alone
-        # classifier training) is outside this build's scope: the joint step fine-tunes the classifier
-        # from whatever checkpoint `classifier.checkpoint_dir` holds, exactly as train_joint.py:18-27 does when it is missing
-        print("\n===== Step 1: fog-intensity classifier training is outside this build's scope: skipped =====")
+        # classifier training) is not run by this mode (run --mode train_classifier first): the joint step fine-tunes the
+        # classifier from whatever checkpoint `classifier.checkpoint_dir` holds, as train_joint.py:18-27 does when it is missing
+        print("\n===== Step 1: fog-intensity classifier training is not run by train_all (--mode train_classifier): skipped =====")
         print("\n===== Step 2: Training Dehazing Models =====")
         for level in ("low", "medium", "high"):
             T.train_dehazing_model(config, level, epochs=args.epochs or 30, resume=resume_for(level))
