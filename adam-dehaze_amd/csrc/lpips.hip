@@ -84,6 +84,15 @@ __device__ __forceinline__ float sub8_sum(float v) {
     return v;
 }
 
+// na - nb = a * ia - b * ib with BOTH products rounded before the subtraction: contracted to fma(a, ia, -(b * ib)) the
+// difference would keep one product's rounding error when fa == fb, and LPIPS(x, x) and its gradient must be exactly 0.
+__device__ __forceinline__ f32x4 unit_diff(f32x4 a, float ia, f32x4 b, float ib) {
+#pragma clang fp contract(off)
+    const f32x4 na = a * ia;
+    const f32x4 nb = b * ib;
+    return na - nb;
+}
+
 __global__ __launch_bounds__(256) void lpips_layer_kernel(const float* __restrict__ fa, const float* __restrict__ fb,
                                                           const float* __restrict__ w, int HW, int C,
                                                           float* __restrict__ partial, int nblk) {
@@ -111,7 +120,7 @@ __global__ __launch_bounds__(256) void lpips_layer_kernel(const float* __restric
             const f32x4 a = *reinterpret_cast<const f32x4*>(an + (size_t)p * C + q * 4);
             const f32x4 b = *reinterpret_cast<const f32x4*>(bn + (size_t)p * C + q * 4);
             const f32x4 ww = *reinterpret_cast<const f32x4*>(w + q * 4);
-            const f32x4 df = a * ia - b * ib;
+            const f32x4 df = unit_diff(a, ia, b, ib);
             const f32x4 t = ww * df * df;
             d += (t[0] + t[1]) + (t[2] + t[3]);
         }
@@ -155,12 +164,15 @@ __global__ __launch_bounds__(256) void lpips_layer_bwd_kernel(const float* __res
         const float s = ra + LP_EPS;
         const float ia = 1.f / s, ib = 1.f / (sqrtf(sb) + LP_EPS);
         // delta_c = 2 w_c (na_c - nb_c) * gk ;  g_a_k = delta_k / s - a_k / (ra s^2) * sum_c delta_c a_c
+        // CONVENTION at an all-zero pixel of fa (ra = 0; common after ReLU): |a| is not differentiable there and torch autograd
+        // returns NaN (0 / 0 in sqrt's backward).  The second term is dropped (k2 = 0), i.e. s is held constant:
+        // g_a_k = delta_k / 1e-10, finite, and exactly 0 when fb is all zero there too.  fa == fb gives delta = 0: gradient 0.
         float dot = 0.f;
         for (int q = sub; q < CQ; q += 8) {
             const f32x4 a = *reinterpret_cast<const f32x4*>(an + (size_t)p * C + q * 4);
             const f32x4 b = *reinterpret_cast<const f32x4*>(bn + (size_t)p * C + q * 4);
             const f32x4 ww = *reinterpret_cast<const f32x4*>(w + q * 4);
-            const f32x4 dl = ww * (a * ia - b * ib) * (2.f * gk);
+            const f32x4 dl = ww * unit_diff(a, ia, b, ib) * (2.f * gk);
             const f32x4 t = dl * a;
             dot += (t[0] + t[1]) + (t[2] + t[3]);
         }
@@ -170,7 +182,7 @@ __global__ __launch_bounds__(256) void lpips_layer_bwd_kernel(const float* __res
             const f32x4 a = *reinterpret_cast<const f32x4*>(an + (size_t)p * C + q * 4);
             const f32x4 b = *reinterpret_cast<const f32x4*>(bn + (size_t)p * C + q * 4);
             const f32x4 ww = *reinterpret_cast<const f32x4*>(w + q * 4);
-            const f32x4 dl = ww * (a * ia - b * ib) * (2.f * gk);
+            const f32x4 dl = ww * unit_diff(a, ia, b, ib) * (2.f * gk);
             *reinterpret_cast<f32x4*>(gn + (size_t)p * C + q * 4) = dl * ia - a * k2;
         }
     }

@@ -296,12 +296,17 @@ __global__ __launch_bounds__(256) void aug_gray_partial_kernel(const float* __re
                                                                double* __restrict__ partial) {
     const int n = blockIdx.y;
     const float* p = params + n * 5;
-    const float b = p[2] != 0.f ? p[3] : 1.f;            // brightness comes first: the contrast step sees clamp(b * x)
+    const bool bfirst = p[2] != 0.f;                     // brightness comes first: the contrast step sees clamp(b * x);
+    const float b = p[3];                                // contrast first: it sees x itself, UNCLAMPED (x need not lie in [0, 1])
     const float* px = x + (int64_t)n * 3 * HW;
     double acc = 0.0;
     for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < HW; i += (int64_t)gridDim.x * 256) {
-        const float r = fminf(fmaxf(b * px[i], 0.f), 1.f), g = fminf(fmaxf(b * px[HW + i], 0.f), 1.f),
-                    bl = fminf(fmaxf(b * px[2 * HW + i], 0.f), 1.f);
+        float r = px[i], g = px[HW + i], bl = px[2 * HW + i];
+        if (bfirst) {
+            r = fminf(fmaxf(b * r, 0.f), 1.f);
+            g = fminf(fmaxf(b * g, 0.f), 1.f);
+            bl = fminf(fmaxf(b * bl, 0.f), 1.f);
+        }
         acc += (double)(0.2989f * r + 0.587f * g + 0.114f * bl);
     }
 #pragma unroll

@@ -282,7 +282,7 @@ class FasterRCNN(nn.Module):
                 for prev in mine:                       # (chunked: at most NMS_LIMIT x NMS_LIMIT IoUs at a time)
                     if cand.numel() == 0:
                         break
-                    cand = cand[(FasterRCNN._iou(boxes[cand], boxes[prev]) <= thr).all(dim=1)]
+                    cand = cand[~FasterRCNN._overlapped(boxes[cand], boxes[prev], thr)]
                 if cand.numel():
                     z = torch.zeros(cand.numel(), dtype=torch.int32, device=boxes.device)
                     mine.append(cand[FasterRCNN._nms_sorted(boxes[cand], z, thr)])
@@ -302,6 +302,16 @@ class FasterRCNN(nn.Module):
         wh = (rb - lt).clamp(min=0)
         inter = wh[..., 0] * wh[..., 1]
         return inter / (area_a[:, None] + area_b[None, :] - inter)
+
+    @staticmethod
+    def _overlapped(a: torch.Tensor, b: torch.Tensor, thr: float) -> torch.Tensor:
+        """[len(a)] bool: some box of `b` overlaps the box by IoU > thr.  The test is the kernel's and torchvision's `iou > thr`, so
+        the IoU of two zero-area boxes (0 / 0 = NaN) suppresses nothing; `iou <= thr` is not its complement.  Row blocks of 2048
+        keep the [rows, len(b), 2] temporaries of box_iou at 0.25 GB for a full 16384-box chunk."""
+        out = torch.empty(a.shape[0], dtype=torch.bool, device=a.device)
+        for lo in range(0, a.shape[0], 2048):
+            out[lo:lo + 2048] = (FasterRCNN._iou(a[lo:lo + 2048], b) > thr).any(dim=1)
+        return out
 
     @staticmethod
     def _nms_sorted(b: torch.Tensor, g: torch.Tensor, thr: float) -> torch.Tensor:

@@ -112,3 +112,61 @@ def oracle_with_masks(fn, masks, cbam=None):
         R._relu = old_relu
         R.KINK_MASKS = old
         R.CBAM_INDICES = old_cbam
+
+
+# ------------------------------------------------------------------------------------------------
+# helpers of the kernel-level GPU tests (test_gpu_train_io / test_gpu_detect_kernels / test_gpu_lpips)
+# ------------------------------------------------------------------------------------------------
+EPS = 2.0 ** -24            # fp32 unit roundoff
+DEV = "cuda:0"
+
+
+def _nan(*shape, dtype=torch.float32):
+    """an output buffer no kernel has written: every element NaN."""
+    return torch.full(shape, float("nan"), device=DEV, dtype=dtype)
+
+
+def _idx(*shape):
+    """an int32 output buffer no kernel has written: every element -7."""
+    return torch.full(shape, -7, device=DEV, dtype=torch.int32)
+
+
+def _same_bits(u, v):
+    if u.is_floating_point():
+        it = torch.int64 if u.dtype == torch.float64 else torch.int32
+        u, v = u.contiguous().view(it), v.contiguous().view(it)
+    return torch.equal(u, v)
+
+
+def _twice(fn):
+    """run fn twice; the two runs' outputs must be bit-equal.  Returns the first run's outputs."""
+    a = fn()
+    b = fn()
+    torch.cuda.synchronize()
+    for i, (u, v) in enumerate(zip(a, b)):
+        assert _same_bits(u, v), f"output {i} differs between two identical runs"
+    return a
+
+
+def _assert_bound(got, ref64, bound, what):
+    """|got - ref64| <= bound element-wise (bound: tensor or number); prints the worst ratio before it asserts."""
+    assert not torch.isnan(got).any(), f"{what}: NaN (an element was not written)"
+    ref64 = torch.as_tensor(ref64, dtype=torch.float64, device=got.device)
+    bound = torch.as_tensor(bound, dtype=torch.float64, device=got.device)
+    err = (got.double() - ref64).abs()
+    worst = float((err / bound.clamp_min(1e-300)).max()) if err.numel() else 0.0
+    print(f"[bound] {what}: worst |err| / bound = {worst:.3f}")
+    d = err - bound
+    assert float(d.max()) <= 0, f"{what}: exceeds its bound by {float(d.max()):.3e} (|err| / bound = {worst:.3f})"
+
+
+def _padded(n, pad=64, dtype=torch.float32, fill=float("nan")):
+    """(whole, owned): an allocation of n elements with `pad` guard elements on both sides, all set to `fill`."""
+    whole = torch.full((n + 2 * pad,), fill, device=DEV, dtype=dtype)
+    return whole, whole[pad:pad + n]
+
+
+def _pad_untouched(whole, n, pad=64):
+    """the guard elements of a _padded allocation still hold their fill (NaN, or -7 for ints)."""
+    g = torch.cat([whole[:pad], whole[pad + n:]])
+    return bool(torch.isnan(g).all()) if g.is_floating_point() else bool((g == -7).all())
