@@ -12,7 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -35,30 +35,19 @@ CONTRACT = os.environ.get("ADH_CONTRACT", "fp32")
 if CONTRACT not in ("fp32", "bf16x3"):
     raise ValueError(f"ADH_CONTRACT must be 'fp32' or 'bf16x3', got {CONTRACT!r}")
 W43_WGRAD_ROUNDS = int(os.environ.get("ADH_W43_WGRAD_ROUNDS", "4"))   # dev: rounds of workgroups the pixel splits may form
-USE_SMALL_WGRAD = os.environ.get("ADH_SMALL_WGRAD", "1") != "0"
+USE_SMALL_WGRAD = os.environ.get("ADH_SMALL_WGRAD", "1") != "0"     # conv_wgrad_small.hip for the few-channel 3x3 layers
 USE_FEWOUT = os.environ.get("ADH_FEWOUT", "1") != "0"               # conv_fewout.hip for the <= 4-output-channel 3x3 heads
 # BatchNorm-backward sums of a ConvBlock taken in the epilogue of its single consumer's data-gradient launch
 # (adh_conv_wino43_dgrad_bnred) instead of a bn_bwd_reduce pass over the same tensor (A/B switch)
 USE_BN_FUSED_REDUCE = os.environ.get("ADH_BN_FUSED_REDUCE", "1") != "0"
-# the output-parity class launches of one transposed layer on separate streams (their partial last rounds overlap): measured
-# -0.2 .. -0.4 ms per layer in isolation, +1.5 ms on the whole step -- opt-in
-CLASS_STREAMS = os.environ.get("ADH_CLASS_STREAMS", "0") != "0"
-# ... and as one grid (adh_conv_wino32_forward_multi): what the streams were after, without their events
+# the output-parity class launches of one transposed layer as one grid (adh_conv_wino32_forward_multi,
+# adh_conv_wgrad_wino32_multi): one partial last round of workgroups instead of four
 MERGE_CLASSES = os.environ.get("ADH_MERGE_CLASSES", "1") != "0"
-_SIDE_STREAMS: Dict[tuple, list] = {}
-
-
-def _side_streams(device: torch.device, n: int):
-    key = (device.type, device.index)
-    pool = _SIDE_STREAMS.setdefault(key, [])
-    while len(pool) < n:
-        pool.append(torch.cuda.Stream(device=device))
-    return pool[:n]
 # Bit-packed ReLU mask for the residual BN layers (1 bit per element written by bn_apply, read by the two backward passes
 # instead of `out`): correct and tested, but measured SLOWER on MI355X (bench, ms/step: bn_apply 8.19 -> 8.47,
 # bn_bwd_reduce 8.79 -> 9.85, bn_bwd_apply 12.78 -> 12.52; +1.1 ms in all): the byte loads double the number of
 # vector-memory instructions of passes that were already running at 5+ TB/s.  Opt-in (ADH_RELU_BITS=1).
-USE_RELU_BITS = os.environ.get("ADH_RELU_BITS", "0") != "0"      # conv_wgrad_small.hip for the few-channel 3x3 layers
+USE_RELU_BITS = os.environ.get("ADH_RELU_BITS", "0") != "0"
 _WINO_ONLY = os.environ.get("ADH_WINOGRAD_ONLY", "")   # dev: "fwd" or "dgrad" restricts the Winograd path to one direction
 
 
@@ -188,6 +177,99 @@ def _rows_nsplit(groups: int, ntiles: int, cus: int = 256, max_rounds: int = 4, 
         if best_cost is None or cost < best_cost * (1.0 - 5e-3):
             best, best_cost = ns, cost
     return best
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Kernel families of the convolution section.  Engine._select names one of _CONV per launch of a forward / data-gradient
+# plan; Engine._wgrad tries _WGRAD_WINO43, _WGRAD_WINO, _WGRAD_WINO32 in turn.  Built once, here: a launch only reads them.
+# ---------------------------------------------------------------------------------------------------------------------
+class _ConvFamily(NamedTuple):
+    pack: str                                     # pack entry point
+    floats: Callable[[WLayout, int, int], int]    # packed size in floats of (layout, padded K, padded Nc)
+    blocks: Optional[str]                         # query: workgroups = statistics rows of a launch; None: writes no statistics
+    launch: str                                   # launch entry point
+    bf16x3: bool                                  # pack and launch have a `_bf16x3` twin (CONTRACT)
+    timer: Optional[str]                          # family a timer accounts the launch under, None: its own name
+    exec_factor: Optional[float]                  # executed / algorithmic FLOPs, None: 1
+
+
+_CONV = {
+    # at most four output channels (the reconstruction heads): one pixel per thread instead of a 32-wide MFMA tile
+    "fewout": _ConvFamily("adh_pack_weights_fewout", lambda L, Kp, NcP: 9 * Kp * 4, None,
+                          "adh_conv_fewout_forward", False, "adh_conv_forward", None),
+    # at most four input channels (data gradient of the reconstruction head, 3 -> 48): a per-pixel kernel as well
+    "fewin": _ConvFamily("adh_pack_weights_fewin", lambda L, Kp, NcP: 9 * 4 * 64, "adh_conv_fewin_num_blocks",
+                         "adh_conv_fewin_forward", False, "adh_conv_forward", None),
+    "wino43": _ConvFamily("adh_pack_weights_wino43", lambda L, Kp, NcP: 36 * Kp * NcP, "adh_conv_wino43_num_blocks",
+                          "adh_conv_wino43_forward", True, "adh_conv_wino43_forward", 0.25),
+    "wino": _ConvFamily("adh_pack_weights_wino", lambda L, Kp, NcP: 16 * Kp * NcP, "adh_conv_wino_num_blocks",
+                        "adh_conv_wino_forward", False, None, 4.0 / 9.0),
+    # F(3x3,2x2): 2x2-tap forms (one parity class of a transposed conv / of a k4 s2 data gradient) and the k4 s2 forms as
+    # four input-parity classes
+    "wino32": _ConvFamily("adh_pack_weights_wino32", lambda L, Kp, NcP: (4 if L.KHt == 4 else 1) * 16 * Kp * NcP,
+                          "adh_conv_wino32_num_blocks", "adh_conv_wino32_forward", True, "adh_conv_wino32_forward", 4.0 / 9.0),
+    # 7x7 stem on the NHWC8 image: (kx, c)-packed 16x16x4 tiles (conv_stem.hip)
+    "stem": _ConvFamily("adh_pack_weights_stem", lambda L, Kp, NcP: 7 * 24 * NcP, "adh_conv_stem_num_blocks",
+                        "adh_conv_stem_forward", False, None, None),
+    "igemm": _ConvFamily("adh_pack_weights", lambda L, Kp, NcP: L.KHt * L.KWt * Kp * NcP, "adh_conv_num_blocks",
+                         "adh_conv_forward", False, None, None),
+}
+
+
+def _twin(fam: _ConvFamily) -> str:
+    """Entry-point suffix of the opt-in contraction, for the families that have the twin."""
+    return "_bf16x3" if fam.bf16x3 and CONTRACT == "bf16x3" else ""
+
+
+class _WgradFamily(NamedTuple):
+    """A weight gradient accumulated in a Winograd domain: `planes` frequency planes of KP x NcP floats per pixel split (and
+    class), transformed back by the reduce kernel."""
+    groups: str                   # query: workgroup groups of the launch, 0: not this family's shape
+    tiles: Optional[str]          # query: tiles the pixel splits divide, None: the 4 x 32-pixel row-tile estimate
+    classes: Optional[str]        # query: classes of one descriptor (a k4 s2 form has four input-parity classes), None: 1
+    launches: Optional[str]       # query: launches they take (conv_wgrad32v2_kernel runs them in ONE grid: classes x groups
+                                  # workgroup groups), None: 1
+    planes: int
+    tile_us: float                # _rows_nsplit's cost of one tile
+    launch: str
+    reduce: str
+    exec_factor: float            # executed / algorithmic FLOPs
+
+
+# 3x3 stride-1, Cin % 32 == 0, Cout % 96 == 0: the F(4x4,3x3) domain (36 frequency slabs)
+_WGRAD_WINO43 = _WgradFamily("adh_conv_wgrad_wino43_groups", "adh_conv_wgrad_wino43_strips", None, None, 36, 3.6,
+                             "adh_conv_wgrad_wino43", "adh_wgrad_reduce_wino43", 0.25)
+# 3x3 stride-1: the F(2x2,3x3) domain (16 frequency slabs), G^T(.)G in the reduce
+_WGRAD_WINO = _WgradFamily("adh_conv_wgrad_wino_groups", None, None, None, 16, 8.6,
+                           "adh_conv_wgrad_wino", "adh_wgrad_reduce_wino", 4.0 / 9.0)
+# the 2x2-tap forms (k4 s2 / transposed layers): the F(3x3,2x2) domain, 16 frequency slabs per class, A^T(.)A in the reduce
+_WGRAD_WINO32 = _WgradFamily("adh_conv_wgrad_wino32_groups", "adh_conv_wgrad_wino32_tiles", "adh_conv_wgrad_wino32_classes",
+                             "adh_conv_wgrad_wino32_launches", 16, 5.0, "adh_conv_wgrad_wino32", "adh_wgrad_reduce_wino32",
+                             4.0 / 9.0)
+
+
+def _forward_taps(L: WLayout, gm: dict) -> Tuple[WLayout, int, int]:
+    """The 3x3 and 2x2 kernels walk their taps forwards.  A plan that walks them backwards (a data gradient, a class of a
+    transposed form) is the same correlation with the filter flipped in both axes: returns the layout to pack and the
+    descriptor's (dy0, dx0) for dstep = 1."""
+    if gm["dstep"] == 1:
+        return L, gm["dy0"], gm["dx0"]
+    last = gm["KH"] - 1
+    Lw = WLayout(L.K, L.Nc, gm["KH"], gm["KW"], L.tap_off0 + last * (L.tap_off_sy + L.tap_off_sx), -L.tap_off_sy,
+                 -L.tap_off_sx, L.stride_k, L.stride_n)
+    return Lw, gm["dy0"] - last, gm["dx0"] - last
+
+
+def _set_taps(d: ConvDesc, dy0: int, dx0: int, dstep: int) -> None:
+    d.dy0, d.dx0 = dy0, dx0
+    d.dstep_y = d.dstep_x = dstep
+
+
+def _virtual_grid(gm: dict, t: torch.Tensor) -> Tuple[int, int]:
+    """(VH, VW) of one plan entry over the output (or output-gradient) tensor `t`."""
+    if gm["vgrid"] == "in":   # one output-parity class of a stride-2 transposed form
+        return (t.shape[1] - gm["out_o"][0] + 1) // 2, (t.shape[2] - gm["out_o"][1] + 1) // 2
+    return t.shape[1], t.shape[2]
 
 
 class Engine:
@@ -346,10 +428,18 @@ class Engine:
                 pass
         return wp
 
+    def _pack_family(self, fam: _ConvFamily, w: torch.Tensor, L: WLayout) -> torch.Tensor:
+        """Weights (w, L) packed for `fam`'s launch entry point."""
+        Kp, NcP = _round_up(L.K, 8), _round_up(L.Nc, 32)
+        nfloats = fam.floats(L, Kp, NcP)
+        twin = _twin(fam)
+        if twin:   # three bf16 planes of every fp32 value: 6 bytes instead of 4
+            nfloats = nfloats * 3 // 2
+        return self._packed(fam.pack + twin, w, L, nfloats)
+
     def _pack(self, w: torch.Tensor, L: WLayout) -> torch.Tensor:
-        KQ = _round_up(L.K, 8) // 4
-        NcP = _round_up(L.Nc, 32)
-        return self._packed("adh_pack_weights", w, L, L.KHt * L.KWt * KQ * NcP * 4)
+        """Weights packed for the general kernel (adh_conv_forward)."""
+        return self._pack_family(_CONV["igemm"], w, L)
 
     @staticmethod
     def _launch_plan(kind: str, k: int, stride: int, pad: int, w: torch.Tensor, direction: str):
@@ -398,6 +488,53 @@ class Engine:
                                       vgrid="out")))
         return plans
 
+    def _select(self, L: WLayout, gm: dict, d: ConvDesc, residual, want_stats: bool, bnred) -> Tuple[_ConvFamily, WLayout]:
+        """The kernel family of one plan entry and the layout to pack for it.  `d` is the entry's descriptor before the
+        epilogue pointers are attached; this is the only code that writes its tap fields: a family that walks its taps
+        forwards gets _forward_taps' offsets, and the plan's own come back when the family turns the shape down."""
+        Kp = d.Cin
+        direction = "dgrad" if gm["dstep"] == -1 else "fwd"
+        k3 = gm["KH"] == 3 and gm["KW"] == 3
+        # 3x3 stride 1 pad 1, forwards or backwards
+        k3s1 = k3 and gm["in_s"] == 1 and gm["out_s"] == 1 and (gm["dy0"], gm["dx0"], gm["dstep"]) in ((-1, -1, 1), (1, 1, -1))
+        if USE_FEWOUT and k3 and L.Nc <= 4 and residual is None and not want_stats and bnred is None and gm["dstep"] == 1 and \
+                H.value("adh_conv_fewout_supported", C.byref(d)):
+            return _CONV["fewout"], L
+        if USE_FEWOUT and k3s1 and L.K <= 4 and Kp == 8 and 4 <= L.Nc <= 64 and L.Nc % 4 == 0 and residual is None and \
+                (not want_stats or L.Nc <= 16):
+            Lw, dy0, dx0 = _forward_taps(L, gm)
+            _set_taps(d, dy0, dx0, 1)
+            if H.value("adh_conv_fewin_supported", C.byref(d)):
+                return _CONV["fewin"], Lw
+            _set_taps(d, gm["dy0"], gm["dx0"], gm["dstep"])
+        if USE_WINOGRAD and k3s1 and Kp % 16 == 0 and (not _WINO_ONLY or _WINO_ONLY == direction):
+            Lw, dy0, dx0 = _forward_taps(L, gm)
+            _set_taps(d, dy0, dx0, 1)
+            w43 = USE_WINO43 if (self.wino43 is None or USE_WINO43 is not True) else self.wino43
+            if (w43 is True or w43 == direction) and H.value("adh_conv_wino43_supported", C.byref(d)):
+                return _CONV["wino43"], Lw
+            if H.value("adh_conv_wino_supported", C.byref(d)):
+                return _CONV["wino"], Lw
+            _set_taps(d, gm["dy0"], gm["dx0"], gm["dstep"])
+        if USE_WINOGRAD and Kp % 16 == 0 and \
+                ((gm["KH"] == 2 and gm["KW"] == 2 and gm["in_s"] == 1 and gm["dstep"] in (1, -1)) or
+                 (gm["KH"] == 4 and gm["KW"] == 4 and gm["in_s"] == 2 and gm["dstep"] == 1)):
+            Lw, dy0, dx0 = _forward_taps(L, gm)
+            _set_taps(d, dy0, dx0, 1)
+            if H.value("adh_conv_wino32_supported", C.byref(d)):
+                return _CONV["wino32"], Lw
+            _set_taps(d, gm["dy0"], gm["dx0"], gm["dstep"])
+        if gm["KH"] == 7 and L.K <= 3 and residual is None and USE_SMALL_WGRAD and \
+                H.value("adh_conv_stem_num_blocks", C.byref(d)):
+            return _CONV["stem"], L
+        return _CONV["igemm"], L
+
+    @staticmethod
+    def _launch(fam, name: str, args: tuple, work: float):
+        """`work`: algorithmic FLOPs of the launch, 2 * virtual pixels * taps * real K * real Nc (Winograd executes less)."""
+        H.call(name + _twin(fam), *args, work=work, work_exec=None if fam.exec_factor is None else work * fam.exec_factor,
+               family=fam.timer)
+
     def _run_gather(self, plans, src: Act, dst_t: torch.Tensor, dstC: int, w: torch.Tensor, scale=None, shift=None,
                     residual: Optional[torch.Tensor] = None, act=H.ACT_NONE, want_stats=False, bnred=None):
         """Launch every plan of one layer; returns (stats partials or None, number of stat rows).
@@ -405,95 +542,17 @@ class Engine:
         the gradient of: when the layer runs as ONE F(4x4,3x3) launch the producer's BatchNorm-backward sums are taken in
         its epilogue (adh_conv_wino43_dgrad_bnred) and returned as the stats rows; otherwise (None, 0) comes back and
         nothing was fused."""
-        descs = []
+        descs = []          # (descriptor, its statistics rows, family, packed weights: alive until the launch is enqueued)
         total_blocks = 0
         for L, gm in plans:
             NcP = _round_up(L.Nc, 32)
             Kp = _round_up(L.K, 8)
             assert src.t.shape[3] >= Kp or src.cs >= Kp, "input activation narrower than the padded contraction"
-            if gm["vgrid"] == "in":   # one output-parity class of a stride-2 transposed form
-                VH = (dst_t.shape[1] - gm["out_o"][0] + 1) // 2
-                VW = (dst_t.shape[2] - gm["out_o"][1] + 1) // 2
-            else:
-                VH, VW = dst_t.shape[1], dst_t.shape[2]
+            VH, VW = _virtual_grid(gm, dst_t)
             d = self._conv_desc(src, Kp, dst_t, dstC, NcP, VH, VW, gm["KH"], gm["KW"], gm["in_s"], gm["out_s"],
                                 gm["out_o"], gm["dy0"], gm["dx0"], gm["dstep"])
-            wino = False
-            if L.Nc <= 4 and gm["KH"] == 3 and gm["KW"] == 3 and residual is None and not want_stats and bnred is None and \
-                    USE_FEWOUT and gm["dstep"] == 1 and H.value("adh_conv_fewout_supported", C.byref(d)):
-                # at most four output channels (the reconstruction heads): one pixel per thread instead of a 32-wide MFMA tile
-                wino = "fewout"
-                wp = self._packed("adh_pack_weights_fewout", w, L, 9 * Kp * 4)
-            if not wino and L.K <= 4 and Kp == 8 and 4 <= L.Nc <= 64 and L.Nc % 4 == 0 and gm["KH"] == 3 and gm["KW"] == 3 and \
-                    gm["in_s"] == 1 and gm["out_s"] == 1 and residual is None and (not want_stats or L.Nc <= 16) and USE_FEWOUT and \
-                    (gm["dy0"], gm["dx0"], gm["dstep"]) in ((-1, -1, 1), (1, 1, -1)):
-                # at most four input channels (data gradient of the reconstruction head, 3 -> 48): a per-pixel kernel as well
-                Lw = L
-                dsave = (d.dy0, d.dx0, d.dstep_y, d.dstep_x)
-                if gm["dstep"] == -1:   # data gradient: the same correlation with the filter flipped in both axes
-                    Lw = WLayout(L.K, L.Nc, 3, 3, L.tap_off0 + 2 * L.tap_off_sy + 2 * L.tap_off_sx, -L.tap_off_sy,
-                                 -L.tap_off_sx, L.stride_k, L.stride_n)
-                    d.dy0 = d.dx0 = -1
-                    d.dstep_y = d.dstep_x = 1
-                if H.value("adh_conv_fewin_supported", C.byref(d)):
-                    wino = "fewin"
-                    wp = self._packed("adh_pack_weights_fewin", w, Lw, 9 * 4 * 64)
-                else:
-                    d.dy0, d.dx0, d.dstep_y, d.dstep_x = dsave
-            if not wino and USE_WINOGRAD and (not _WINO_ONLY or _WINO_ONLY == ("dgrad" if gm["dstep"] == -1 else "fwd")) \
-                    and gm["KH"] == 3 and gm["KW"] == 3 and gm["in_s"] == 1 and gm["out_s"] == 1 and Kp % 16 == 0 \
-                    and (gm["dy0"], gm["dx0"], gm["dstep"]) in ((-1, -1, 1), (1, 1, -1)):
-                Lw = L
-                if gm["dstep"] == -1:   # data gradient: the same correlation with the filter flipped in both axes
-                    Lw = WLayout(L.K, L.Nc, 3, 3, L.tap_off0 + 2 * L.tap_off_sy + 2 * L.tap_off_sx, -L.tap_off_sy,
-                                 -L.tap_off_sx, L.stride_k, L.stride_n)
-                    d.dy0 = d.dx0 = -1
-                    d.dstep_y = d.dstep_x = 1
-                w43 = USE_WINO43 if (self.wino43 is None or USE_WINO43 is not True) else self.wino43
-                if (w43 is True or w43 == ("dgrad" if gm["dstep"] == -1 else "fwd")) and \
-                        H.value("adh_conv_wino43_supported", C.byref(d)):
-                    wino = 43
-                    if CONTRACT == "bf16x3":   # three bf16 planes of U: 6 bytes per weight and frequency
-                        wp = self._packed("adh_pack_weights_wino43_bf16x3", w, Lw, 36 * Kp * NcP * 3 // 2)
-                    else:
-                        wp = self._packed("adh_pack_weights_wino43", w, Lw, 36 * (Kp // 4) * NcP * 4)
-                else:
-                    wino = bool(H.value("adh_conv_wino_supported", C.byref(d)))
-                if wino == 43:
-                    pass
-                elif wino:
-                    KQ = Kp // 4
-                    wp = self._packed("adh_pack_weights_wino", w, Lw, 16 * KQ * NcP * 4)
-                else:
-                    d.dy0 = d.dx0 = gm["dy0"]
-                    d.dstep_y = d.dstep_x = gm["dstep"]
-            if not wino and USE_WINOGRAD and Kp % 16 == 0 and \
-                    ((gm["KH"] == 2 and gm["KW"] == 2 and gm["in_s"] == 1 and gm["dstep"] in (1, -1)) or
-                     (gm["KH"] == 4 and gm["KW"] == 4 and gm["in_s"] == 2 and gm["dstep"] == 1)):
-                # F(3x3,2x2): 2x2-tap forms (one parity class of a transposed conv / of a k4 s2 data gradient) and the
-                # k4 s2 forms as four input-parity classes.  Backward-walking taps = forward-walking with the filter flipped.
-                Lw = L
-                if gm["dstep"] == -1:
-                    Lw = WLayout(L.K, L.Nc, 2, 2, L.tap_off0 + L.tap_off_sy + L.tap_off_sx, -L.tap_off_sy, -L.tap_off_sx,
-                                 L.stride_k, L.stride_n)
-                    d.dy0, d.dx0 = gm["dy0"] - 1, gm["dx0"] - 1
-                    d.dstep_y = d.dstep_x = 1
-                if H.value("adh_conv_wino32_supported", C.byref(d)):
-                    wino = 32
-                    ncls = 4 if gm["KH"] == 4 else 1
-                    if CONTRACT == "bf16x3":
-                        wp = self._packed("adh_pack_weights_wino32_bf16x3", w, Lw, ncls * 16 * Kp * NcP * 3 // 2)
-                    else:
-                        wp = self._packed("adh_pack_weights_wino32", w, Lw, ncls * 16 * (Kp // 4) * NcP * 4)
-                else:
-                    d.dy0 = d.dx0 = gm["dy0"]
-                    d.dstep_y = d.dstep_x = gm["dstep"]
-            if not wino and gm["KH"] == 7 and L.K <= 3 and residual is None and USE_SMALL_WGRAD and \
-                    H.value("adh_conv_stem_num_blocks", C.byref(d)):
-                wino = "stem"   # 7x7 stem on the NHWC8 image: (kx, c)-packed 16x16x4 tiles (conv_stem.hip)
-                wp = self._packed("adh_pack_weights_stem", w, L, 7 * 24 * NcP)
-            if not wino:
-                wp = self._pack(w, L)   # keep alive until the launch below is enqueued
+            fam, Lw = self._select(L, gm, d, residual, want_stats, bnred)
+            wp = self._pack_family(fam, w, Lw)
             d.wp = wp.data_ptr()
             d.scale = H.ptr(scale)
             d.shift = H.ptr(shift)
@@ -501,16 +560,13 @@ class Engine:
                 d.residual = residual.data_ptr()
                 d.res_cstride = residual.stride(2)
             d.act = act
-            if wino == "fewout":
-                nb = 0
-            else:
-                nb = H.value({32: "adh_conv_wino32_num_blocks", 43: "adh_conv_wino43_num_blocks", True: "adh_conv_wino_num_blocks",
-                              "stem": "adh_conv_stem_num_blocks", "fewin": "adh_conv_fewin_num_blocks",
-                              False: "adh_conv_num_blocks"}[wino], C.byref(d))
-            descs.append((d, nb, wp, wino))
+            nb = H.value(fam.blocks, C.byref(d)) if fam.blocks else 0
+            descs.append((d, nb, fam, wp))
             total_blocks += nb
+        launch, extra = None, ()
         if bnred is not None:
-            if len(descs) != 1 or descs[0][3] != 43 or residual is not None or scale is not None or shift is not None:
+            if len(descs) != 1 or descs[0][2] is not _CONV["wino43"] or residual is not None or scale is not None or \
+                    shift is not None:
                 bnred = None
             else:
                 y_p, ss_p, mean_p = bnred
@@ -518,81 +574,54 @@ class Engine:
                 d0.residual, d0.res_cstride = y_p.data_ptr(), y_p.stride(2)
                 d0.scale, d0.shift = ss_p[0].data_ptr(), ss_p[1].data_ptr()
                 want_stats = True
-        _B3 = "_bf16x3" if CONTRACT == "bf16x3" else ""      # entry-point suffix of the opt-in contraction
+                launch, extra = "adh_conv_wino43_dgrad_bnred", (mean_p.data_ptr(),)
         stats = None
         if want_stats:
-            NcP = descs[0][0].NcP
-            stats = self._f(total_blocks, 2, NcP)
-        row = 0
-        row_i = 0
-        flops_kn = [L.K * L.Nc for L, _ in plans]
-        # The output-parity classes of a transposed form are independent launches whose grids are not multiples of the CU count
-        # (e.g. 1056 workgroups = 4.125 rounds of one workgroup per CU: the last round runs on 1/8 of the chip).  On separate
-        # streams the next class fills the CUs the previous one's tail leaves idle.
-        if MERGE_CLASSES and 2 <= len(descs) <= 4 and all(w == 32 and dd.KH == 2 for dd, _, _, w in descs):
-            # the output-parity classes of a transposed form as ONE grid: one partial last round of workgroups instead of four
-            for dd, nb, _wp, _w in descs:
-                if stats is not None:
-                    dd.stats = stats.data_ptr() + row * 2 * dd.NcP * 4
+            stats = self._f(total_blocks, 2, descs[0][0].NcP)
+            row = 0
+            for d, nb, _, _ in descs:
+                d.stats = stats.data_ptr() + row * 2 * d.NcP * 4
                 row += nb
-            arr = (H.ConvDesc * len(descs))(*[dd for dd, _, _, _ in descs])
-            work = sum(2.0 * dd.N * dd.VH * dd.VW * dd.KH * dd.KW * kn for (dd, _, _, _), kn in zip(descs, flops_kn))
+        works = [2.0 * d.N * d.VH * d.VW * d.KH * d.KW * L.K * L.Nc for (d, _, _, _), (L, _) in zip(descs, plans)]
+        # The output-parity classes of a transposed form are independent launches whose grids are not multiples of the CU count
+        # (e.g. 1056 workgroups = 4.125 rounds of one workgroup per CU: the last round runs on 1/8 of the chip): as ONE grid
+        # they have one partial last round of workgroups instead of four
+        if MERGE_CLASSES and 2 <= len(descs) <= 4 and all(fam is _CONV["wino32"] and d.KH == 2 for d, _, fam, _ in descs):
+            arr = (H.ConvDesc * len(descs))(*[d for d, _, _, _ in descs])
             try:
-                H.call("adh_conv_wino32_forward_multi" + _B3, arr, len(descs), work=work, work_exec=work * 4.0 / 9.0,
-                       family="adh_conv_wino32_forward")
+                self._launch(_CONV["wino32"], "adh_conv_wino32_forward_multi", (arr, len(descs)), sum(works))
                 return stats, total_blocks
             except RuntimeError as e:
                 if "unsupported" not in str(e).lower():
-                    raise
-                row = 0           # descriptors that differ in more than the class fields: one launch each, below
-        fork = None
-        if CLASS_STREAMS and len(descs) > 1 and all(w == 32 for _, _, _, w in descs):
-            main = torch.cuda.current_stream()
-            fork = torch.cuda.Event()
-            fork.record(main)
-            side = _side_streams(self.device, min(4, len(descs)))
-        for d, nb, _wp, wino in descs:
-            if stats is not None:
-                d.stats = stats.data_ptr() + row * 2 * d.NcP * 4
-            if fork is not None:
-                st = side[row_i % len(side)]
-                st.wait_event(fork)
-                with torch.cuda.stream(st):
-                    work = 2.0 * d.N * d.VH * d.VW * d.KH * d.KW * flops_kn[row_i]
-                    H.call("adh_conv_wino32_forward" + _B3, C.byref(d), work=work, work_exec=work * 4.0 / 9.0,
-                           family="adh_conv_wino32_forward")
-                row += nb
-                row_i += 1
-                continue
-            # algorithmic FLOPs of this launch: 2 * virtual pixels * taps * real K * real Nc (Winograd executes 4/9)
-            work = 2.0 * d.N * d.VH * d.VW * d.KH * d.KW * flops_kn[row_i]
-            if wino == "fewout":
-                H.call("adh_conv_fewout_forward", C.byref(d), work=work, family="adh_conv_forward")
-            elif wino == "fewin":
-                H.call("adh_conv_fewin_forward", C.byref(d), work=work, family="adh_conv_forward")
-            elif wino == "stem":
-                H.call("adh_conv_stem_forward", C.byref(d), work=work)
-            elif wino == 43 and bnred is not None:
-                H.call("adh_conv_wino43_dgrad_bnred" + ("_bf16x3" if CONTRACT == "bf16x3" else ""), C.byref(d), bnred[2].data_ptr(),
-                       work=work, work_exec=work * 0.25, family="adh_conv_wino43_forward")
-            elif wino == 43:
-                H.call("adh_conv_wino43_forward" + ("_bf16x3" if CONTRACT == "bf16x3" else ""), C.byref(d), work=work,
-                       work_exec=work * 0.25, family="adh_conv_wino43_forward")
-            elif wino == 32:
-                H.call("adh_conv_wino32_forward" + _B3, C.byref(d), work=work, work_exec=work * 4.0 / 9.0,
-                       family="adh_conv_wino32_forward")
-            elif wino:
-                H.call("adh_conv_wino_forward", C.byref(d), work=work, work_exec=work * 4.0 / 9.0)
-            else:
-                H.call("adh_conv_forward", C.byref(d), work=work)
-            row += nb
-            row_i += 1
-        if fork is not None:
-            for st in side:
-                join = torch.cuda.Event()
-                join.record(st)
-                main.wait_event(join)
+                    raise           # descriptors that differ in more than the class fields: one launch each, below
+        for (d, _, fam, _), work in zip(descs, works):
+            self._launch(fam, launch or fam.launch, (C.byref(d),) + extra, work)
         return stats, total_blocks
+
+    def _split_slab(self, groups: int, ntiles: int, floats: int, **cost) -> Tuple[int, torch.Tensor]:
+        """(nsplit, slab) of a split-accumulating weight-gradient launch: every pixel split writes `floats` partial sums."""
+        nsplit = _rows_nsplit(groups, ntiles, slab_bytes=floats * 4, max_splits=max(1, _SLAB_BUDGET // (floats * 4)), **cost)
+        # _rows_nsplit searches within the budget already: this binds only when ADH_NSPLIT forces the count past it
+        while nsplit * floats * 4 > _SLAB_BUDGET and nsplit > 1:
+            nsplit //= 2
+        return nsplit, self._f(nsplit * floats)
+
+    def _wgrad_winograd(self, fam: _WgradFamily, max_rounds: int, d: ConvDesc, L: WLayout, KP: int, dw: torch.Tensor) -> bool:
+        """One plan entry's weight gradient accumulated in `fam`'s domain: pixel splits into a slab, then the reduce kernel
+        sums the splits and transforms back into `dw`.  False: not the family's shape, nothing was launched."""
+        groups = H.value(fam.groups, C.byref(d))
+        if not groups:
+            return False
+        ncls = H.value(fam.classes, C.byref(d)) if fam.classes else 1
+        launches = max(1, H.value(fam.launches, C.byref(d))) if fam.launches else 1
+        ntiles = H.value(fam.tiles, C.byref(d)) if fam.tiles else d.N * ((d.VH + 3) // 4) * ((d.VW + 31) // 32)
+        nsplit, slab = self._split_slab(groups * ncls // launches, ntiles, ncls * fam.planes * KP * d.NcP, tile_us=fam.tile_us,
+                                        max_rounds=max_rounds, launches=launches)
+        work = 2.0 * d.N * d.VH * d.VW * d.KH * d.KW * L.K * L.Nc
+        H.call(fam.launch, C.byref(d), slab.data_ptr(), nsplit, work=work, work_exec=work * fam.exec_factor)
+        of_desc = (C.byref(d),) if fam.classes else ()      # the reduce kernel of the class form reads the classes off `d`
+        H.call(fam.reduce, slab.data_ptr(), nsplit, *of_desc, KP, d.NcP, C.byref(L), dw.data_ptr(), 0)
+        return True
 
     def _wgrad(self, plans, x: Act, g_y: torch.Tensor, gC: int, w: torch.Tensor) -> torch.Tensor:
         """Weight gradient in the parameter's own layout (OIHW / IOHW)."""
@@ -619,19 +648,9 @@ class Engine:
         for L, gm in plans:
             NcP = _round_up(L.Nc, 32)
             KP = _round_up(L.K, 32)
-            Cin4 = _round_up(L.K, 4)
-            if gm["vgrid"] == "in":
-                VH = (g_y.shape[1] - gm["out_o"][0] + 1) // 2
-                VW = (g_y.shape[2] - gm["out_o"][1] + 1) // 2
-            else:
-                VH, VW = g_y.shape[1], g_y.shape[2]
-            d = self._conv_desc(x, Cin4, g_y, _round_up(gC, 4), NcP, VH, VW, gm["KH"], gm["KW"], gm["in_s"],
+            VH, VW = _virtual_grid(gm, g_y)
+            d = self._conv_desc(x, _round_up(L.K, 4), g_y, _round_up(gC, 4), NcP, VH, VW, gm["KH"], gm["KW"], gm["in_s"],
                                 gm["out_s"], gm["out_o"], gm["dy0"], gm["dx0"], gm["dstep"])
-            ntiles_est = x.N * ((VH + 3) // 4) * ((VW + 31) // 32)
-            T_all = gm["KH"] * gm["KW"]
-            zgroups = 7 if T_all == 49 else 1
-            groups = (KP // 32) * max(1, NcP // 96) * zgroups
-            # one 512-thread workgroup per CU is resident: aim at ~4 rounds of 256 workgroups
             T = gm["KH"] * gm["KW"]
             small = H.value("adh_conv_wgrad_small_slabs", C.byref(d)) if USE_SMALL_WGRAD else 0
             if small:
@@ -641,56 +660,22 @@ class Engine:
                        work=2.0 * d.N * d.VH * d.VW * T * L.K * L.Nc)
                 H.call("adh_wgrad_reduce_small", slab.data_ptr(), small, KP, NcP, C.byref(L), dw.data_ptr(), 0)
                 continue
-            w43_groups = H.value("adh_conv_wgrad_wino43_groups", C.byref(d)) if (USE_WINOGRAD and USE_WINO43_WGRAD) else 0
-            if w43_groups:
-                # 3x3 stride-1, Cin % 32 == 0, Cout % 96 == 0: accumulate in the F(4x4,3x3) domain (36 frequency slabs)
-                nstrips = H.value("adh_conv_wgrad_wino43_strips", C.byref(d))
-                nsplit = _rows_nsplit(w43_groups, nstrips, max_rounds=W43_WGRAD_ROUNDS, slab_bytes=36 * KP * NcP * 4,
-                                      max_splits=max(1, _SLAB_BUDGET // (36 * KP * NcP * 4)), tile_us=3.6)
-                while nsplit * 36 * KP * NcP * 4 > (1 << 30) and nsplit > 1:
-                    nsplit //= 2
-                slab = self._f(nsplit * 36 * KP * NcP)
-                H.call("adh_conv_wgrad_wino43", C.byref(d), slab.data_ptr(), nsplit,
-                       work=2.0 * d.N * d.VH * d.VW * T * L.K * L.Nc, work_exec=2.0 * d.N * d.VH * d.VW * 2.25 * L.K * L.Nc)
-                H.call("adh_wgrad_reduce_wino43", slab.data_ptr(), nsplit, KP, NcP, C.byref(L), dw.data_ptr(), 0)
+            if USE_WINOGRAD and ((USE_WINO43_WGRAD and self._wgrad_winograd(_WGRAD_WINO43, W43_WGRAD_ROUNDS, d, L, KP, dw))
+                                 or self._wgrad_winograd(_WGRAD_WINO, 4, d, L, KP, dw)
+                                 or self._wgrad_winograd(_WGRAD_WINO32, 4, d, L, KP, dw)):
                 continue
-            wino_groups = H.value("adh_conv_wgrad_wino_groups", C.byref(d)) if USE_WINOGRAD else 0
-            if wino_groups:
-                # 3x3 stride-1: accumulate in the Winograd domain (16 frequency slabs), G^T(.)G in the reduce
-                nsplit = _rows_nsplit(wino_groups, ntiles_est, slab_bytes=16 * KP * NcP * 4,
-                                      max_splits=max(1, _SLAB_BUDGET // (16 * KP * NcP * 4)), tile_us=8.6)
-                while nsplit * 16 * KP * NcP * 4 > (1 << 30) and nsplit > 1:
-                    nsplit //= 2
-                slab = self._f(nsplit * 16 * KP * NcP)
-                H.call("adh_conv_wgrad_wino", C.byref(d), slab.data_ptr(), nsplit,
-                       work=2.0 * d.N * d.VH * d.VW * T * L.K * L.Nc, work_exec=2.0 * d.N * d.VH * d.VW * 4 * L.K * L.Nc)
-                H.call("adh_wgrad_reduce_wino", slab.data_ptr(), nsplit, KP, NcP, C.byref(L), dw.data_ptr(), 0)
-                continue
-            w32_groups = H.value("adh_conv_wgrad_wino32_groups", C.byref(d)) if USE_WINOGRAD else 0
-            if w32_groups:
-                # the 2x2-tap forms (k4 s2 / transposed layers): accumulate in the F(3x3,2x2) domain, 16 frequency slabs per
-                # class, A^T(.)A in the reduce
-                ncls = H.value("adh_conv_wgrad_wino32_classes", C.byref(d))
-                # (conv_wgrad32v2_kernel runs the classes of a k4 s2 form in ONE grid: classes x groups workgroup groups)
-                launches = max(1, H.value("adh_conv_wgrad_wino32_launches", C.byref(d)))
-                nsplit = _rows_nsplit(w32_groups * ncls // launches, H.value("adh_conv_wgrad_wino32_tiles", C.byref(d)),
-                                      launches=launches, slab_bytes=ncls * 16 * KP * NcP * 4, tile_us=5.0,
-                                      max_splits=max(1, _SLAB_BUDGET // (ncls * 16 * KP * NcP * 4)))
-                while nsplit * ncls * 16 * KP * NcP * 4 > (1 << 30) and nsplit > 1:
-                    nsplit //= 2
-                slab = self._f(nsplit * ncls * 16 * KP * NcP)
-                H.call("adh_conv_wgrad_wino32", C.byref(d), slab.data_ptr(), nsplit,
-                       work=2.0 * d.N * d.VH * d.VW * T * L.K * L.Nc, work_exec=2.0 * d.N * d.VH * d.VW * T * (4.0 / 9.0) * L.K * L.Nc)
-                H.call("adh_wgrad_reduce_wino32", slab.data_ptr(), nsplit, C.byref(d), KP, NcP, C.byref(L), dw.data_ptr(), 0)
-                continue
-            nsplit = max(1, min(ntiles_est, max(1, 1024 // groups), 512))
+            # the row-split kernel (conv_wgrad_rows_kernel) where it takes the shape, else the general one: one 512-thread
+            # workgroup per CU is resident, aim at ~4 rounds of 256 workgroups
+            ntiles_est = x.N * ((VH + 3) // 4) * ((VW + 31) // 32)
             rows_groups = H.value("adh_conv_wgrad_groups", C.byref(d))
             if rows_groups:
                 nsplit = _rows_nsplit(rows_groups, ntiles_est)
-            T = gm["KH"] * gm["KW"]
+            else:
+                groups = (KP // 32) * max(1, NcP // 96) * (7 if T == 49 else 1)
+                nsplit = max(1, min(ntiles_est, max(1, 1024 // groups), 512))
             nslabs = H.value("adh_conv_wgrad_slabs", C.byref(d), nsplit)
-            # cap the slab at 1 GiB
-            while nslabs * T * KP * NcP * 4 > (1 << 30) and nsplit > 1:
+            # cap the slab at 1 GiB (the slab count is the kernel's to say: not _split_slab's recipe)
+            while nslabs * T * KP * NcP * 4 > _SLAB_BUDGET and nsplit > 1:
                 nsplit //= 2
                 nslabs = H.value("adh_conv_wgrad_slabs", C.byref(d), nsplit)
             slab = self._f(nslabs * T * KP * NcP)
@@ -705,38 +690,31 @@ class Engine:
         shapes -- the caller launches the classes one by one."""
         descs = []
         for L, gm in plans:
-            NcP = _round_up(L.Nc, 32)
-            if gm["vgrid"] == "in":
-                VH = (g_y.shape[1] - gm["out_o"][0] + 1) // 2
-                VW = (g_y.shape[2] - gm["out_o"][1] + 1) // 2
-            else:
-                VH, VW = g_y.shape[1], g_y.shape[2]
-            descs.append(self._conv_desc(x, _round_up(L.K, 4), g_y, _round_up(gC, 4), NcP, VH, VW, gm["KH"], gm["KW"], gm["in_s"],
-                                         gm["out_s"], gm["out_o"], gm["dy0"], gm["dx0"], gm["dstep"]))
+            VH, VW = _virtual_grid(gm, g_y)
+            descs.append(self._conv_desc(x, _round_up(L.K, 4), g_y, _round_up(gC, 4), _round_up(L.Nc, 32), VH, VW, gm["KH"],
+                                         gm["KW"], gm["in_s"], gm["out_s"], gm["out_o"], gm["dy0"], gm["dx0"], gm["dstep"]))
         L0 = plans[0][0]
         d0, n = descs[0], len(descs)
         KP, NcP = d0.Cin, d0.NcP
         if any(L.K != L0.K or L.Nc != L0.Nc for L, _ in plans) or KP != _round_up(L0.K, 32):
             return False
-        groups = H.value("adh_conv_wgrad_wino32_groups", C.byref(d0))
-        if not groups or H.value("adh_conv_wgrad_wino32_classes", C.byref(d0)) != 1:
+        fam = _WGRAD_WINO32
+        groups = H.value(fam.groups, C.byref(d0))
+        if not groups or H.value(fam.classes, C.byref(d0)) != 1:
             return False
-        plane = 16 * KP * NcP
-        nsplit = _rows_nsplit(groups * n, H.value("adh_conv_wgrad_wino32_tiles", C.byref(d0)), slab_bytes=n * plane * 4,
-                              tile_us=5.0, max_splits=max(1, _SLAB_BUDGET // (n * plane * 4)))
-        slab = self._f(nsplit * n * plane)
+        plane = fam.planes * KP * NcP
+        nsplit, slab = self._split_slab(groups * n, H.value(fam.tiles, C.byref(d0)), n * plane, tile_us=fam.tile_us)
         arr = (H.ConvDesc * n)(*descs)
         work = sum(2.0 * dd.N * dd.VH * dd.VW * 4 * L.K * L.Nc for dd, (L, _) in zip(descs, plans))
         try:
-            H.call("adh_conv_wgrad_wino32_multi", arr, n, slab.data_ptr(), nsplit, work=work, work_exec=work * 4.0 / 9.0,
-                   family="adh_conv_wgrad_wino32")
+            H.call("adh_conv_wgrad_wino32_multi", arr, n, slab.data_ptr(), nsplit, work=work, work_exec=work * fam.exec_factor,
+                   family=fam.launch)
         except RuntimeError as e:
             if "unsupported" not in str(e).lower():
                 raise
             return False
         for m, (L, _) in enumerate(plans):     # the splits are summed: one class plane each
-            H.call("adh_wgrad_reduce_wino32", slab.data_ptr() + m * plane * 4, 1, C.byref(descs[m]), KP, NcP, C.byref(L),
-                   dw.data_ptr(), 0)
+            H.call(fam.reduce, slab.data_ptr() + m * plane * 4, 1, C.byref(descs[m]), KP, NcP, C.byref(L), dw.data_ptr(), 0)
         return True
 
     def _wgrad_packed_stem(self, gm, x: Act, g_y: torch.Tensor, gC: int, w: torch.Tensor, dw: torch.Tensor):
