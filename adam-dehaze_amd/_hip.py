@@ -190,6 +190,7 @@ _SIGNATURES = {
     "adh_psnr": [vp, vp, vp, i32, i64, f32, vp, i32, vp, vp],
     "adh_ssim_num_blocks": [i32, i32],
     "adh_ssim_gray": [vp, vp, vp, i32, i32, i32, f32, vp, i32, vp],
+    "adh_ssim_gray_bwd": [vp, vp, vp, i32, i32, i32, f32, vp, vp],
     "adh_add_inplace": [vp, vp, vp, i64],
     "adh_axpby_strided": [vp, vp, i32, vp, i32, i64, i32, f32, f32],
     "adh_maxpool": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp],

@@ -1,6 +1,7 @@
 """Losses of the hot path (/root/reference training/loss.py) on the HIP kernels.
 
-`DehazingLoss` = 1.0*L1 + 0.1*content(VGG16 taps) + 0.1*LPIPS(alex); `JointLoss` adds 0.2*CE
+`DehazingLoss` = 1.0*L1 + 0.1*content(VGG16 taps) + 0.1*LPIPS(alex) (+ lambda_ssim * (1 - SSIM), off by default: a
+structural term that needs no pretrained weights, not in the reference); `JointLoss` adds 0.2*CE
 (+ 0.5 * detection, always 0 in the drivers).  Forward signatures and returned dict keys follow
 loss.py:125-162 and :179-224.  The third-party feature networks (VGG16 / LPIPS-AlexNet) are built here
 with torchvision / lpips parameter names; their pretrained weights cannot be downloaded offline, so they
@@ -13,6 +14,7 @@ from typing import Optional
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import _hip as H
 
@@ -110,6 +112,37 @@ class _CE3Fn(torch.autograd.Function):
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
         return dl * g, None
+
+
+class _SSIMFn(torch.autograd.Function):
+    """Per-image SSIM [N] of metrics.ssim_batch (the same launch, so the same bits) with the gradient for `pred` from
+    csrc/ssim_loss.hip.  Nothing but the two images is saved: the backward recomputes the window statistics."""
+
+    @staticmethod
+    def forward(ctx, pred, target, data_range):
+        from .metrics import ssim_batch
+        out = ssim_batch(pred, target, data_range)          # checks devices, dtypes, shapes and the 7x7 minimum
+        ctx.data_range = float(data_range)
+        ctx.save_for_backward(pred.contiguous(), target.contiguous())
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        pred, target = ctx.saved_tensors
+        N, _, Hh, Ww = pred.shape
+        g = g.to(torch.float32).contiguous()                # [N], stays on the device
+        gp = torch.empty_like(pred)
+        H.call("adh_ssim_gray_bwd", pred.data_ptr(), target.data_ptr(), N, Hh, Ww, ctx.data_range, g.data_ptr(), gp.data_ptr())
+        return gp, None, None
+
+
+def ssim_per_image(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0) -> torch.Tensor:
+    """Differentiable per-image SSIM [N] (channel-mean grayscale, skimage defaults): the value of metrics.ssim_batch, bit
+    for bit, with a gradient for `pred`; `target` gets none."""
+    return _SSIMFn.apply(pred, target.detach(), data_range)
 
 
 def l1_loss(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -456,14 +489,31 @@ class PerceptualLoss(nn.Module):
         return _LPIPSFn.apply(self, record, x, target)
 
 
+class SSIMLoss(nn.Module):
+    """1 - mean over the batch of the per-image SSIM: 0 for identical images, up to 2."""
+
+    def __init__(self, data_range=1.0):
+        super().__init__()
+        self.data_range = data_range
+
+    def forward(self, pred, target):
+        return 1.0 - ssim_per_image(pred, target, self.data_range).mean()
+
+
 class DehazingLoss(nn.Module):
     """Combined loss for image dehazing (loss.py:110-162)."""
 
-    def __init__(self, lambda_l1=1.0, lambda_content=0.1, lambda_perceptual=0.1, content=True, perceptual=True):
+    def __init__(self, lambda_l1=1.0, lambda_content=0.1, lambda_perceptual=0.1, content=True, perceptual=True,
+                 lambda_ssim=0.0):
         """`content` / `perceptual` = False drop the VGG16 / LPIPS terms (their pretrained weights cannot be
-        downloaded here: the extractors are randomly initialised until a checkpoint is loaded)."""
+        downloaded here: the extractors are randomly initialised until a checkpoint is loaded).  `lambda_ssim` > 0 adds
+        lambda_ssim * (1 - mean SSIM) and the key 'ssim' to the returned dict; 0 (the reference) launches nothing extra."""
         super().__init__()
         self.lambda_l1, self.lambda_content, self.lambda_perceptual = lambda_l1, lambda_content, lambda_perceptual
+        self.lambda_ssim = float(lambda_ssim)
+        if self.lambda_ssim < 0:
+            raise ValueError(f"lambda_ssim must be >= 0, got {lambda_ssim}")
+        self.ssim_loss = SSIMLoss() if self.lambda_ssim > 0 else None
         self.content_loss = ContentLoss() if content else None
         self.perceptual_loss = PerceptualLoss() if perceptual else None
 
@@ -475,7 +525,11 @@ class DehazingLoss(nn.Module):
         if perceptual.dim() > 0:
             perceptual = perceptual.mean()
         total = self.lambda_l1 * l1 + self.lambda_content * content + self.lambda_perceptual * perceptual
-        return total, {"l1": l1, "content": content, "perceptual": perceptual, "total": total}
+        if self.ssim_loss is None:
+            return total, {"l1": l1, "content": content, "perceptual": perceptual, "total": total}
+        ssim = self.ssim_loss(pred, target)
+        total = total + self.lambda_ssim * ssim
+        return total, {"l1": l1, "content": content, "perceptual": perceptual, "ssim": ssim, "total": total}
 
 
 class JointLoss(nn.Module):
@@ -486,7 +540,7 @@ class JointLoss(nn.Module):
         self.lambda_dehazing = lambda_dehazing
         self.lambda_classification = lambda_classification
         self.lambda_detection = lambda_detection
-        self.dehazing_loss = DehazingLoss()
+        self.dehazing_loss = DehazingLoss(lambda_ssim=_lambda_ssim(config))
 
     def forward(self, pred, target_clear, pred_intensity=None, target_intensity=None, detection_loss=None):
         dehazing_loss, comps = self.dehazing_loss(pred, target_clear)
@@ -501,9 +555,14 @@ class JointLoss(nn.Module):
                        "detection": detection_component, "total": total, "dehazing_components": comps}
 
 
+def _lambda_ssim(config) -> float:
+    """`loss.lambda_ssim` of the config (absent in the reference's: 0, the term is off)."""
+    return float(((config or {}).get("loss") or {}).get("lambda_ssim", 0.0))
+
+
 def get_dehazing_loss(config):
     """loss.py:226-232."""
-    return DehazingLoss(lambda_l1=1.0, lambda_content=0.1, lambda_perceptual=0.1)
+    return DehazingLoss(lambda_l1=1.0, lambda_content=0.1, lambda_perceptual=0.1, lambda_ssim=_lambda_ssim(config))
 
 
 def get_joint_loss(config):

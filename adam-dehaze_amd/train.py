@@ -140,8 +140,11 @@ def joint_train_step(system: Dict, batch: Dict) -> Dict:
     if sync is not None:
         sync.finish()
     system["optimizer"].step()
-    return {"loss": loss.detach(), "dehazing": comps["dehazing"].detach(),
-            "classification": comps["classification"].detach()}
+    stats = {"loss": loss.detach(), "dehazing": comps["dehazing"].detach(),
+             "classification": comps["classification"].detach()}
+    if "ssim" in comps["dehazing_components"]:         # loss.lambda_ssim > 0 only
+        stats["ssim"] = comps["dehazing_components"]["ssim"].detach()
+    return stats
 
 
 def dehazing_train_step(model, criterion, optimizer, batch: Dict, level: Optional[int], device, sync=None):
@@ -174,7 +177,10 @@ def dehazing_train_step(model, criterion, optimizer, batch: Dict, level: Optiona
     optimizer.step()
     if empty:
         return None
-    return {"loss": loss.detach(), "l1": comps["l1"].detach()}
+    stats = {"loss": loss.detach(), "l1": comps["l1"].detach()}
+    if "ssim" in comps:                                # loss.lambda_ssim > 0 only
+        stats["ssim"] = comps["ssim"].detach()
+    return stats
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -433,10 +439,12 @@ def train_joint_model(config, train_loader=None, val_loader=None, steps_per_epoc
         for m in system["models"].values():
             m.train()
         system["router"].train()
-        total, n = None, 0
+        total, ssim_total, n = None, None, 0
         for batch in loader_for(train_loader, epoch, steps_per_epoch, 0):
             stats = joint_train_step(system, batch)
             total = stats["loss"] if total is None else total + stats["loss"]
+            if "ssim" in stats:
+                ssim_total = stats["ssim"] if ssim_total is None else ssim_total + stats["ssim"]
             n += 1
         _sync_buffers_from_rank0(system["sync"], system["router"])
         val = validate_joint(system, loader_for(val_loader, 0, val_steps, 500000))   # a fixed validation set
@@ -445,7 +453,8 @@ def train_joint_model(config, train_loader=None, val_loader=None, steps_per_epoc
         rec = {"epoch": epoch, "train_loss": train_loss, **val, "lr": system["optimizer"].param_groups[0]["lr"]}
         history.append(rec)
         if rank == 0:
-            print(f"Epoch {epoch + 1}/{epochs}:\n  Train Loss: {train_loss:.4f}\n  Val Loss: {val['val_loss']:.4f} "
+            ssim_part = "" if ssim_total is None else f" (1 - SSIM: {float(ssim_total) / max(1, n):.4f}, this rank)"
+            print(f"Epoch {epoch + 1}/{epochs}:\n  Train Loss: {train_loss:.4f}{ssim_part}\n  Val Loss: {val['val_loss']:.4f} "
                   f"(Dehaze: {val['val_dehaze_loss']:.4f}, Class: {val['val_class_loss']:.4f})\n"
                   f"  Val PSNR: {val['val_psnr']:.2f} dB, Val SSIM: {val['val_ssim']:.4f}")
             if val["val_psnr"] > best_val_psnr:
@@ -515,16 +524,21 @@ def train_dehazing_model(config, intensity_level: str, train_loader=None, val_lo
     try:
         for epoch in range(start_epoch, epochs):
             model.train()
+            ssim_terms = []
             for batch in loader_for(train_loader, epoch, steps, 0):
                 st = dehazing_train_step(model, criterion, optimizer, batch, level, device, sync=sync)
                 if st is not None:
                     losses.append(st["loss"])
+                    if "ssim" in st:
+                        ssim_terms.append(st["ssim"])
             _sync_buffers_from_rank0(sync, model)
             val = validate_dehazing(model, criterion, loader_for(val_loader, 0, val_steps, 500000), level, device)
             scheduler.step(val["val_loss"])
             if rank == 0:
                 print(f"Epoch {epoch + 1}/{epochs}:\n  Val Loss: {val['val_loss']:.4f}, Val PSNR: {val['val_psnr']:.2f}, "
                       f"Val SSIM: {val['val_ssim']:.4f}")
+                if ssim_terms:                         # the opt-in loss term, mean over this rank's steps like the L1 term
+                    print(f"  Train 1 - SSIM: {float(torch.stack(ssim_terms).mean()):.4f}")
                 if val["val_psnr"] > best_val_psnr:
                     save_checkpoint_atomic(dehazing_checkpoint(model, optimizer, scheduler, epoch, val),
                                            os.path.join(ck_dir, "best_model.pth"))

@@ -544,6 +544,13 @@ int adh_psnr(void* stream, const float* pred, const float* target, int N, int64_
 int adh_ssim_num_blocks(int H, int W);
 int adh_ssim_gray(void* stream, const float* pred_nchw, const float* target_nchw, int N, int H, int W, float data_range,
                   double* partial, int nblk, float* ssim);
+/* Gradient of exactly that number with respect to pred (ssim_loss.hip): g_pred[n][ch][p] = g_ssim[n] * d ssim[n] / d pred[n][ch][p],
+ * the three channels of a pixel alike (the grayscale weighs them 1/3 each).  One fused pass that recomputes the window
+ * statistics (nothing is saved by the forward), float64 after the fp32 grayscale with one rounding at the store, no atomics, no
+ * workspace.  g_ssim: float[N] on the device; g_pred: float[N*3*H*W], written, not accumulated, exact zeros for an image whose
+ * g_ssim is 0; it may not overlap pred or target (ADH_E_ARG).  ADH_E_UNSUPPORTED when H or W < 7.  No gradient for target. */
+int adh_ssim_gray_bwd(void* stream, const float* pred_nchw, const float* target_nchw, int N, int H, int W, float data_range,
+                      const float* g_ssim, float* g_pred_nchw);
 
 /* ---- Depthwise convolution and squeeze-excitation (torchvision MobileNetV2 / V3; depthwise.hip) ------------------------
  * Conv2d(C, C, k, stride, padding (k-1)/2, groups=C, bias=False) on NHWC fp32 activations with channel strides x_cs /
