@@ -272,6 +272,24 @@ def _virtual_grid(gm: dict, t: torch.Tensor) -> Tuple[int, int]:
     return t.shape[1], t.shape[2]
 
 
+# What Engine.conv keeps of a layer for Engine._conv_backward, per mode; a bare convolution keeps nothing (None)
+class _ConvTrain(NamedTuple):       # batch statistics
+    y: torch.Tensor                 # raw convolution output
+    mean: torch.Tensor
+    invstd: torch.Tensor
+    ss: torch.Tensor                # {scale, shift}
+    mbits: Optional[torch.Tensor]   # bit-packed ReLU mask of a residual tail (USE_RELU_BITS)
+
+
+class _ConvEval(NamedTuple):        # frozen BatchNorm folded into the convolution's epilogue
+    scale: torch.Tensor
+
+
+class _ConvEvalAct(NamedTuple):     # frozen statistics, BatchNorm + activation as a pass of their own
+    y: torch.Tensor
+    ss: torch.Tensor
+
+
 class Engine:
     def __init__(self, device: torch.device, record: bool):
         self.device = device
@@ -289,6 +307,19 @@ class Engine:
     # ------------------------------------------------------------------ helpers
     def _f(self, *shape, zero=False):
         return (torch.zeros if zero else torch.empty)(shape, device=self.device, dtype=torch.float32)
+
+    def _buf(self, *shape, dtype):
+        """An uninitialised buffer that is not float32: int32 indices, uint8 mask bits, float64 sums, a copy of an input."""
+        return torch.empty(shape, device=self.device, dtype=dtype)
+
+    def _on_grad(self, o: Act, fn: Callable[[torch.Tensor], None], x: Optional[Act] = None):
+        """Record the backward of the op that produced `o`: take and clear o.grad, and call fn(gradient) unless none
+        arrived -- or unless `x`, the input the op's only gradient goes to, wants none."""
+        def bwd():
+            g, o.grad = o.grad, None
+            if g is not None and (x is None or x.needs_grad):
+                fn(g)
+        self.tape.append(bwd)
 
     def use_param(self, *ps: Optional[torch.Tensor]):
         """Forward-side bookkeeping: each recorded op declares the parameters its backward closure will add a gradient
@@ -357,15 +388,11 @@ class Engine:
                out.data_ptr())
         a = Act(out, 8, needs_grad=self.record)
         if self.record:
-            def bwd():
-                g = a.grad
-                a.grad = None
-                if g is None:
-                    return
-                gx = torch.empty_like(x)
+            def bwd(g):
+                gx = self._buf(*x.shape, dtype=x.dtype)
                 H.call("adh_image_normalize_bwd", g.data_ptr(), g.stride(2), N, Hh, Ww, inv[0], inv[1], inv[2], gx.data_ptr())
                 holder["gx"] = gx
-            self.tape.append(bwd)
+            self._on_grad(a, bwd)
         return a
 
     def mse(self, a: Act, b: Act, scale: float, sink: list):
@@ -734,21 +761,170 @@ class Engine:
         H.call("adh_wgrad_reduce_packed", slab.data_ptr(), nsplit, NcP, Cin, KH, KW, Cout, dw.data_ptr(), 0)
         return dw
 
-    def _channel_sum(self, g: torch.Tensor, Cc: int) -> torch.Tensor:
-        """sum over pixels of g[..., :Cc] (bias gradient) using the BN-backward reduction kernels."""
-        P = g.shape[0] * g.shape[1] * g.shape[2]
-        C4 = _round_up(Cc, 4)
+    # ------------------------------------------------------------------ BatchNorm sequences (bn_act.hip)
+    # Every BatchNorm layer of every network -- Engine.conv, dwconv, bn_relu_preact -- folds and differentiates through these.
+    def _bn_train_fold(self, bn: BNState, stats: torch.Tensor, nblk: int, pitch: int, P: int, ss: torch.Tensor):
+        """Train-mode fold of the per-block sums `stats` [nblk][2][pitch] of a raw layer output over P pixels: {scale, shift}
+        into ss[0] / ss[1], the running-buffer update, and (mean, invstd) for the backward pass."""
+        Cc = bn.weight.numel()
+        mean, invstd = self._f(Cc), self._f(Cc)
+        fold = (bn.weight.data_ptr(), bn.bias.data_ptr(), bn.eps, bn.momentum, bn.running_mean.data_ptr(),
+                bn.running_var.data_ptr(), ss[0].data_ptr(), ss[1].data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                H.ptr(bn.num_batches_tracked))
+        if SYNC_BN is not None:
+            # statistics over the GLOBAL batch: local sums in fp64 -> all-reduce of 2 C + 1 doubles -> finalize
+            sums = self._buf(2 * Cc + 1, dtype=torch.float64)
+            H.call("adh_bn_partial_sums", stats.data_ptr(), nblk, pitch, Cc, float(P), sums.data_ptr())
+            SYNC_BN(sums)
+            H.call("adh_bn_finalize_sums", sums.data_ptr(), Cc, *fold)
+        else:
+            H.call("adh_bn_finalize", stats.data_ptr(), nblk, pitch, Cc, float(P), *fold)
+        return mean, invstd
+
+    def _bn_fold_eval(self, bn: BNState, scale: torch.Tensor, shift: Optional[torch.Tensor] = None,
+                      conv_bias: Optional[torch.Tensor] = None):
+        """Eval-mode fold of the running statistics with gamma / beta (and the bias of the convolution in front) into
+        `scale` / `shift`.  shift=None is the invstd-only form: without gamma and beta the scale comes out as
+        1 / sqrt(running_var + eps), and the shift goes to a buffer nobody reads."""
+        gamma, beta = (bn.weight, bn.bias) if shift is not None else (None, None)
+        if shift is None:
+            shift = self._f(scale.numel())
+        H.call("adh_bn_fold_eval", bn.running_mean.numel(), H.ptr(gamma), H.ptr(beta), bn.running_mean.data_ptr(),
+               bn.running_var.data_ptr(), bn.eps, H.ptr(conv_bias), scale.data_ptr(), shift.data_ptr())
+
+    def _bn_bwd_reduce(self, g: torch.Tensor, out: Optional[Act], act: int, y: torch.Tensor, mean: torch.Tensor,
+                       invstd: torch.Tensor, P: int, C4: int, mask_ss: Optional[torch.Tensor] = None,
+                       mbits: Optional[torch.Tensor] = None, work: float = 0.0):
+        """(partial [nblk][2][C4], nblk): per-block rows of (sum m g, sum m g xhat), xhat = (y - mean) * invstd and m the
+        activation's derivative -- recomputed from y with `mask_ss` = {scale, shift}, read from `mbits`, or from `out`."""
         nblk = H.value("adh_bn_bwd_num_blocks", P, C4)
         partial = self._f(nblk, 2, C4)
-        zeros = self._f(C4, zero=True)
-        H.call("adh_bn_bwd_reduce", g.data_ptr(), g.stride(2), None, 0, H.ACT_NONE, g.data_ptr(), g.stride(2),
-               zeros.data_ptr(), zeros.data_ptr(), partial.data_ptr(), P, C4, None, None)
-        dbeta = self._f(C4)
+        H.call("adh_bn_bwd_reduce", g.data_ptr(), g.stride(2), H.ptr(out.t) if out is not None else None,
+               out.cs if out is not None else 0, act, y.data_ptr(), y.stride(2), mean.data_ptr(), invstd.data_ptr(),
+               partial.data_ptr(), P, C4, H.ptr(mask_ss), H.ptr(mbits), work=work)
+        return partial, nblk
+
+    def _bn_bwd_finalize(self, partial: torch.Tensor, nblk: int, P: int, C4: int, gamma: Optional[torch.Tensor],
+                         invstd: torch.Tensor, dgamma: Optional[torch.Tensor], dbeta: torch.Tensor) -> torch.Tensor:
+        """Sum the rows of _bn_bwd_reduce into dgamma / dbeta; returns the data-gradient coefficients [3][C4]."""
         coef = self._f(3, C4)
-        H.call("adh_bn_bwd_finalize", partial.data_ptr(), nblk, C4, float(P), None, zeros.data_ptr(), None,
+        H.call("adh_bn_bwd_finalize", partial.data_ptr(), nblk, C4, float(P), H.ptr(gamma), invstd.data_ptr(), H.ptr(dgamma),
                dbeta.data_ptr(), 0, coef.data_ptr())
+        return coef
+
+    def _bn_bwd_apply(self, g: torch.Tensor, out: Optional[Act], act: int, y: Optional[torch.Tensor],
+                      mean: Optional[torch.Tensor], invstd: Optional[torch.Tensor], coef: torch.Tensor, train: int,
+                      g_y: torch.Tensor, g_res: Optional[torch.Tensor], P: int, C4: int,
+                      mask_ss: Optional[torch.Tensor] = None, mbits: Optional[torch.Tensor] = None, work: float = 0.0):
+        """The data-gradient pass: g_y = the gradient at the raw layer output y, g_res = the masked gradient for a residual
+        input.  train = 0: g_y = coef[0] * m * g (frozen statistics, or no BatchNorm at all with an identity row)."""
+        H.call("adh_bn_bwd_apply", g.data_ptr(), g.stride(2), H.ptr(out.t) if out is not None else None,
+               out.cs if out is not None else 0, act, H.ptr(y), y.stride(2) if y is not None else 0, H.ptr(mean), H.ptr(invstd),
+               coef.data_ptr(), train, g_y.data_ptr(), g_y.stride(2), H.ptr(g_res), g_res.stride(2) if g_res is not None else 0,
+               P, C4, H.ptr(mask_ss), H.ptr(mbits), work=work)
+
+    def _bn_grad_buffers(self, bn: BNState, C4: int):
+        """Where the finalize kernels write d-gamma / d-beta (C4 floats each): the parameters' gradient buffers when the
+        channel count is a whole number of quads, else scratch the caller slices."""
+        if C4 == bn.weight.numel():
+            return self.grad_buffer(bn.weight), self.grad_buffer(bn.bias)
+        return self._f(C4), self._f(C4)
+
+    @staticmethod
+    def _bn_bwd_reads(act: int, mask_ss, mbits) -> int:
+        """Tensors a backward pass reads: g and y, and `out` when the ReLU mask can come from nowhere else."""
+        return 3 if (act == H.ACT_RELU and mask_ss is None and mbits is None) else 2
+
+    def _bn_train_coef(self, bn: BNState, g, out, act, y, mean, invstd, mask_ss, mbits, P: int, C4: int, fused=None):
+        """Train-mode backward up to the data-gradient pass: the reduce (unless `fused` = (rows, nrows, pitch, .) came with g
+        from the consumer's data-gradient epilogue), then the finalize.  Returns (coef, dgamma, dbeta); the caller runs its
+        own data-gradient pass and then adds the parameter gradients."""
+        Cc = bn.weight.numel()
+        if SYNC_BN is not None:
+            fused = None     # the all-reduce takes the fp64 sums of a reduce pass
+        if fused is None:
+            partial, nblk = self._bn_bwd_reduce(g, out, act, y, mean, invstd, P, C4, mask_ss, mbits,
+                                                work=4.0 * P * Cc * self._bn_bwd_reads(act, mask_ss, mbits))
+        dgamma, dbeta = self._bn_grad_buffers(bn, C4)
+        if SYNC_BN is not None:
+            # d-gamma / d-beta: local sums (averaged with the other gradients); the means inside the input gradient:
+            # global sums (torch.nn.SyncBatchNorm's backward)
+            coef = self._f(3, C4)
+            loc, glob = self._buf(2 * C4 + 1, dtype=torch.float64), self._buf(2 * C4 + 1, dtype=torch.float64)
+            H.call("adh_bn_partial_sums", partial.data_ptr(), nblk, C4, C4, float(P), loc.data_ptr())
+            glob.copy_(loc)
+            SYNC_BN(glob)
+            H.call("adh_bn_bwd_finalize_sums", loc.data_ptr(), glob.data_ptr(), C4, bn.weight.data_ptr(), invstd.data_ptr(),
+                   dgamma.data_ptr(), dbeta.data_ptr(), 0, coef.data_ptr())
+        elif fused is not None:
+            # rows of (sum g m, sum g m (y - mean))
+            coef = self._f(3, C4)
+            H.call("adh_bn_bwd_finalize_centered", fused[0].data_ptr(), fused[1], fused[2], C4, float(P), bn.weight.data_ptr(),
+                   invstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), 0, coef.data_ptr())
+        else:
+            coef = self._bn_bwd_finalize(partial, nblk, P, C4, bn.weight, invstd, dgamma, dbeta)
+        return coef, dgamma[:Cc], dbeta[:Cc]
+
+    def _bn_train_backward(self, bn: BNState, g, out, act, y, mean, invstd, mask_ss, mbits, g_y, g_res, P: int, C4: int,
+                           fused=None):
+        """Train-mode backward of out = act(BN(y) (+ residual)): _bn_train_coef, the data-gradient pass into g_y (and g_res),
+        then the d-gamma / d-beta."""
+        coef, dgamma, dbeta = self._bn_train_coef(bn, g, out, act, y, mean, invstd, mask_ss, mbits, P, C4, fused)
+        reads = self._bn_bwd_reads(act, mask_ss, mbits) + 1 + (1 if g_res is not None else 0)     # + write g_y (+ g_res)
+        self._bn_bwd_apply(g, out, act, y, mean, invstd, coef, 1, g_y, g_res, P, C4, mask_ss, mbits,
+                           work=4.0 * P * bn.weight.numel() * reads)
+        self.add_param_grad(bn.weight, dgamma)
+        self.add_param_grad(bn.bias, dbeta)
+
+    def _bn_frozen_param_grads(self, bn: BNState, g, out, act, y, mean, inv, P: int, C4: int, mask_ss, work: float = 0.0):
+        """d-gamma / d-beta of a BatchNorm with frozen statistics and trainable gamma / beta (fine-tuning under
+        module.eval()): xhat = (y - running_mean) * invstd.  `mean`: the running mean over C4 channels; `inv`: C4 floats the
+        invstd is folded into.  Returns (dgamma, dbeta) for the caller to add after its data-gradient pass."""
+        Cc = bn.weight.numel()
+        self._bn_fold_eval(bn, inv)
+        partial, nblk = self._bn_bwd_reduce(g, out, act, y, mean, inv, P, C4, mask_ss, work=work)
+        dgamma, dbeta = self._bn_grad_buffers(bn, C4)
+        self._bn_bwd_finalize(partial, nblk, P, C4, None, inv, dgamma, dbeta)
+        return dgamma[:Cc], dbeta[:Cc]
+
+    def _bn_act_eval_backward(self, g: torch.Tensor, y: torch.Tensor, ss: torch.Tensor, bn: BNState, act_code: int,
+                              g_y: torch.Tensor, P: int, Cc: int, out: Optional[Act] = None,
+                              g_res: Optional[torch.Tensor] = None):
+        """Backward of out = act(y * scale + shift (+ residual)) with frozen BatchNorm statistics (scale / shift =
+        ss[0] / ss[1], folded from the running estimates): g_y = scale * act'(z) * g, g_res = act'(z) * g, and d-gamma /
+        d-beta when the BN parameters train.  `out`: the block output of a residual tail (NONE / RELU), whose ReLU mask is
+        read from it."""
+        C4 = _round_up(Cc, 4)
+        coef = self._f(3, C4, zero=True)
+        coef[0].copy_(ss[0])
+        mask_ss = ss if (act_code != H.ACT_NONE and out is None) else None
+        self._bn_bwd_apply(g, out, act_code, y, None, None, coef, 0, g_y, g_res, P, C4, mask_ss)
+        if not (bn.weight.requires_grad or bn.bias.requires_grad):
+            return
+        mean4, inv4 = self._f(C4, zero=True), self._f(C4, zero=True)
+        mean4[:Cc].copy_(bn.running_mean)
+        dgamma, dbeta = self._bn_frozen_param_grads(bn, g, out, act_code, y, mean4, inv4, P, C4, mask_ss)
+        self.add_param_grad(bn.weight, dgamma)
+        self.add_param_grad(bn.bias, dbeta)
+
+    def _identity_coef(self, rows: int, C4: int) -> torch.Tensor:
+        """[rows][C4] coefficients of no BatchNorm at all: scale 1 in row 0, zeros below."""
+        coef = self._f(rows, C4, zero=True)
+        coef[0].fill_(1.0)
+        return coef
+
+    def _channel_sum(self, g: torch.Tensor, Cc: int) -> torch.Tensor:
+        """sum over pixels of g[..., :Cc] (bias gradient) using the BN-backward reduction kernels: with mean = invstd = 0 and
+        no mask the first row of sums is sum g, which the finalize writes as d-beta."""
+        P = g.shape[0] * g.shape[1] * g.shape[2]
+        C4 = _round_up(Cc, 4)
+        zeros = self._f(C4, zero=True)
+        partial, nblk = self._bn_bwd_reduce(g, None, H.ACT_NONE, g, zeros, zeros, P, C4)
+        dbeta = self._f(C4)
+        self._bn_bwd_finalize(partial, nblk, P, C4, None, zeros, None, dbeta)
         return dbeta[:Cc]
 
+    # ------------------------------------------------------------------ ConvBlock
     def conv(self, x: Act, w: torch.Tensor, b: Optional[torch.Tensor], bn: Optional[BNState], *, kind: str = "conv",
              k: int = 3, stride: int = 1, pad: int = 1, relu: bool = True, residual: Optional[Act] = None,
              training: bool = False, out: Optional[torch.Tensor] = None, out_alloc_C: Optional[int] = None,
@@ -779,39 +955,28 @@ class Engine:
             ac = out_alloc_C if out_alloc_C is not None else _round_up(Cout, 8)
             out = self._f(N, OH, OW, ac, zero=(ac != Cout))
         _check_dense_pixels(out)
-        plans = self._launch_plan(kind, k, stride, pad, w, "fwd")
+        geom = (kind, k, stride, pad)
+        plans = self._launch_plan(*geom, w, "fwd")
         res_t = residual.t if residual is not None else None
         P = N * OH * OW
+        apply_work = 4.0 * P * Cout * (3 if res_t is not None else 2)     # bytes: read y (+ residual), write out
+        saved = None     # a bare convolution: nothing but the output is needed
 
         if bn is not None and training:
             # raw conv output + per-block statistics, then normalise (+residual, ReLU) in one streaming pass
             y = self._f(N, OH, OW, _round_up(Cout, 4))
             stats, nblk = self._run_gather(plans, x, y, Cout, w, shift=b, want_stats=True)
             ss = self._f(2, _round_up(Cout, 4), zero=True)   # {scale, shift}: kept for the backward ReLU mask
-            scale, shift = ss[0], ss[1]
-            mean, invstd = self._f(Cout), self._f(Cout)
-            NcP = _round_up(Cout, 32)
-            if SYNC_BN is not None:
-                # statistics over the GLOBAL batch: local sums in fp64 -> all-reduce of 2 C + 1 doubles -> finalize
-                sums = torch.empty(2 * Cout + 1, device=self.device, dtype=torch.float64)
-                H.call("adh_bn_partial_sums", stats.data_ptr(), nblk, NcP, Cout, float(P), sums.data_ptr())
-                SYNC_BN(sums)
-                H.call("adh_bn_finalize_sums", sums.data_ptr(), Cout, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.eps,
-                       bn.momentum, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                       mean.data_ptr(), invstd.data_ptr(), H.ptr(bn.num_batches_tracked))
-            else:
-                H.call("adh_bn_finalize", stats.data_ptr(), nblk, NcP, Cout, float(P), bn.weight.data_ptr(),
-                       bn.bias.data_ptr(), bn.eps, bn.momentum, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                       scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), H.ptr(bn.num_batches_tracked))
+            mean, invstd = self._bn_train_fold(bn, stats, nblk, _round_up(Cout, 32), P, ss)
             # residual + ReLU (ResidualBlock tail): the backward ReLU mask cannot be recomputed from y alone; keep it as one
             # bit per element (1/32 of `out`) written by this pass instead of reading `out` twice in the backward pass
             mbits = None
             if USE_RELU_BITS and relu and res_t is not None and self.record and Cout % 8 == 0:
-                mbits = torch.empty((P * Cout + 7) // 8, device=self.device, dtype=torch.uint8)
-            H.call("adh_bn_apply", y.data_ptr(), y.stride(2), scale.data_ptr(), shift.data_ptr(), H.ptr(res_t),
+                mbits = self._buf((P * Cout + 7) // 8, dtype=torch.uint8)
+            H.call("adh_bn_apply", y.data_ptr(), y.stride(2), ss[0].data_ptr(), ss[1].data_ptr(), H.ptr(res_t),
                    res_t.stride(2) if res_t is not None else 0, act_code, out.data_ptr(), out.stride(2), P, Cout, H.ptr(mbits),
-                   work=4.0 * P * Cout * (3 if res_t is not None else 2))     # bytes: read y (+ residual), write out
-            saved = ("train", y, mean, invstd, ss, mbits)
+                   work=apply_work)
+            saved = _ConvTrain(y, mean, invstd, ss, mbits)
         elif bn is not None:
             # frozen statistics with trainable gamma / beta (fine-tuning under module.eval()): d-gamma needs
             # xhat = (y - running_mean) * invstd, which the block output cannot give back where gamma == 0, so the raw conv
@@ -819,10 +984,9 @@ class Engine:
             bn_trains = self.record and (bn.weight.requires_grad or bn.bias.requires_grad)
             if act_code in (H.ACT_NONE, H.ACT_RELU) and not bn_trains:
                 scale, shift = self._f(Cout), self._f(Cout)
-                H.call("adh_bn_fold_eval", Cout, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                       bn.running_var.data_ptr(), bn.eps, H.ptr(b), scale.data_ptr(), shift.data_ptr())
+                self._bn_fold_eval(bn, scale, shift, conv_bias=b)
                 self._run_gather(plans, x, out, Cout, w, scale=scale, shift=shift, residual=res_t, act=act_code)
-                saved = ("eval", scale)
+                saved = _ConvEval(scale)
             else:
                 # the MFMA conv epilogues know NONE / RELU only: the raw conv (+ its bias), then the folded BN (+ residual) +
                 # activation in one pass (the two passes train mode takes); y is kept for xhat and the derivative at the
@@ -832,24 +996,22 @@ class Engine:
                 y = self._f(N, OH, OW, _round_up(Cout, 4))
                 self._run_gather(plans, x, y, Cout, w, shift=b)
                 ss = self._f(2, _round_up(Cout, 4), zero=True)
-                H.call("adh_bn_fold_eval", Cout, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                       bn.running_var.data_ptr(), bn.eps, None, ss[0].data_ptr(), ss[1].data_ptr())
+                self._bn_fold_eval(bn, ss[0], ss[1])
                 H.call("adh_bn_apply", y.data_ptr(), y.stride(2), ss[0].data_ptr(), ss[1].data_ptr(), H.ptr(res_t),
                        res_t.stride(2) if res_t is not None else 0, act_code, out.data_ptr(), out.stride(2), P, Cout, None,
-                       work=4.0 * P * Cout * (3 if res_t is not None else 2))
-                saved = ("eval_act", y, ss)
+                       work=apply_work)
+                saved = _ConvEvalAct(y, ss)
         elif stats is not None:
             assert b is None and res_t is None and act_code == H.ACT_NONE, "stats are taken of a bare convolution only"
             partials, nblk = self._run_gather(plans, x, out, Cout, w, want_stats=True)
             stats.append((partials, nblk, partials.shape[2]))
-            saved = ("plain",)
         else:
             self._run_gather(plans, x, out, Cout, w, shift=b, residual=res_t, act=act_code)
-            saved = ("plain",)
 
         o = Act(out, Cout)
-        if self.record and saved[0] == "train" and relu and residual is None and USE_BN_FUSED_REDUCE and SYNC_BN is None:
-            o.bn_src = (saved[1], saved[4], saved[2])
+        if self.record and isinstance(saved, _ConvTrain) and relu and residual is None and USE_BN_FUSED_REDUCE and \
+                SYNC_BN is None:
+            o.bn_src = (saved.y, saved.ss, saved.mean)
         if RELU_CAPTURE is not None and act_code in (H.ACT_RELU, H.ACT_RELU6):
             RELU_CAPTURE[id(w)] = out
         if self.record:
@@ -857,96 +1019,58 @@ class Engine:
             bn_grads = bn is not None and (training or bn.weight.requires_grad or bn.bias.requires_grad)
             self.use_param(w if (w.requires_grad or self.alias.get(id(w)) is not None) else None, b,
                            bn.weight if bn_grads else None, bn.bias if bn_grads else None)
-            self.tape.append(lambda: self._conv_backward(x, w, b, bn, kind, k, stride, pad, act_code, residual, o, saved))
+            self._on_grad(o, lambda g: self._conv_backward(g, x, w, b, bn, geom, act_code, residual, o, saved))
         return o
 
-    def _conv_backward(self, x: Act, w, b, bn, kind, k, stride, pad, act_code, residual, o: Act, saved):
-        g = o.grad
-        o.grad = None
-        if g is None:
-            return
+    def _conv_backward(self, g: torch.Tensor, x: Act, w, b, bn, geom, act_code, residual, o: Act, saved):
+        """`geom` = (kind, k, stride, pad) of the layer; `saved`: what Engine.conv kept of its mode (_ConvTrain / _ConvEval /
+        _ConvEvalAct), None for a bare convolution."""
         Cout = o.C
         C4 = _round_up(Cout, 4)
         N, OH, OW = o.N, o.Hh, o.Ww
         P = N * OH * OW
-        relu = act_code == H.ACT_RELU
-        mode = saved[0]
         C8 = _round_up(Cout, 8)
         g_y = self._f(N, OH, OW, C8, zero=(C8 != C4))   # padded channels must be finite zeros (dgrad reads them)
         g_res = None
         if residual is not None and residual.needs_grad:
             g_res = self._f(N, OH, OW, C4)
-        if mode == "train":
-            _, y, mean, invstd, ss, mbits = saved
+        if isinstance(saved, _ConvTrain):
             # without a residual the ReLU mask is recomputed from y (fma(y, scale, shift) > 0, the forward expression):
             # the two backward passes then read two tensors each instead of three
-            mask_ss = ss.data_ptr() if (act_code != H.ACT_NONE and residual is None) else None
-            fused = o.bn_partial if (o.bn_partial is not None and o.bn_partial[3] is g and SYNC_BN is None) else None
+            mask_ss = saved.ss if (act_code != H.ACT_NONE and residual is None) else None
+            # the sums came with g, from the consumer's data-gradient epilogue
+            fused = o.bn_partial if (o.bn_partial is not None and o.bn_partial[3] is g) else None
             o.bn_partial = None
-            if fused is None:
-                nblk = H.value("adh_bn_bwd_num_blocks", P, C4)
-                partial = self._f(nblk, 2, C4)
-                H.call("adh_bn_bwd_reduce", g.data_ptr(), g.stride(2), o.t.data_ptr(), o.cs, act_code, y.data_ptr(),
-                       y.stride(2), mean.data_ptr(), invstd.data_ptr(), partial.data_ptr(), P, C4, mask_ss, H.ptr(mbits),
-                       work=4.0 * P * Cout * (2 if (mask_ss is not None or mbits is not None or not relu) else 3))   # g, y (+ out)
-            if C4 == Cout:
-                dgamma, dbeta = self.grad_buffer(bn.weight), self.grad_buffer(bn.bias)
-            else:
-                dgamma, dbeta = self._f(C4), self._f(C4)
-            coef = self._f(3, C4)
-            if SYNC_BN is not None:
-                # d-gamma / d-beta: local sums (averaged with the other gradients); the means inside the input gradient:
-                # global sums (torch.nn.SyncBatchNorm's backward)
-                loc = torch.empty(2 * C4 + 1, device=self.device, dtype=torch.float64)
-                H.call("adh_bn_partial_sums", partial.data_ptr(), nblk, C4, C4, float(P), loc.data_ptr())
-                glob = loc.clone()
-                SYNC_BN(glob)
-                H.call("adh_bn_bwd_finalize_sums", loc.data_ptr(), glob.data_ptr(), C4, bn.weight.data_ptr(), invstd.data_ptr(),
-                       dgamma.data_ptr(), dbeta.data_ptr(), 0, coef.data_ptr())
-            elif fused is not None:
-                # the sums came with g: rows of (sum g m, sum g m (y - mean)) from the consumer's data-gradient epilogue
-                H.call("adh_bn_bwd_finalize_centered", fused[0].data_ptr(), fused[1], fused[2], C4, float(P), bn.weight.data_ptr(),
-                       invstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), 0, coef.data_ptr())
-            else:
-                H.call("adh_bn_bwd_finalize", partial.data_ptr(), nblk, C4, float(P), bn.weight.data_ptr(),
-                       invstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), 0, coef.data_ptr())
-            H.call("adh_bn_bwd_apply", g.data_ptr(), g.stride(2), o.t.data_ptr(), o.cs, act_code, y.data_ptr(),
-                   y.stride(2), mean.data_ptr(), invstd.data_ptr(), coef.data_ptr(), 1, g_y.data_ptr(), g_y.stride(2),
-                   H.ptr(g_res), g_res.stride(2) if g_res is not None else 0, P, C4, mask_ss, H.ptr(mbits),
-                   work=4.0 * P * Cout * ((2 if (mask_ss is not None or mbits is not None or not relu) else 3) + 1 +
-                                          (1 if g_res is not None else 0)))
-            self.add_param_grad(bn.weight, dgamma[:Cout])
-            self.add_param_grad(bn.bias, dbeta[:Cout])
+            self._bn_train_backward(bn, g, o, act_code, saved.y, saved.mean, saved.invstd, mask_ss, saved.mbits, g_y, g_res,
+                                    P, C4, fused)
             if b is not None:   # a bias feeding train-mode BN has an exactly zero gradient
                 self.add_param_grad(b, self._f(Cout, zero=True))
-        elif mode == "eval_act":
+        elif isinstance(saved, _ConvEvalAct):
             # with a residual the ReLU mask cannot be recomputed from y: it is read from the block output
-            self._bn_act_eval_backward(g, saved[1], saved[2], bn, act_code, g_y, P, Cout,
+            self._bn_act_eval_backward(g, saved.y, saved.ss, bn, act_code, g_y, P, Cout,
                                        out=o if residual is not None else None, g_res=g_res)
             if b is not None:
                 self.add_param_grad(b, self._channel_sum(g_y, Cout))
         else:
-            coef = self._f(3, C4, zero=True)
-            if mode == "eval":
-                coef[0, :Cout].copy_(saved[1])
+            if isinstance(saved, _ConvEval):
+                coef = self._f(3, C4, zero=True)
+                coef[0, :Cout].copy_(saved.scale)
             else:
-                coef[0].fill_(1.0)
-            H.call("adh_bn_bwd_apply", g.data_ptr(), g.stride(2), o.t.data_ptr(), o.cs, act_code, None, 0, None, None,
-                   coef.data_ptr(), 0, g_y.data_ptr(), g_y.stride(2), H.ptr(g_res),
-                   g_res.stride(2) if g_res is not None else 0, P, C4, None, None)
+                coef = self._identity_coef(3, C4)
+            self._bn_bwd_apply(g, o, act_code, None, None, None, coef, 0, g_y, g_res, P, C4)
             if b is not None:
                 self.add_param_grad(b, self._channel_sum(g_y, Cout))
         if g_res is not None:
             self.accum(residual, g_res)
         # weight gradient (skipped for frozen weights, e.g. the VGG16 feature extractor of the content loss)
         if w.requires_grad or self.alias.get(id(w)) is not None:
-            self.add_param_grad(w, self._wgrad(self._launch_plan(kind, k, stride, pad, w, "fwd"), x, g_y, Cout, w))
+            self.add_param_grad(w, self._wgrad(self._launch_plan(*geom, w, "fwd"), x, g_y, Cout, w))
         # data gradient
         if x.needs_grad:
-            plans = self._launch_plan(kind, k, stride, pad, w, "dgrad")
+            plans = self._launch_plan(*geom, w, "dgrad")
             gsrc = Act(g_y, Cout)
             if x.grad is None:
-                sparse = (kind == "conv" and stride == 2 and len(plans) < 4)
+                sparse = (geom[0] == "conv" and geom[2] == 2 and len(plans) < 4)
                 gx = self._f(x.N, x.Hh, x.Ww, _round_up(x.C, 4), zero=sparse)
                 # x = ReLU(BN(conv)) of a train-mode ConvBlock and this is the first gradient to reach it: take that BN's
                 # backward sums in this launch's epilogue.  They are used only if no other gradient is added to x.grad
@@ -966,9 +1090,9 @@ class Engine:
         Ch = w1.shape[0]
         nblk = H.value("adh_cbam_pool_num_blocks", HW)
         partial = self._f(N, nblk, 2, Cc)
-        partial_idx = torch.empty((N, nblk, Cc), device=self.device, dtype=torch.int32)
+        partial_idx = self._buf(N, nblk, Cc, dtype=torch.int32)
         pooled = self._f(N, 2, Cc)
-        amax_idx = torch.empty((N, Cc), device=self.device, dtype=torch.int32)
+        amax_idx = self._buf(N, Cc, dtype=torch.int32)
         xbytes = 4.0 * N * HW * Cc
         H.call("adh_cbam_pool", x.t.data_ptr(), x.cs, N, HW, Cc, partial.data_ptr(), partial_idx.data_ptr(), nblk,
                pooled.data_ptr(), amax_idx.data_ptr(), work=xbytes)
@@ -977,7 +1101,7 @@ class Engine:
         H.call("adh_cbam_mlp", pooled.data_ptr(), w1.data_ptr(), w2.data_ptr(), N, Cc, Ch, ca.data_ptr(),
                hidden.data_ptr())
         smap = self._f(N, HW, 2)
-        cidx = torch.empty((N, HW), device=self.device, dtype=torch.int32)
+        cidx = self._buf(N, HW, dtype=torch.int32)
         H.call("adh_cbam_spatial_stats", x.t.data_ptr(), x.cs, ca.data_ptr(), N, HW, Cc, smap.data_ptr(),
                cidx.data_ptr(), work=xbytes)
         sa = self._f(N, HW)
@@ -992,11 +1116,7 @@ class Engine:
         if self.record:
             self.use_param(wsp, w1, w2)
 
-            def bwd():
-                g = o.grad
-                o.grad = None
-                if g is None:
-                    return
+            def bwd(g):
                 gsa_pre = self._f(N, HW)
                 H.call("adh_cbam_bwd_a", g.data_ptr(), g.stride(2), x.t.data_ptr(), x.cs, ca.data_ptr(), sa.data_ptr(),
                        N, HW, Cc, gsa_pre.data_ptr(), work=2 * xbytes)
@@ -1024,7 +1144,7 @@ class Engine:
                            sa.data_ptr(), gsmap.data_ptr(), cidx.data_ptr(), gpool.data_ptr(), amax_idx.data_ptr(), N,
                            HW, Cc, gx.data_ptr(), gx.stride(2), work=2 * xbytes)   # reads g, writes gx (x itself is not read)
                     self.accum(x, gx)
-            self.tape.append(bwd)
+            self._on_grad(o, bwd)
         return o
 
     # ------------------------------------------------------------------ zero-copy concat
@@ -1047,14 +1167,10 @@ class Engine:
             off += p.C
         assert off == buf.shape[3]
         if self.record:
-            def bwd():
-                g = o.grad
-                o.grad = None
-                if g is None:
-                    return
+            def bwd(g):
                 for p, of in zip(parts, offs):
                     self.accum(p, g[..., of:of + p.C])
-            self.tape.append(bwd)
+            self._on_grad(o, bwd)
         return o
 
     # ------------------------------------------------------------------ pooling / resize (alt models, odd sizes)
@@ -1063,20 +1179,16 @@ class Engine:
         N, Hh, Ww, Cc = x.N, x.Hh, x.Ww, x.C
         OH, OW = (Hh + 2 * pad - k) // stride + 1, (Ww + 2 * pad - k) // stride + 1
         out = self._f(N, OH, OW, Cc)
-        idx = torch.empty((N, OH, OW, Cc), device=self.device, dtype=torch.int32) if self.record else None
+        idx = self._buf(N, OH, OW, Cc, dtype=torch.int32) if self.record else None
         H.call("adh_maxpool", x.t.data_ptr(), x.cs, N, Hh, Ww, Cc, k, stride, pad, out.data_ptr(), Cc, H.ptr(idx))
         o = Act(out, Cc)
         if self.record:
-            def bwd():
-                g = o.grad
-                o.grad = None
-                if g is None or not x.needs_grad:
-                    return
+            def bwd(g):
                 gx = self._f(N, Hh, Ww, Cc)
                 H.call("adh_maxpool_bwd", g.data_ptr(), g.stride(2), idx.data_ptr(), N, OH, OW, Cc, k, stride, pad, Hh, Ww,
                        gx.data_ptr(), Cc)
                 self.accum(x, gx)
-            self.tape.append(bwd)
+            self._on_grad(o, bwd, x)
         return o
 
     def bilinear(self, x: Act, OH: int, OW: int, align_corners: bool, out: Optional[torch.Tensor] = None) -> Act:
@@ -1087,16 +1199,12 @@ class Engine:
                out.stride(2))
         o = Act(out, Cc)
         if self.record:
-            def bwd():
-                g = o.grad
-                o.grad = None
-                if g is None or not x.needs_grad:
-                    return
+            def bwd(g):
                 gx = self._f(N, Hh, Ww, Cc)
                 H.call("adh_bilinear_bwd", g.data_ptr(), g.stride(2), N, Hh, Ww, Cc, OH, OW, int(align_corners),
                        gx.data_ptr(), Cc)
                 self.accum(x, gx)
-            self.tape.append(bwd)
+            self._on_grad(o, bwd, x)
         return o
 
     # ------------------------------------------------------------------ classifier helpers
@@ -1109,24 +1217,20 @@ class Engine:
         for c0 in range(0, Cc, 1024):      # the pooling kernel takes <= 1024 channels per launch (resnet50: 2048): channel slices of x
             cw = min(1024, Cc - c0)
             partial = self._f(N, nblk, 2, cw)
-            partial_idx = torch.empty((N, nblk, cw), device=self.device, dtype=torch.int32)
+            partial_idx = self._buf(N, nblk, cw, dtype=torch.int32)
             pooled = self._f(N, 2, cw)
-            amax_idx = torch.empty((N, cw), device=self.device, dtype=torch.int32)
+            amax_idx = self._buf(N, cw, dtype=torch.int32)
             H.call("adh_cbam_pool", x.t.data_ptr() + 4 * c0, x.cs, N, HW, cw, partial.data_ptr(), partial_idx.data_ptr(), nblk,
                    pooled.data_ptr(), amax_idx.data_ptr())
             means[:, c0:c0 + cw] = pooled[:, 0, :]
         o = Act(means.view(N, 1, 1, Cc), Cc)   # [N,1,1,C] means
         if self.record:
-            def bwd():
-                g = o.grad
-                o.grad = None
-                if g is None or not x.needs_grad:
-                    return
+            def bwd(g):
                 gc = g.reshape(N, -1)[:, :Cc].contiguous()
                 gx = self._f(N, Hh, Ww, Cc)
                 H.call("adh_global_avgpool_bwd", gc.data_ptr(), N, HW, Cc, gx.data_ptr(), Cc)
                 self.accum(x, gx)
-            self.tape.append(bwd)
+            self._on_grad(o, bwd, x)
         return o
 
     def avgpool(self, x: Act, k: int) -> Act:
@@ -1137,17 +1241,13 @@ class Engine:
         H.call("adh_avgpool", x.t.data_ptr(), x.cs, N, Hh, Ww, Cc, k, out.data_ptr(), Cc)
         o = Act(out, Cc)
         if self.record:
-            def bwd():
-                g = o.grad
-                o.grad = None
-                if g is None or not x.needs_grad:
-                    return
+            def bwd(g):
                 C4 = _round_up(Cc, 4)
                 gx = self._f(N, Hh, Ww, C4)
                 H.call("adh_avgpool2_bwd", g.data_ptr(), g.stride(2), N, Hh, Ww, C4, gx.data_ptr(), C4, 0,
                        work=4.0 * (N * Hh * Ww + g.shape[0] * g.shape[1] * g.shape[2]) * Cc)   # bytes: read g, write gx
                 self.accum(x, gx)
-            self.tape.append(bwd)
+            self._on_grad(o, bwd, x)
         return o
 
     def bn_relu_eval(self, x: Act, bn: BNState, out: Optional[torch.Tensor] = None) -> Act:
@@ -1156,8 +1256,7 @@ class Engine:
         assert not self.record, "bn_relu_eval records no backward: use bn_relu_preact"
         N, Hh, Ww, Cc = x.N, x.Hh, x.Ww, x.C
         scale, shift = self._f(Cc), self._f(Cc)
-        H.call("adh_bn_fold_eval", Cc, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-               bn.running_var.data_ptr(), bn.eps, None, scale.data_ptr(), shift.data_ptr())
+        self._bn_fold_eval(bn, scale, shift)
         if out is None:
             out = self._f(N, Hh, Ww, Cc)
         H.call("adh_bn_apply", x.t.data_ptr(), x.cs, scale.data_ptr(), shift.data_ptr(), None, 0, H.ACT_RELU,
@@ -1207,8 +1306,8 @@ class Engine:
         (the no-grad eval pass is bn_relu_eval).  training: the batch statistics of `moments`, folded with this layer's gamma /
         beta (adh_bn_fold_moments, with nn.BatchNorm2d's running-buffer update); else the running statistics (frozen BN with
         trainable gamma / beta).  The output is materialised (the 1x1 convolution's weight gradient reads it).  Backward:
-        adh_bn_bwd_reduce of (dA, x) with the ReLU mask recomputed from x, adh_bn_bwd_finalize, then adh_bn_preact_bwd_accum
-        adds d(loss)/dx into sink['g'][..., :C] at the buffer's channel stride."""
+        the sums of (dA, x) with the ReLU mask recomputed from x and their finalize (_bn_train_coef / _bn_frozen_param_grads),
+        then adh_bn_preact_bwd_accum adds d(loss)/dx into sink['g'][..., :C] at the buffer's channel stride."""
         N, Hh, Ww, Cc = x.N, x.Hh, x.Ww, x.C
         P = x.pixels
         assert Cc % 4 == 0 and x.cs % 4 == 0, "pre-activation BatchNorm needs whole channel quads"
@@ -1222,8 +1321,7 @@ class Engine:
                    bn.bias.data_ptr(), bn.eps, bn.momentum, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
                    ss[0].data_ptr(), ss[1].data_ptr(), mean.data_ptr(), invstd.data_ptr(), H.ptr(bn.num_batches_tracked))
         else:
-            H.call("adh_bn_fold_eval", Cc, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                   bn.running_var.data_ptr(), bn.eps, None, ss[0].data_ptr(), ss[1].data_ptr())
+            self._bn_fold_eval(bn, ss[0], ss[1])
         out = self._f(N, Hh, Ww, Cc)
         H.call("adh_bn_apply", x.t.data_ptr(), x.cs, ss[0].data_ptr(), ss[1].data_ptr(), None, 0, H.ACT_RELU, out.data_ptr(), Cc,
                P, Cc, None, work=8.0 * P * Cc)                                   # bytes: read x, write out
@@ -1235,11 +1333,7 @@ class Engine:
         bn_grads = training or bn.weight.requires_grad or bn.bias.requires_grad
         self.use_param(bn.weight if bn_grads else None, bn.bias if bn_grads else None)
 
-        def bwd():
-            g = o.grad
-            o.grad = None
-            if g is None:
-                return
+        def bwd(g):
             dbuf, acc = sink["g"], 1
             if dbuf is None:   # the first writer of the block's gradient: store, and zero what it does not cover
                 dbuf, acc = self._f(N, Hh, Ww, sink["C"]), 0
@@ -1247,69 +1341,25 @@ class Engine:
                     dbuf[..., Cc:].zero_()
                 sink["g"] = dbuf
             coef = ss       # frozen statistics: dx = scale * m * dA (only row 0 is read)
-            if bn_grads:
-                if training:
-                    mu, inv = mean, invstd
-                else:       # xhat from the running statistics: adh_bn_fold_eval without gamma / beta gives invstd as its scale
-                    mu, inv, junk = bn.running_mean.contiguous(), self._f(Cc), self._f(Cc)
-                    H.call("adh_bn_fold_eval", Cc, None, None, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.eps,
-                           None, inv.data_ptr(), junk.data_ptr())
-                nblk = H.value("adh_bn_bwd_num_blocks", P, Cc)
-                partial = self._f(nblk, 2, Cc)
-                H.call("adh_bn_bwd_reduce", g.data_ptr(), g.stride(2), None, 0, H.ACT_RELU, x.t.data_ptr(), x.cs, mu.data_ptr(),
-                       inv.data_ptr(), partial.data_ptr(), P, Cc, ss.data_ptr(), None, work=8.0 * P * Cc)   # bytes: dA, x
-                dgamma, dbeta = self.grad_buffer(bn.weight), self.grad_buffer(bn.bias)
-                fin = self._f(3, Cc)
-                H.call("adh_bn_bwd_finalize", partial.data_ptr(), nblk, Cc, float(P), bn.weight.data_ptr() if training else None,
-                       inv.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), 0, fin.data_ptr())
-                if training:
-                    coef = fin
+            if training:
+                coef, dgamma, dbeta = self._bn_train_coef(bn, g, None, H.ACT_RELU, x.t, mean, invstd, ss, None, P, Cc)
+            elif bn_grads:
+                dgamma, dbeta = self._bn_frozen_param_grads(bn, g, None, H.ACT_RELU, x.t, bn.running_mean.contiguous(),
+                                                            self._f(Cc), P, Cc, ss, work=8.0 * P * Cc)   # bytes: dA, x
             H.call("adh_bn_preact_bwd_accum", g.data_ptr(), g.stride(2), x.t.data_ptr(), x.cs, ss.data_ptr(), H.ptr(mean),
                    H.ptr(invstd), coef.data_ptr(), int(training), dbuf.data_ptr(), dbuf.stride(2), P, Cc, acc,
                    work=4.0 * P * Cc * (4 if acc else 3))                        # bytes: dA, x (, dbuf), write dbuf
             if bn_grads:
                 self.add_param_grad(bn.weight, dgamma)
                 self.add_param_grad(bn.bias, dbeta)
-        self.tape.append(bwd)
+        self._on_grad(o, bwd)
         return o
 
     # ------------------------------------------------------------------ MobileNetV2 / V3 (torchvision) building blocks
-    def _bn_act_eval_backward(self, g: torch.Tensor, y: torch.Tensor, ss: torch.Tensor, bn: BNState, act_code: int,
-                              g_y: torch.Tensor, P: int, Cc: int, out: Optional[Act] = None,
-                              g_res: Optional[torch.Tensor] = None):
-        """Backward of out = act(y * scale + shift (+ residual)) with frozen BatchNorm statistics (scale / shift =
-        ss[0] / ss[1], folded from the running estimates): g_y = scale * act'(z) * g, g_res = act'(z) * g, and d-gamma /
-        d-beta when the BN parameters train.  `out`: the block output of a residual tail (NONE / RELU), whose ReLU mask is
-        read from it."""
-        C4 = _round_up(Cc, 4)
-        coef = self._f(3, C4, zero=True)
-        coef[0].copy_(ss[0])
-        mask_ss = ss.data_ptr() if (act_code != H.ACT_NONE and out is None) else None
-        o_ptr, o_cs = (out.t.data_ptr(), out.cs) if out is not None else (None, 0)
-        H.call("adh_bn_bwd_apply", g.data_ptr(), g.stride(2), o_ptr, o_cs, act_code, y.data_ptr(), y.stride(2), None, None,
-               coef.data_ptr(), 0, g_y.data_ptr(), g_y.stride(2), H.ptr(g_res), g_res.stride(2) if g_res is not None else 0,
-               P, C4, mask_ss, None)
-        if not (bn.weight.requires_grad or bn.bias.requires_grad):
-            return
-        # xhat = (y - running_mean) * invstd; adh_bn_fold_eval without gamma / beta gives invstd as its scale
-        mean4, inv4, junk = self._f(C4, zero=True), self._f(C4, zero=True), self._f(C4)
-        mean4[:Cc].copy_(bn.running_mean)
-        H.call("adh_bn_fold_eval", Cc, None, None, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.eps, None,
-               inv4.data_ptr(), junk.data_ptr())
-        nblk = H.value("adh_bn_bwd_num_blocks", P, C4)
-        partial = self._f(nblk, 2, C4)
-        H.call("adh_bn_bwd_reduce", g.data_ptr(), g.stride(2), o_ptr, o_cs, act_code, y.data_ptr(), y.stride(2), mean4.data_ptr(),
-               inv4.data_ptr(), partial.data_ptr(), P, C4, mask_ss, None)
-        dgamma, dbeta, scratch = self._f(C4), self._f(C4), self._f(3, C4)
-        H.call("adh_bn_bwd_finalize", partial.data_ptr(), nblk, C4, float(P), None, inv4.data_ptr(), dgamma.data_ptr(),
-               dbeta.data_ptr(), 0, scratch.data_ptr())
-        self.add_param_grad(bn.weight, dgamma[:Cc])
-        self.add_param_grad(bn.bias, dbeta[:Cc])
-
     def dwconv(self, x: Act, w: torch.Tensor, bn: BNState, *, k: int, stride: int, act: int, training: bool) -> Act:
         """Depthwise Conv2d(C, C, k, stride, (k-1)//2, groups=C, bias=False) -> BatchNorm2d -> act: torchvision's
         Conv2dNormActivation with groups == C (MobileNetV2 / V3).  Train mode: raw y + per-block statistics from the
-        depthwise kernel, adh_bn_finalize, adh_bn_apply.  Eval mode: the folded BN and the activation in the kernel's
+        depthwise kernel, the train-mode fold, adh_bn_apply.  Eval mode: the folded BN and the activation in the kernel's
         epilogue (with gradients: the raw y is kept and adh_bn_apply runs as a pass of its own)."""
         N, Hh, Ww, Cc = x.N, x.Hh, x.Ww, x.C
         assert tuple(w.shape) == (Cc, 1, k, k) and Cc % 4 == 0, "depthwise weight must be [C,1,k,k], C % 4 == 0"
@@ -1322,40 +1372,26 @@ class Engine:
         # algorithmic bytes of one depthwise launch: read x once, write y once
         dw_bytes = 4.0 * (N * Hh * Ww + P) * Cc
         ss = self._f(2, Cc)
-        if training:
+        y = mean = invstd = None
+        if training or self.record:     # the raw y is kept for the backward pass; the BatchNorm and the activation follow
             y = self._f(N, OH, OW, Cc)
+        if training:
             nblk = H.value("adh_dwconv_num_blocks", P, Cc)
             stats = self._f(nblk, 2, Cc)
             H.call("adh_dwconv_fwd", x.t.data_ptr(), x.cs, N, Hh, Ww, Cc, k, stride, wp.data_ptr(), y.data_ptr(), Cc, OH, OW,
                    None, None, H.ACT_NONE, stats.data_ptr(), work=dw_bytes)
-            mean, invstd = self._f(Cc), self._f(Cc)
-            if SYNC_BN is not None:
-                sums = torch.empty(2 * Cc + 1, device=self.device, dtype=torch.float64)
-                H.call("adh_bn_partial_sums", stats.data_ptr(), nblk, Cc, Cc, float(P), sums.data_ptr())
-                SYNC_BN(sums)
-                H.call("adh_bn_finalize_sums", sums.data_ptr(), Cc, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.eps,
-                       bn.momentum, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), ss[0].data_ptr(), ss[1].data_ptr(),
-                       mean.data_ptr(), invstd.data_ptr(), H.ptr(bn.num_batches_tracked))
-            else:
-                H.call("adh_bn_finalize", stats.data_ptr(), nblk, Cc, Cc, float(P), bn.weight.data_ptr(), bn.bias.data_ptr(),
-                       bn.eps, bn.momentum, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), ss[0].data_ptr(),
-                       ss[1].data_ptr(), mean.data_ptr(), invstd.data_ptr(), H.ptr(bn.num_batches_tracked))
-            H.call("adh_bn_apply", y.data_ptr(), Cc, ss[0].data_ptr(), ss[1].data_ptr(), None, 0, act, out.data_ptr(), ac, P, Cc,
-                   None, work=8.0 * P * Cc)
-            saved = ("train", y, mean, invstd)
+            mean, invstd = self._bn_train_fold(bn, stats, nblk, Cc, P, ss)
         else:
-            H.call("adh_bn_fold_eval", Cc, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                   bn.running_var.data_ptr(), bn.eps, None, ss[0].data_ptr(), ss[1].data_ptr())
-            if self.record:
-                y = self._f(N, OH, OW, Cc)
+            self._bn_fold_eval(bn, ss[0], ss[1])
+            if y is not None:
                 H.call("adh_dwconv_fwd", x.t.data_ptr(), x.cs, N, Hh, Ww, Cc, k, stride, wp.data_ptr(), y.data_ptr(), Cc, OH,
                        OW, None, None, H.ACT_NONE, None, work=dw_bytes)
-                H.call("adh_bn_apply", y.data_ptr(), Cc, ss[0].data_ptr(), ss[1].data_ptr(), None, 0, act, out.data_ptr(), ac,
-                       P, Cc, None, work=8.0 * P * Cc)
-                saved = ("eval", y)
             else:
                 H.call("adh_dwconv_fwd", x.t.data_ptr(), x.cs, N, Hh, Ww, Cc, k, stride, wp.data_ptr(), out.data_ptr(), ac,
                        OH, OW, ss[0].data_ptr(), ss[1].data_ptr(), act, None, work=dw_bytes)
+        if y is not None:
+            H.call("adh_bn_apply", y.data_ptr(), Cc, ss[0].data_ptr(), ss[1].data_ptr(), None, 0, act, out.data_ptr(), ac, P, Cc,
+                   None, work=8.0 * P * Cc)
         o = Act(out, Cc)
         if RELU_CAPTURE is not None and act in (H.ACT_RELU, H.ACT_RELU6):
             RELU_CAPTURE[id(w)] = out
@@ -1365,37 +1401,11 @@ class Engine:
             bn_grads = training or bn.weight.requires_grad or bn.bias.requires_grad
             self.use_param(w if w_grad else None, bn.weight if bn_grads else None, bn.bias if bn_grads else None)
 
-            def bwd():
-                g = o.grad
-                o.grad = None
-                if g is None:
-                    return
+            def bwd(g):
                 g_y = self._f(N, OH, OW, Cc)
-                y = saved[1]
-                if saved[0] == "train":
-                    _, _, mean, invstd = saved
-                    mask_ss = ss.data_ptr() if act != H.ACT_NONE else None
-                    nblk_b = H.value("adh_bn_bwd_num_blocks", P, Cc)
-                    partial = self._f(nblk_b, 2, Cc)
-                    H.call("adh_bn_bwd_reduce", g.data_ptr(), g.stride(2), None, 0, act, y.data_ptr(), Cc, mean.data_ptr(),
-                           invstd.data_ptr(), partial.data_ptr(), P, Cc, mask_ss, None, work=8.0 * P * Cc)
-                    dgamma, dbeta = self.grad_buffer(bn.weight), self.grad_buffer(bn.bias)
-                    coef = self._f(3, Cc)
-                    if SYNC_BN is not None:
-                        loc = torch.empty(2 * Cc + 1, device=self.device, dtype=torch.float64)
-                        H.call("adh_bn_partial_sums", partial.data_ptr(), nblk_b, Cc, Cc, float(P), loc.data_ptr())
-                        glob = loc.clone()
-                        SYNC_BN(glob)
-                        H.call("adh_bn_bwd_finalize_sums", loc.data_ptr(), glob.data_ptr(), Cc, bn.weight.data_ptr(),
-                               invstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), 0, coef.data_ptr())
-                    else:
-                        H.call("adh_bn_bwd_finalize", partial.data_ptr(), nblk_b, Cc, float(P), bn.weight.data_ptr(),
-                               invstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), 0, coef.data_ptr())
-                    H.call("adh_bn_bwd_apply", g.data_ptr(), g.stride(2), None, 0, act, y.data_ptr(), Cc, mean.data_ptr(),
-                           invstd.data_ptr(), coef.data_ptr(), 1, g_y.data_ptr(), Cc, None, 0, P, Cc, mask_ss, None,
-                           work=12.0 * P * Cc)
-                    self.add_param_grad(bn.weight, dgamma)
-                    self.add_param_grad(bn.bias, dbeta)
+                if training:
+                    self._bn_train_backward(bn, g, None, act, y, mean, invstd, ss if act != H.ACT_NONE else None, None, g_y,
+                                            None, P, Cc)
                 else:
                     self._bn_act_eval_backward(g, y, ss, bn, act, g_y, P, Cc)
                 if w_grad:
@@ -1415,33 +1425,25 @@ class Engine:
                         x.bn_partial = None
                         H.call("adh_dwconv_dgrad", g_y.data_ptr(), Cc, N, OH, OW, Cc, k, stride, wp.data_ptr(),
                                x.grad.data_ptr(), x.grad.stride(2), Hh, Ww, 1, work=dw_bytes)
-            self.tape.append(bwd)
+            self._on_grad(o, bwd)
         return o
 
     def activation(self, x: Act, act: int) -> Act:
         """act(x) as a pass of its own (the squeeze-excitation gate, Hardsigmoid): adh_bn_apply with scale 1, shift 0."""
         N, Hh, Ww, Cc = x.N, x.Hh, x.Ww, x.C
         C4 = _round_up(Cc, 4)
-        ss = self._f(2, C4, zero=True)
-        ss[0].fill_(1.0)
+        ss = self._identity_coef(2, C4)
         out = self._f(N, Hh, Ww, C4)
         H.call("adh_bn_apply", x.t.data_ptr(), x.cs, ss[0].data_ptr(), ss[1].data_ptr(), None, 0, act, out.data_ptr(), C4,
                x.pixels, C4, None)
         o = Act(out, Cc)
         if self.record:
-            def bwd():
-                g = o.grad
-                o.grad = None
-                if g is None or not x.needs_grad:
-                    return
+            def bwd(g):
                 gx = self._f(N, Hh, Ww, C4)
-                coef = self._f(3, C4, zero=True)
-                coef[0].fill_(1.0)
-                H.call("adh_bn_bwd_apply", g.data_ptr(), g.stride(2), None, 0, act, x.t.data_ptr(), x.cs, None, None,
-                       coef.data_ptr(), 0, gx.data_ptr(), C4, None, 0, x.pixels, C4,
-                       ss.data_ptr() if act != H.ACT_NONE else None, None)
+                self._bn_bwd_apply(g, None, act, x.t, None, None, self._identity_coef(3, C4), 0, gx, None, x.pixels, C4,
+                                   ss if act != H.ACT_NONE else None)
                 self.accum(x, gx)
-            self.tape.append(bwd)
+            self._on_grad(o, bwd, x)
         return o
 
     def channel_scale(self, x: Act, s: Act) -> Act:
@@ -1455,11 +1457,7 @@ class Engine:
                work=8.0 * N * HW * Cc)
         o = Act(out, Cc)
         if self.record:
-            def bwd():
-                g = o.grad
-                o.grad = None
-                if g is None:
-                    return
+            def bwd(g):
                 nblk = H.value("adh_channel_scale_bwd_num_blocks", HW, Cc)
                 partial = self._f(N * nblk * Cc)
                 gs = self._f(N, 1, 1, Cc)
@@ -1469,7 +1467,7 @@ class Engine:
                 self.accum(s, gs)
                 if gx is not None:
                     self.accum(x, gx)
-            self.tape.append(bwd)
+            self._on_grad(o, bwd)
         return o
 
     def mul_mask(self, x: Act, mask: torch.Tensor) -> Act:
@@ -1479,15 +1477,11 @@ class Engine:
         H.call("adh_mul", out.data_ptr(), x.t.data_ptr(), mask.data_ptr(), out.numel())
         o = Act(out, x.C)
         if self.record:
-            def bwd():
-                g = o.grad
-                o.grad = None
-                if g is None or not x.needs_grad:
-                    return
+            def bwd(g):
                 gx = self._f(*x.t.shape)
                 H.call("adh_mul", gx.data_ptr(), g.contiguous().data_ptr(), mask.data_ptr(), gx.numel())
                 self.accum(x, gx)
-            self.tape.append(bwd)
+            self._on_grad(o, bwd, x)
         return o
 
     # ------------------------------------------------------------------ branch heads
@@ -1495,7 +1489,7 @@ class Engine:
         """Final blend producing the NCHW output (low_intensity.py:41-45,116; medium_intensity.py:117;
         high_intensity.py:135-138,214)."""
         N, _, Hh, Ww = x_img.shape
-        out = torch.empty_like(x_img)
+        out = self._buf(*x_img.shape, dtype=x_img.dtype)
         H.call("adh_head_blend", mode, x_img.data_ptr(), r.t.data_ptr(), r.cs, H.ptr(gd.t if gd else None),
                gd.cs if gd else 0, H.ptr(alpha), N, Hh, Ww, out.data_ptr())
         holder = {"g": None}

@@ -1,4 +1,4 @@
-"""Launch trace of the engine's convolution section, taken on the CPU.
+"""Launch trace of the engine, taken on the CPU: the convolution section (CASES) and every other op (OPS_CASES).
 
 `_hip.call` is replaced by a recorder that launches nothing; the `adh_*_supported` / `*_groups` / `*_num_blocks` queries
 (`_hip.value`) are host functions and stay real.  One record per `H.call`:
@@ -10,14 +10,24 @@ the case's trace, byte offset, buffer size in bytes]}, a ConvDesc as {"d": [its 
 them as {"da": [...]} and a WLayout as {"l": [its nine fields]}.  Buffer sizes pin slab and pack sizes, offsets pin the
 statistics-row offsets.  A pointer that falls in no registered buffer raises.
 
-tests/golden/launch_trace.json holds the trace of every case in CASES.  It is regenerated with
+The OPS_CASES go through the engine's public methods and backward().  Their recorder also
+  - registers every buffer the engine allocates (Engine._f and Engine._buf) and fills the ones not asked for with zero=True
+    with NaN (integer buffers: all bits set), so a host-side write that goes missing shows;
+  - appends ["SYNC_BN", pointer] where the engine calls SYNC_BN, when a case sets that switch to "trace";
+  - gives every record a sixth item: for each non-null pointer of the record, in order, the first 12 hex digits of the SHA-1
+    of its buffer's bytes at the time of the call (None for a buffer above 64 KiB).  That pins what torch writes on the host
+    and no launch shows (zero=True, coef[0].copy_(...), dbuf[..., C:].zero_(), ...).
 
-    python -m tests._launch_trace --regen
+tests/golden/launch_trace.json holds the trace of every case in CASES, tests/golden/launch_trace_ops.json of every case in
+OPS_CASES.  They are regenerated with
+
+    python -m tests._launch_trace --regen          (--regen-ops for the second)
 
 from the repository root, with the library built -- and only from a version of engine.py whose launches are known to be
-right: the golden is what a change to the selection / launch code is compared against.
+right: a golden is what a change to the selection / launch code is compared against.
 """
 import ctypes as C
+import hashlib
 import json
 import math
 import os
@@ -35,6 +45,8 @@ from adam_dehaze_amd import _hip as H              # noqa: E402
 from adam_dehaze_amd.engine import Act, BNState, Engine   # noqa: E402
 
 GOLDEN_PATH = os.path.join(ROOT, "tests", "golden", "launch_trace.json")
+OPS_GOLDEN_PATH = os.path.join(ROOT, "tests", "golden", "launch_trace_ops.json")
+DIGEST_MAX_BYTES = 64 << 10
 DESC_FIELDS = [f[0] for f in H.ConvDesc._fields_]
 DESC_POINTERS = {f[0] for f in H.ConvDesc._fields_ if f[1] is H.vp}
 
@@ -55,7 +67,9 @@ def _r(a, b):
 class Trace:
     """Recorder + buffer registry of one case."""
 
-    def __init__(self):
+    def __init__(self, digests=False):
+        self.digests = digests  # OPS_CASES: records carry the digests of their pointers' buffers
+        self._dig = []
         self.records = []
         self.keep = []          # every registered tensor stays alive for the case: the allocator must not reuse addresses
         self.spans = []         # (start, size in bytes)
@@ -72,6 +86,21 @@ class Trace:
     def new(self, *shape, dtype=torch.float32):
         return self.reg(torch.zeros(shape, dtype=dtype))
 
+    def ramp(self, lo, hi, *shape):
+        """a non-constant input: lo .. hi over the elements in storage order"""
+        n = math.prod(shape)
+        return self.reg(torch.linspace(lo, hi, n, dtype=torch.float32).reshape(shape).clone())
+
+    def alloc(self, t, zero):
+        """a buffer the engine allocated: registered, and poisoned unless the engine asked for zeros"""
+        if not zero:
+            t.fill_(float("nan") if t.is_floating_point() else -1 if t.dtype.is_signed else 255)
+        return self.reg(t)
+
+    def sync_bn(self, sums):
+        self.records.append(["SYNC_BN", self._ptr(sums.data_ptr())])
+        self._dig = []
+
     def engine(self, record=True):
         self.eng = Engine(torch.device("cpu"), record=record)
         return self.eng
@@ -82,6 +111,9 @@ class Trace:
         for start, size in self.spans:
             if start <= p < start + size:
                 n = self.numbers.setdefault(start, len(self.numbers))
+                if self.digests:
+                    self._dig.append(hashlib.sha1(C.string_at(start, size)).hexdigest()[:12] if size <= DIGEST_MAX_BYTES
+                                     else None)
                 return {"p": [n, p - start, size]}
         raise AssertionError(f"pointer {p:#x} falls in no registered buffer")
 
@@ -105,8 +137,10 @@ class Trace:
     def call(self, name, *args, work=0.0, work_exec=None, family=None):
         argtypes = H._SIGNATURES[name][1:]          # [0] is the stream
         assert len(args) == len(argtypes), (name, len(args), len(argtypes))
-        self.records.append([name, family, float(work), None if work_exec is None else float(work_exec),
-                             [self._arg(a, t) for a, t in zip(args, argtypes)]])
+        self._dig = []
+        rec = [name, family, float(work), None if work_exec is None else float(work_exec),
+               [self._arg(a, t) for a, t in zip(args, argtypes)]]
+        self.records.append(rec + [self._dig] if self.digests else rec)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -303,22 +337,252 @@ CASES = {
 }
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# every other op: through the public methods and backward(), at the smallest shapes that reach every branch
+# ---------------------------------------------------------------------------------------------------------------------
+def _bn_ramp(T, Cc, trainable=True):
+    """non-constant gamma / beta / running statistics: the digests of the buffers they are copied into depend on them"""
+    return BNState(T.ramp(0.5, 1.5, Cc).requires_grad_(trainable), T.ramp(-0.2, 0.3, Cc).requires_grad_(trainable),
+                   T.ramp(-1.0, 1.0, Cc), T.ramp(0.5, 2.0, Cc), T.new(1, dtype=torch.int64))
+
+
+def _backward(T, o):
+    o.grad = T.ramp(-1.0, 1.0, *o.t.shape)
+    T.eng.backward()
+
+
+def dwconv(k, s, act, mode, second_consumer=False):
+    """mode: train | eval_grad (trainable gamma / beta) | eval_frozen | eval_norecord"""
+    def run(T):
+        Cc = 24
+        eng = T.engine(record=mode != "eval_norecord")
+        x = Act(T.ramp(-1.0, 1.0, 2, 9, 11, Cc))
+        w = T.new(Cc, 1, k, k).requires_grad_(True)
+        o = eng.dwconv(x, w, _bn_ramp(T, Cc, trainable=mode != "eval_frozen"), k=k, stride=s, act=act,
+                       training=mode == "train")
+        if eng.record:
+            if second_consumer:
+                x.grad = T.new(*x.t.shape)
+            _backward(T, o)
+            assert x.grad is not None
+    return run
+
+
+def conv_op(k, Cin, Cout, N, Hh, Ww, *, bn=None, training=False, bias=False, residual=False, act=None, relu=True,
+            stats=False, twice=False):
+    """Engine.conv and its backward; bn: None | "frozen" | "trainable"; twice: the same weight and bias in a second layer"""
+    def run(T):
+        eng = T.engine(record=True)
+        x = Act(T.ramp(-1.0, 1.0, N, Hh, Ww, _r(Cin, 8)), Cin)
+        w = _weight(T, "conv", k, Cin, Cout)
+        b = T.ramp(-0.5, 0.5, Cout).requires_grad_(True) if bias else None
+        res = Act(T.ramp(-2.0, 2.0, N, Hh, Ww, _r(Cout, 8)), Cout) if residual else None
+        got = [] if stats else None
+        out = T.new(N, Hh, Ww, 2 * _r(Cout, 8))[..., _r(Cout, 8):] if stats else None   # a slice of a wider buffer
+        o = x
+        for _ in range(2 if twice else 1):
+            o = eng.conv(o, w, b, None if bn is None else _bn_ramp(T, Cout, trainable=bn == "trainable"), k=k, stride=1,
+                         pad=(k - 1) // 2, relu=relu, act=act, residual=res, training=training, stats=got, out=out)
+        assert not stats or len(got) == 1
+        _backward(T, o)
+        assert x.grad is not None and (res is None or res.grad is not None)
+    return run
+
+
+def sync_chain(T):
+    """two train-mode ConvBlocks under SYNC_BN"""
+    eng = T.engine(record=True)
+    a = x0 = Act(T.ramp(-1.0, 1.0, 1, 16, 32, 32))
+    for _ in range(2):
+        a = eng.conv(a, _weight(T, "conv", 3, 32, 32), None, _bn_ramp(T, 32), training=True)
+    _backward(T, a)
+    assert x0.grad is not None
+
+
+def preact(training):
+    """two pre-activation BatchNorms over the first 16 channels of a 32-channel block buffer: in backward() the second is the
+    first writer of the block gradient (and zeroes channels 16 .. 31), the first accumulates"""
+    def run(T):
+        eng = T.engine(record=True)
+        buf = T.ramp(-1.0, 1.0, 2, 6, 7, 32)
+        sink = {"g": None, "C": 32}
+        moments = (T.ramp(-1.0, 1.0, 32).double(), T.ramp(0.5, 2.0, 32).double()) if training else None
+        for m in moments or ():
+            T.reg(m)
+        outs = [eng.bn_relu_preact(Act(buf[..., :16], 16), _bn_ramp(T, 16), training, moments, sink) for _ in range(2)]
+        for o in outs:
+            o.grad = T.ramp(-1.0, 1.0, *o.t.shape)
+        eng.backward()
+        assert sink["g"] is not None
+    return run
+
+
+def bn_relu_eval(T):
+    eng = T.engine(record=False)
+    eng.bn_relu_eval(Act(T.ramp(-1.0, 1.0, 2, 6, 7, 32)[..., :16], 16), _bn_ramp(T, 16))
+
+
+def dense_block(T):
+    """one DenseNet layer the way classifier.py drives it: dense_input, dense_moments without and with a conv epilogue's
+    partials, dense_output, and a closing BatchNorm over the whole buffer as the first writer of the block gradient"""
+    eng = T.engine(record=True)
+    h = Act(T.ramp(-1.0, 1.0, 2, 6, 7, 16))
+    buf = eng._f(2, 6, 7, 32)
+    sink = {"g": None, "C": 32}
+    eng.dense_input(h, buf, sink)
+    moments = (T.new(32, dtype=torch.float64), T.new(32, dtype=torch.float64))
+    eng.dense_moments(Act(buf[..., :16], 16), moments, 0)
+    a = eng.bn_relu_preact(Act(buf[..., :16], 16), _bn_ramp(T, 16), True, moments, sink)
+    b = eng.conv(a, _weight(T, "conv", 1, 16, 16), None, _bn_ramp(T, 16), k=1, pad=0, training=True)
+    stats = []
+    o = eng.conv(b, _weight(T, "conv", 3, 16, 16), None, None, relu=False, out=buf[..., 16:], stats=stats)
+    eng.dense_output(o, sink, 16)
+    eng.dense_moments(o, moments, 16, partials=stats[0])
+    _backward(T, eng.bn_relu_preact(Act(buf, 32), _bn_ramp(T, 32), True, moments, sink))
+    assert h.grad is not None
+
+
+def attention(T):
+    eng = T.engine(record=True)
+    x = Act(T.ramp(-1.0, 1.0, 2, 9, 11, 16))
+    w1, w2, wsp = (T.new(*shape).requires_grad_(True) for shape in ((2, 16), (16, 2), (1, 2, 7, 7)))
+    _backward(T, eng.attention(x, w1, w2, wsp))
+    assert x.grad is not None
+
+
+def unary(op, shape, *args):
+    """x -> Engine.<op>(x, *args) and its backward"""
+    def run(T):
+        eng = T.engine(record=True)
+        x = Act(T.ramp(-1.0, 1.0, *shape))
+        _backward(T, getattr(eng, op)(x, *args))
+        assert x.grad is not None
+    return run
+
+
+def concat(T):
+    eng = T.engine(record=True)
+    buf, views = eng.concat_buffer(2, 3, 5, (8, 16))
+    parts = [Act(v) for v in views]
+    parts[0].grad = T.new(2, 3, 5, 8)       # the first part already holds a gradient: accum adds into it
+    _backward(T, eng.concat(buf, parts))
+    assert parts[1].grad is not None
+
+
+def activation(T):
+    eng = T.engine(record=True)
+    x = Act(T.ramp(-4.0, 4.0, 2, 3, 5, 8), 6)
+    _backward(T, eng.activation(x, H.ACT_HARDSIGMOID))
+    assert x.grad is not None
+
+
+def channel_scale(T):
+    eng = T.engine(record=True)
+    x, s = Act(T.ramp(-1.0, 1.0, 2, 3, 5, 8)), Act(T.ramp(0.0, 1.0, 2, 1, 1, 8))
+    _backward(T, eng.channel_scale(x, s))
+    assert x.grad is not None and s.grad is not None
+
+
+def mul_mask(T):
+    eng = T.engine(record=True)
+    x = Act(T.ramp(-1.0, 1.0, 2, 3, 5, 8))
+    _backward(T, eng.mul_mask(x, T.ramp(0.0, 2.0, 2, 3, 5, 8)))
+    assert x.grad is not None
+
+
+def head_blend(mode):
+    def run(T):
+        eng = T.engine(record=True)
+        x_img = T.ramp(0.0, 1.0, 1, 3, 8, 8)
+        r = Act(T.ramp(-1.0, 1.0, 1, 8, 8, 8), 3)
+        gd = Act(T.ramp(0.0, 1.0, 1, 8, 8, 4), 1) if mode in (2, 4) else None       # BLEND_GUIDED, BLEND_DUAL
+        alpha = T.ramp(0.5, 0.5, 1).requires_grad_(True) if mode == 0 else None      # BLEND_LIGHT
+        _, holder = eng.head_blend(mode, x_img, r, gd, alpha)
+        holder["g"] = T.ramp(-1.0, 1.0, 1, 3, 8, 8)
+        eng.backward()
+        assert r.grad is not None and (gd is None or gd.grad is not None)
+    return run
+
+
+def mse(T):
+    eng = T.engine(record=True)
+    a, b = Act(T.ramp(-1.0, 1.0, 2, 3, 5, 8)), Act(T.ramp(1.0, -1.0, 2, 3, 5, 8), needs_grad=False)
+    vals = []
+    eng.mse(a, b, 0.5, vals)
+    eng.upstream["g"] = T.ramp(1.0, 1.0, 1)
+    eng.backward()
+    assert len(vals) == 1 and a.grad is not None
+
+
+def images(T):
+    eng = T.engine(record=True)
+    x = T.ramp(0.0, 1.0, 1, 3, 8, 8)
+    eng.image_to_nhwc8(x)
+    holder = {}
+    _backward(T, eng.image_normalize_to_nhwc8(x, (0.485, 0.456, 0.406), (0.229, 0.224, 0.225), holder))
+    assert holder["gx"].shape == x.shape
+
+
+SYNC = dict(SYNC_BN="trace")
+DW = {"3s2_hswish": (3, 2, H.ACT_HARDSWISH), "5s1_none": (5, 1, H.ACT_NONE)}
+OPS_CASES = {
+    **{f"dwconv_{g}/{mode}": (dwconv(*a, mode), {}, {}) for g, a in DW.items()
+       for mode in ("train", "eval_grad", "eval_frozen", "eval_norecord")},
+    **{f"dwconv_{g}/train,sync_bn": (dwconv(*a, "train"), SYNC, {}) for g, a in DW.items()},
+    "dwconv_3s2_hswish/train,second_consumer": (dwconv(*DW["3s2_hswish"], "train", second_consumer=True), {}, {}),
+    "conv/eval,residual": (conv_op(3, 16, 16, 1, 8, 8, bn="frozen", residual=True), {}, {}),
+    "conv/eval_act,relu6": (conv_op(1, 16, 24, 1, 8, 8, bn="frozen", act=H.ACT_RELU6), {}, {}),
+    "conv/eval_act,trainable,residual": (conv_op(3, 16, 16, 1, 8, 8, bn="trainable", residual=True), {}, {}),
+    "conv/eval_act,trainable,bias": (conv_op(1, 16, 24, 1, 8, 8, bn="trainable", bias=True, act=H.ACT_HARDSWISH), {}, {}),
+    "conv/bias": (conv_op(3, 16, 16, 1, 8, 8, bias=True, relu=False), {}, {}),
+    "conv/bias,shared_weight": (conv_op(3, 16, 16, 1, 8, 8, bias=True, twice=True), {}, {}),
+    "conv/stats": (conv_op(3, 16, 16, 1, 8, 8, relu=False, stats=True), {}, {}),
+    "conv/train,sync_bn": (sync_chain, SYNC, {}),
+    "conv/train,cout_6": (conv_op(3, 16, 6, 1, 8, 8, bn="trainable", training=True, bias=True), {}, {}),
+    "conv/train,residual,relu_bits": (conv_op(3, 16, 16, 1, 8, 8, bn="trainable", training=True, residual=True),
+                                      dict(USE_RELU_BITS=True), {}),
+    "bn_relu_preact/train": (preact(True), {}, {}),
+    "bn_relu_preact/frozen,trainable": (preact(False), {}, {}),
+    "bn_relu_eval": (bn_relu_eval, {}, {}),
+    "dense_block": (dense_block, {}, {}),
+    "attention": (attention, {}, {}),
+    "maxpool_3_2_1": (unary("maxpool", (2, 9, 11, 8), 3, 2, 1), {}, {}),
+    "bilinear/align": (unary("bilinear", (2, 4, 6, 8), 7, 5, True), {}, {}),
+    "bilinear/no_align": (unary("bilinear", (2, 4, 6, 8), 7, 5, False), {}, {}),
+    "avgpool_2_odd": (unary("avgpool", (2, 9, 11, 8), 2), {}, {}),
+    "global_avgpool_1032": (unary("global_avgpool", (2, 3, 3, 1032)), {}, {}),
+    "concat": (concat, {}, {}),
+    "activation_hsigmoid_6": (activation, {}, {}),
+    "channel_scale": (channel_scale, {}, {}),
+    "mul_mask": (mul_mask, {}, {}),
+    **{f"head_blend/{m}": (head_blend(m), {}, {}) for m in range(5)},
+    "mse": (mse, {}, {}),
+    "images": (images, {}, {}),
+}
+
+
 def library_env_set():
     return [v for v in LIBRARY_ENV if os.environ.get(v) is not None]
 
 
 def run_case(name, mp):
-    """The trace of one case; `mp` is a pytest MonkeyPatch."""
-    runner, switches, env = CASES[name]
+    """The trace of one case of CASES or OPS_CASES; `mp` is a pytest MonkeyPatch."""
+    ops = name not in CASES
+    runner, switches, env = (OPS_CASES if ops else CASES)[name]
+    T = Trace(digests=ops)
     for k, v in {**DEFAULTS, **switches}.items():
-        mp.setattr(E, k, v)
+        mp.setattr(E, k, T.sync_bn if (k, v) == ("SYNC_BN", "trace") else v)
     mp.delenv("ADH_NSPLIT", raising=False)
     for k, v in env.items():
         mp.setenv(k, v)
-    T = Trace()
     mp.setattr(H, "call", T.call)
     real_f = Engine._f
-    mp.setattr(Engine, "_f", lambda self, *shape, zero=False: T.reg(real_f(self, *shape, zero=zero)))
+    if ops:
+        real_buf = Engine._buf
+        mp.setattr(Engine, "_f", lambda self, *shape, zero=False: T.alloc(real_f(self, *shape, zero=zero), zero))
+        mp.setattr(Engine, "_buf", lambda self, *shape, dtype: T.alloc(real_buf(self, *shape, dtype=dtype), False))
+    else:
+        mp.setattr(Engine, "_f", lambda self, *shape, zero=False: T.reg(real_f(self, *shape, zero=zero)))
     runner(T)
     return T.records
 
@@ -332,6 +596,10 @@ def differences(got, want, where=""):
         return out
     for i, (g, w) in enumerate(zip(got, want)):
         at = f"{where}[{i}] {w[0]}"
+        if "SYNC_BN" in (g[0], w[0]):
+            if g != w:
+                out.append(f"{at}: {g} != {w}")
+            continue
         if g[:2] != w[:2]:
             out.append(f"{at}: entry point / family {g[:2]} != {w[:2]}")
             continue
@@ -352,6 +620,8 @@ def differences(got, want, where=""):
                         out.append(f"{at}: argument {n} descriptor {m}: (got, golden) {bad}")
             else:
                 out.append(f"{at}: argument {n}: {a} != {b}")
+        if g[5:] != w[5:]:
+            out.append(f"{at}: buffer digests {g[5:]} != {w[5:]}")
     return out[:8]
 
 
@@ -359,24 +629,30 @@ def summary(records):
     return " ".join(r[0][4:] for r in records)
 
 
-def main(argv):
-    if library_env_set():
-        raise SystemExit(f"unset {library_env_set()} first")
-    if "--regen" not in argv:
-        for name in CASES:
-            with pytest.MonkeyPatch.context() as mp:
-                print(f"{name}: {summary(run_case(name, mp))}")
-        return
+def _write_golden(path, table):
     cases = {}
-    for name in CASES:
+    for name in table:
         with pytest.MonkeyPatch.context() as mp:
             cases[name] = run_case(name, mp)
-    with open(GOLDEN_PATH, "w") as f:
+    with open(path, "w") as f:
         f.write('{"conv_desc_fields": %s,\n "cases": {\n' % json.dumps(DESC_FIELDS))
         f.write(",\n".join('  %s: [\n%s]' % (json.dumps(n), ",\n".join("   " + json.dumps(r, separators=(",", ":")) for r in recs))
                            for n, recs in cases.items()))
         f.write("\n }}\n")
-    print(f"{GOLDEN_PATH}: {len(cases)} cases, {sum(len(r) for r in cases.values())} launches, {os.path.getsize(GOLDEN_PATH)} bytes")
+    print(f"{path}: {len(cases)} cases, {sum(len(r) for r in cases.values())} launches, {os.path.getsize(path)} bytes")
+
+
+def main(argv):
+    if library_env_set():
+        raise SystemExit(f"unset {library_env_set()} first")
+    if "--regen" in argv:
+        _write_golden(GOLDEN_PATH, CASES)
+    if "--regen-ops" in argv:
+        _write_golden(OPS_GOLDEN_PATH, OPS_CASES)
+    if "--regen" not in argv and "--regen-ops" not in argv:
+        for name in list(CASES) + list(OPS_CASES):
+            with pytest.MonkeyPatch.context() as mp:
+                print(f"{name}: {summary(run_case(name, mp))}")
 
 
 if __name__ == "__main__":

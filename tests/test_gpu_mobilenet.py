@@ -195,8 +195,7 @@ BN_KEY = {"mobilenet_v2": "backbone.features.3.conv.1.1", "mobilenet_v3_large": 
           "mobilenet_v3_small": "backbone.features.4.block.1.1"}
 
 
-@pytest.mark.parametrize("name", NAMES)
-def test_backbone_train_forward_backward_vs_restatement(name):
+def _check_train_forward_backward_vs_restatement(name):
     """Train-mode BN + cross-entropy backward against the float64 restatement, with the ReLU / ReLU6 derivative masks the
     kernels used replayed in the restatement (engine.RELU_CAPTURE): with only 24 .. 96 samples per BatchNorm channel in the
     last stages, a pre-activation that rounds to the other side of a kink in fp32 moves whole gradients by percents (fp32
@@ -240,6 +239,22 @@ def test_backbone_train_forward_backward_vs_restatement(name):
     errs = {k: rel_err(names[k].grad, sdr[k].grad) for k in GRAD_KEYS[name] + ("classifier.1.weight", "classifier.4.weight")}
     bad = {k: e for k, e in errs.items() if not e < 2e-2}
     assert not bad, (bad, errs)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_backbone_train_forward_backward_vs_restatement(name):
+    _check_train_forward_backward_vs_restatement(name)
+
+
+def test_v3_small_train_under_sync_bn_in_a_world_of_one(monkeypatch):
+    """The synchronised-BatchNorm sequences of the dense and the depthwise layers (local sums in fp64 -> all-reduce ->
+    finalize, forward and backward) with an all-reduce that leaves the sums as they are: one rank's sums are the global
+    sums, so the step must meet the same float64 restatement within the same bounds."""
+    import adam_dehaze_amd.engine as E
+    calls = []
+    monkeypatch.setattr(E, "SYNC_BN", lambda sums: calls.append(sums.numel()))
+    _check_train_forward_backward_vs_restatement("mobilenet_v3_small")
+    assert len(calls) >= 2 * 30 and all(n % 2 == 1 for n in calls)      # forward and backward of every BatchNorm: 2 C + 1 doubles
 
 
 def test_v3_small_eval_mode_with_gradients():

@@ -1,6 +1,8 @@
 """Which kernel a convolution layer gets, with which descriptor, pack size, split count, slab size and statistics-row offsets:
 the launch sequence of Engine._run_gather / _wgrad / conv / backward, recorded on the CPU (tests/_launch_trace.py) and
-compared with tests/golden/launch_trace.json."""
+compared with tests/golden/launch_trace.json.  Every other op of the engine -- the BatchNorm sequences, the depthwise,
+DenseNet, attention, pooling and pointwise ops, with the host-side writes between their launches -- is compared with
+tests/golden/launch_trace_ops.json the same way."""
 import json
 import re
 
@@ -13,6 +15,14 @@ from tests import _launch_trace as LT
 @pytest.fixture(scope="module")
 def golden():
     with open(LT.GOLDEN_PATH) as f:
+        g = json.load(f)
+    assert g["conv_desc_fields"] == LT.DESC_FIELDS, "ConvDesc changed: regenerate the golden (tests/_launch_trace.py)"
+    return g["cases"]
+
+
+@pytest.fixture(scope="module")
+def ops_golden():
+    with open(LT.OPS_GOLDEN_PATH) as f:
         g = json.load(f)
     assert g["conv_desc_fields"] == LT.DESC_FIELDS, "ConvDesc changed: regenerate the golden (tests/_launch_trace.py)"
     return g["cases"]
@@ -33,6 +43,26 @@ def test_launch_sequence_matches_golden(name, golden, monkeypatch):
     got = LT.run_case(name, monkeypatch)
     diff = LT.differences(got, golden[name], name)
     assert not diff, "\n".join(diff)
+
+
+def test_ops_golden_has_exactly_the_cases(ops_golden):
+    assert list(ops_golden) == list(LT.OPS_CASES) and not set(LT.OPS_CASES) & set(LT.CASES)
+
+
+@pytest.mark.parametrize("name", list(LT.OPS_CASES))
+def test_op_launch_sequence_matches_golden(name, ops_golden, monkeypatch):
+    got = LT.run_case(name, monkeypatch)
+    diff = LT.differences(got, ops_golden[name], name)
+    assert not diff, "\n".join(diff)
+
+
+def test_every_entry_point_the_engine_names_is_in_a_trace(golden, ops_golden):
+    """an op cannot be added to engine.py, or drop out of the traces, silently"""
+    with open(LT.E.__file__) as f:
+        want = set(re.findall(r'H\.call\("(adh_\w+)"', f.read()))
+    assert len(want) >= 50
+    seen = {r[0] for cases in (golden, ops_golden) for recs in cases.values() for r in recs}
+    assert not want - seen, sorted(want - seen)
 
 
 def test_second_forward_with_pack_cache_records_no_pack_call(monkeypatch):
