@@ -1,23 +1,27 @@
-"""The training / validation drivers of the hot path (/root/reference training/train_joint.py:29-310,
-training/train_dehazing.py:16-214) on the HIP engine, plus the data-parallel wrapper.
+"""The training, validation and evaluation drivers (/root/reference training/train_joint.py:29-310,
+training/train_dehazing.py:16-214, training/train_classifier.py:13-226, evaluation/evaluate.py) on the HIP engine.
 
-`build_joint_system(config)` reproduces the reference's construction order (classifier, low, medium,
-high -> router -> optimiser -> scheduler -> criterion, train_joint.py:36-98) including the duplicated
-branch parameters in the optimiser's parameter list.  `joint_train_step` is the body of the hot loop
-(train_joint.py:129-166), `dehazing_train_step` the one of train_dehazing.py:71-106; `validate_joint` /
-`validate_dehazing` mirror the validation loops (train_joint.py:173-236, train_dehazing.py:109-166) with
-PSNR / SSIM computed on the device for whole batches (metrics.py) and ONE host read-back per epoch;
-checkpoints carry exactly the reference's keys (train_joint.py:272-283,291-302; train_dehazing.py:196-203,
-208-215) plus `scheduler_state_dict`, and `resume=` restores model, optimiser, scheduler, epoch and
-best-PSNR (the reference parses `--resume` and ignores it, main.py:50-51).
-Dataset I/O (cv2 image folders) is out of scope: `data.synthetic_loader` produces foggy frames on the GPU
-with the reference's own fog model when no loader is supplied.
+Hot path: `build_joint_system(config)` reproduces the reference's construction order (classifier, low, medium, high ->
+router -> optimiser -> scheduler -> criterion, train_joint.py:36-98) including the duplicated branch parameters in the
+optimiser's list; `joint_train_step` is the body of the hot loop (train_joint.py:129-166), `dehazing_train_step` the one of
+train_dehazing.py:71-106.
 
-Data-parallel runs (torchrun, one process per GPU): replicas are made identical by broadcasting rank 0's
-parameters and buffers after construction / checkpoint loading; gradients go through
-`parallel.GradientSynchronizer` (flat buckets all-reduced while backward is still running); every
-host-side decision that steers training -- the metric given to ReduceLROnPlateau, "skip this step, the
-sub-batch is empty" -- is agreed across ranks first, so learning rates and step counts cannot diverge.
+One epoch loop, `_run_epochs`, serves the three stages and is the only statement of the order between ranks: train, take
+rank 0's buffers, validate (sample-weighted sums all-reduced, ONE host read-back per epoch), scheduler step on the agreed
+validation loss, rank 0 reports and writes `best_model.pth` / every fifth `checkpoint_epoch_N.pth` atomically, barrier.  A
+stage plugs in closures: `train_joint_model` (score val_psnr, reports the rank-averaged train loss, leaves its synchronizer
+installed), `train_dehazing_model` (score val_psnr, level-filtered steps, uninstalls its synchronizer in a `finally`),
+`train_classifier` (score accuracy from -1; single process, no resume, reloads the best model).  Written once beside it:
+`_loader_or_synthetic` (the given loader, else `data.synthetic_loader`: image folders are out of scope),
+`_restore_training_state` (what `resume=` restores after the stage's own key check; the reference parses `--resume` and
+ignores it, main.py:50-51), `_validation_sums` for `validate_joint` / `validate_dehazing`, `_joint_system_for_evaluation`
+for the evaluators.  Checkpoints carry the reference's keys (train_joint.py:272-283, train_dehazing.py:196-203) plus
+`scheduler_state_dict`.
+
+Data-parallel runs (torchrun, one process per GPU): replicas are made identical by broadcasting rank 0's parameters and
+buffers after construction / checkpoint loading; gradients go through `parallel.GradientSynchronizer`; every host-side
+decision that steers training -- the metric given to ReduceLROnPlateau, "skip this step, the sub-batch is empty" -- is
+agreed across ranks first, so learning rates and step counts cannot diverge.
 """
 from __future__ import annotations
 
@@ -206,6 +210,17 @@ def _finish_validation(sums: Dict[str, torch.Tensor], count: int, device) -> Dic
     return out
 
 
+def _validation_sums(keys, device):
+    """The accumulator of a validation pass: (sums, add).  The key set is fixed and every sum starts at zero, so a rank that
+    saw nothing still hands the full vector to the all-reduce inside _finish_validation (a rank returning early
+    left the others waiting in the collective)."""
+    sums = {k: torch.zeros((), dtype=torch.float64, device=device) for k in keys}
+
+    def add(k, v):
+        sums[k] = sums[k] + v
+    return sums, add
+
+
 def validate_joint(system: Dict, val_loader: Iterable[Dict]) -> Dict[str, float]:
     """train_joint.py:173-236: eval mode, classifier -> router -> JointLoss, per-image PSNR / SSIM; returns
     {'val_loss','val_dehaze_loss','val_class_loss','val_psnr','val_ssim','val_samples'} (sample-weighted means)."""
@@ -214,12 +229,8 @@ def validate_joint(system: Dict, val_loader: Iterable[Dict]) -> Dict[str, float]
     for m in system["models"].values():
         m.eval()
     system["router"].eval()
-    sums: Dict[str, torch.Tensor] = {}
+    sums, add = _validation_sums(("val_loss", "val_dehaze_loss", "val_class_loss", "val_psnr", "val_ssim"), dev)
     count = 0
-
-    def add(k, v):
-        sums[k] = v if k not in sums else sums[k] + v
-
     with torch.no_grad():
         for batch in val_loader:
             hazy, clear, labels = batch["hazy"].to(dev), batch["clear"].to(dev), batch["intensity"].to(dev)
@@ -233,10 +244,6 @@ def validate_joint(system: Dict, val_loader: Iterable[Dict]) -> Dict[str, float]
             add("val_psnr", psnr_batch(dehazed, clear).double().sum())
             add("val_ssim", ssim_batch(dehazed, clear).double().sum())
             count += n
-    # fixed key set, zeros when this rank saw nothing: under data parallelism EVERY rank must enter the all-reduce inside
-    # _finish_validation (a rank returning early here left the others waiting in the collective)
-    for k in ("val_loss", "val_dehaze_loss", "val_class_loss", "val_psnr", "val_ssim"):
-        sums.setdefault(k, torch.zeros((), dtype=torch.float64, device=dev))
     return _finish_validation(sums, count, dev)
 
 
@@ -244,12 +251,9 @@ def validate_dehazing(model, criterion, val_loader: Iterable[Dict], level: Optio
     """train_dehazing.py:109-166: eval mode, images of this branch's level only; returns
     {'val_loss','val_perceptual','val_psnr','val_ssim','val_samples'}."""
     model.eval()
-    sums: Dict[str, torch.Tensor] = {}
+    device = torch.device(device)
+    sums, add = _validation_sums(("val_loss", "val_perceptual", "val_psnr", "val_ssim"), device)
     count = 0
-
-    def add(k, v):
-        sums[k] = v if k not in sums else sums[k] + v
-
     with torch.no_grad():
         for batch in val_loader:
             hazy, clear = batch["hazy"], batch["clear"]
@@ -267,9 +271,7 @@ def validate_dehazing(model, criterion, val_loader: Iterable[Dict], level: Optio
             add("val_psnr", psnr_batch(out, clear).double().sum())
             add("val_ssim", ssim_batch(out, clear).double().sum())
             count += n
-    for k in ("val_loss", "val_perceptual", "val_psnr", "val_ssim"):      # see validate_joint: no early return
-        sums.setdefault(k, torch.zeros((), dtype=torch.float64, device=torch.device(device)))
-    return _finish_validation(sums, count, torch.device(device))
+    return _finish_validation(sums, count, device)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -377,24 +379,34 @@ def checkpoint_stage(path: str, config) -> str:
     raise ValueError(f"--resume {path}: model_state_dict matches none of the configured branches")
 
 
+def _restore_training_state(ck: Dict, optimizer, scheduler, sync, module) -> int:
+    """What every resume does once its stage has checked `ck` and loaded the weights into `module`: optimiser and scheduler
+    state, the packed copies of the old weights dropped, the replicas made identical again.  Returns the epoch to continue
+    with; the best score so far is `_best_psnr_on_disk` of the stage's directory."""
+    if "optimizer_state_dict" in ck:
+        optimizer.load_state_dict(ck["optimizer_state_dict"])
+    if "scheduler_state_dict" in ck:
+        scheduler.load_state_dict(ck["scheduler_state_dict"])
+    from .engine import invalidate_weight_cache
+    invalidate_weight_cache()
+    if sync is not None:
+        sync.broadcast_parameters(module)
+    return int(ck["epoch"]) + 1
+
+
 def resume_joint(system: Dict, path: str) -> int:
-    """Restore a joint checkpoint; returns the epoch to continue with."""
+    """Restore a joint checkpoint (every rank loads it, then takes rank 0's copy); returns the epoch to continue with."""
     ck = torch.load(path, map_location="cpu")
     if "router_state_dict" not in ck:
         raise ValueError(f"--resume {path}: not a joint-training checkpoint (keys {sorted(ck)[:6]} ...); a branch "
                          "checkpoint resumes `--mode train_dehazing`, not this stage")
     system["router"].load_state_dict(ck["router_state_dict"])   # holds the classifier and the three branches
-    if "optimizer_state_dict" in ck:
-        system["optimizer"].load_state_dict(ck["optimizer_state_dict"])
-    if "scheduler_state_dict" in ck:
-        system["scheduler"].load_state_dict(ck["scheduler_state_dict"])
-    from .engine import invalidate_weight_cache
-    invalidate_weight_cache()
+    start_epoch = _restore_training_state(ck, system["optimizer"], system["scheduler"], system["sync"], system["router"])
     print(f"Resumed joint training from {path} (epoch {ck['epoch'] + 1} done)")
-    return int(ck["epoch"]) + 1
+    return start_epoch
 
 
-def _warn_synthetic(config, what: str, rank: int):
+def _warn_synthetic(config, what: str, rank: int, stacklevel: int = 3):
     paths = [config.get("dataset", {}).get(k) for k in ("train_path", "val_path", "test_path")]
     if rank == 0:
         msg = (f"{what}: no DataLoader was supplied -- training on SYNTHETIC foggy frames generated on the GPU "
@@ -402,7 +414,51 @@ def _warn_synthetic(config, what: str, rank: int):
         if any(paths):
             msg += (f"  Dataset paths are configured ({[p for p in paths if p]}) but this build does not read image "
                     "folders (data/dataset.py needs cv2, out of scope): pass train_loader= / val_loader=.")
-        warnings.warn(msg, stacklevel=3)
+        warnings.warn(msg, stacklevel=stacklevel)
+
+
+def _loader_or_synthetic(loader, config, steps: int, seed_offset: int, device, epoch: int = 0, warn: Optional[str] = None):
+    """The loader choice of every driver: `loader` as it is (a callable is asked for the epoch's iterable), else `steps`
+    synthetic batches seeded `seed + seed_offset + epoch`: offset 0 and the epoch for training frames, 500000 for the fixed
+    validation set, 900000 / 910000 for the test sets, whose drivers pass their name as `warn` to say so."""
+    if loader is not None:
+        return loader(epoch) if callable(loader) else loader
+    rank = _world_rank()[1]
+    if warn is not None:
+        _warn_synthetic(config, warn, rank, stacklevel=4)
+    return synthetic_loader(config["dataset"]["batch_size"], config["dataset"]["img_size"], steps,
+                            seed=config["seed"] + seed_offset + epoch, rank=rank, device=device)
+
+
+def _run_epochs(first_epoch: int, epochs: int, train_epoch, validate, scheduler, loss_key: str, score_key: str, best: float,
+                score_text: str, ck_dir: str, checkpoint, report, sync=None, modules=(), device=None):
+    """The epoch loop of the three training stages: the one statement of what the ranks do in which order.  The stage plugs
+    in `train_epoch(epoch)`, `validate() -> dict`, `checkpoint(epoch, val) -> dict` and `report(epoch, train_loss, val)`.
+    Returns the per-epoch records {"epoch", "train_loss", **val, "lr"}."""
+    rank = _world_rank()[1]
+    history = []
+    if rank == 0:
+        os.makedirs(ck_dir, exist_ok=True)
+    for epoch in range(first_epoch, epochs):
+        # None, or this rank's mean train loss where the stage reports the rank-averaged one (the joint stage)
+        train_loss = train_epoch(epoch)
+        _sync_buffers_from_rank0(sync, *modules)      # validation and rank 0's checkpoint see one model
+        val = validate()                              # every rank enters its all-reduce, also one with nothing to validate
+        if train_loss is not None:
+            train_loss = all_reduce_mean_scalar(train_loss, device)
+        scheduler.step(val[loss_key])                 # every rank steps on the same (rank-averaged) value
+        history.append({"epoch": epoch, "train_loss": train_loss, **val, "lr": scheduler.opt.param_groups[0]["lr"]})
+        if rank == 0:
+            report(epoch, train_loss, val)
+            if val[score_key] > best:
+                save_checkpoint_atomic(checkpoint(epoch, val), os.path.join(ck_dir, "best_model.pth"))
+                print("Saved best model with validation " + score_text.format(val[score_key]))
+            if (epoch + 1) % 5 == 0:
+                save_checkpoint_atomic(checkpoint(epoch, val), os.path.join(ck_dir, f"checkpoint_epoch_{epoch + 1}.pth"))
+        best = max(best, val[score_key])
+        # nobody runs ahead (into the next stage's load_pretrained_model, a --resume) while rank 0 is still writing
+        _barrier()
+    return history
 
 
 def train_joint_model(config, train_loader=None, val_loader=None, steps_per_epoch: int = 4, epochs: Optional[int] = None,
@@ -410,7 +466,7 @@ def train_joint_model(config, train_loader=None, val_loader=None, steps_per_epoc
     """train_joint.py:29 entry point: epochs of (train, validate, scheduler.step(val_loss), best / periodic
     checkpoints).  `train_loader` / `val_loader`: iterables of batch dicts (re-iterated every epoch) or callables
     epoch -> iterable; synthetic frames when None.  Returns (system, history of per-epoch dicts)."""
-    world, rank = _world_rank()
+    world = _world_rank()[0]
     system = build_joint_system(config, world)
     dev = system["device"]
     ck_dir = config["joint_training"]["checkpoint_dir"]
@@ -418,53 +474,40 @@ def train_joint_model(config, train_loader=None, val_loader=None, steps_per_epoc
     start_epoch, best_val_psnr = 0, 0.0
     path = _resolve_resume(resume, ck_dir)
     if path is not None:
-        start_epoch = resume_joint(system, path)
-        best_val_psnr = _best_psnr_on_disk(ck_dir)
-        if system["sync"] is not None:
-            system["sync"].broadcast_parameters(system["router"])
+        start_epoch, best_val_psnr = resume_joint(system, path), _best_psnr_on_disk(ck_dir)
     if train_loader is None or val_loader is None:
-        _warn_synthetic(config, "train_joint_model", rank)
-    bs, size = config["dataset"]["batch_size"], config["dataset"]["img_size"]
+        _warn_synthetic(config, "train_joint_model", _world_rank()[1])
+    ssim_total, n = None, 0      # the opt-in loss term summed over the epoch's steps on this rank, for the report
 
-    def loader_for(ld, epoch, steps, seed_off):
-        if ld is None:
-            return synthetic_loader(bs, size, steps, seed=config["seed"] + seed_off + epoch, rank=rank, device=dev)
-        return ld(epoch) if callable(ld) else ld
-
-    history = []
-    if rank == 0:
-        os.makedirs(ck_dir, exist_ok=True)
-    for epoch in range(start_epoch, epochs):
+    def train_epoch(epoch):
+        nonlocal ssim_total, n
         system["classifier"].train()
         for m in system["models"].values():
             m.train()
         system["router"].train()
         total, ssim_total, n = None, None, 0
-        for batch in loader_for(train_loader, epoch, steps_per_epoch, 0):
+        for batch in _loader_or_synthetic(train_loader, config, steps_per_epoch, 0, dev, epoch):
             stats = joint_train_step(system, batch)
             total = stats["loss"] if total is None else total + stats["loss"]
             if "ssim" in stats:
                 ssim_total = stats["ssim"] if ssim_total is None else ssim_total + stats["ssim"]
             n += 1
-        _sync_buffers_from_rank0(system["sync"], system["router"])
-        val = validate_joint(system, loader_for(val_loader, 0, val_steps, 500000))   # a fixed validation set
-        train_loss = all_reduce_mean_scalar(float(total) / max(1, n) if total is not None else 0.0, dev)
-        system["scheduler"].step(val["val_loss"])      # every rank steps on the same (rank-averaged) value
-        rec = {"epoch": epoch, "train_loss": train_loss, **val, "lr": system["optimizer"].param_groups[0]["lr"]}
-        history.append(rec)
-        if rank == 0:
-            ssim_part = "" if ssim_total is None else f" (1 - SSIM: {float(ssim_total) / max(1, n):.4f}, this rank)"
-            print(f"Epoch {epoch + 1}/{epochs}:\n  Train Loss: {train_loss:.4f}{ssim_part}\n  Val Loss: {val['val_loss']:.4f} "
-                  f"(Dehaze: {val['val_dehaze_loss']:.4f}, Class: {val['val_class_loss']:.4f})\n"
-                  f"  Val PSNR: {val['val_psnr']:.2f} dB, Val SSIM: {val['val_ssim']:.4f}")
-            if val["val_psnr"] > best_val_psnr:
-                save_checkpoint_atomic(joint_checkpoint(system, epoch, val), os.path.join(ck_dir, "best_model.pth"))
-                print(f"Saved best model with validation PSNR: {val['val_psnr']:.2f} dB")
-            if (epoch + 1) % 5 == 0:
-                save_checkpoint_atomic(joint_checkpoint(system, epoch, val),
-                                       os.path.join(ck_dir, f"checkpoint_epoch_{epoch + 1}.pth"))
-        best_val_psnr = max(best_val_psnr, val["val_psnr"])
-        _barrier()       # nobody runs ahead (and reads a checkpoint) while rank 0 is still writing
+        return float(total) / max(1, n) if total is not None else 0.0
+
+    def report(epoch, train_loss, val):
+        ssim_part = "" if ssim_total is None else f" (1 - SSIM: {float(ssim_total) / max(1, n):.4f}, this rank)"
+        print(f"Epoch {epoch + 1}/{epochs}:\n  Train Loss: {train_loss:.4f}{ssim_part}\n  Val Loss: {val['val_loss']:.4f} "
+              f"(Dehaze: {val['val_dehaze_loss']:.4f}, Class: {val['val_class_loss']:.4f})\n"
+              f"  Val PSNR: {val['val_psnr']:.2f} dB, Val SSIM: {val['val_ssim']:.4f}")
+
+    def validate():
+        return validate_joint(system, _loader_or_synthetic(val_loader, config, val_steps, 500000, dev))
+
+    # (unlike the branch stage, this one leaves its synchronizer installed when it returns)
+    history = _run_epochs(start_epoch, epochs, train_epoch, validate, system["scheduler"], loss_key="val_loss",
+                          score_key="val_psnr", best=best_val_psnr, score_text="PSNR: {:.2f} dB", ck_dir=ck_dir,
+                          checkpoint=lambda epoch, val: joint_checkpoint(system, epoch, val), report=report,
+                          sync=system["sync"], modules=(system["router"],), device=dev)
     return system, history
 
 
@@ -473,7 +516,7 @@ def train_dehazing_model(config, intensity_level: str, train_loader=None, val_lo
     """train_dehazing.py:16 entry point for one branch: Adam(lr, wd 1e-4) + ReduceLROnPlateau(patience 5) +
     DehazingLoss, level-filtered batches, validation, best / every-5-epochs checkpoints under
     `<dehazing.checkpoint_dir>/<level>/` (the reference runs 30 epochs, :64).  Returns (model, per-step train losses)."""
-    world, rank = _world_rank()
+    world = _world_rank()[0]
     device = torch.device(config["device"])
     factory = {"low": create_low_intensity_model, "medium": create_medium_intensity_model,
                "high": create_high_intensity_model}[intensity_level]
@@ -500,55 +543,38 @@ def train_dehazing_model(config, intensity_level: str, train_loader=None, val_lo
             raise ValueError(f"--resume {path}: checkpoint does not belong to the '{intensity_level}' branch "
                              f"({len(missing)} state_dict keys differ, e.g. {sorted(missing)[:3]})")
         model.load_state_dict(ck["model_state_dict"])
-        if "optimizer_state_dict" in ck:
-            optimizer.load_state_dict(ck["optimizer_state_dict"])
-        if "scheduler_state_dict" in ck:
-            scheduler.load_state_dict(ck["scheduler_state_dict"])
-        start_epoch, best_val_psnr = int(ck["epoch"]) + 1, _best_psnr_on_disk(ck_dir)
-        from .engine import invalidate_weight_cache
-        invalidate_weight_cache()
-        if sync is not None:
-            sync.broadcast_parameters(model)
+        start_epoch = _restore_training_state(ck, optimizer, scheduler, sync, model)
+        best_val_psnr = _best_psnr_on_disk(ck_dir)
     if train_loader is None or val_loader is None:
-        _warn_synthetic(config, f"train_dehazing_model[{intensity_level}]", rank)
-    bs, size = config["dataset"]["batch_size"], config["dataset"]["img_size"]
+        _warn_synthetic(config, f"train_dehazing_model[{intensity_level}]", _world_rank()[1])
+    losses, ssim_terms = [], []
 
-    def loader_for(ld, epoch, nsteps, seed_off):
-        if ld is None:
-            return synthetic_loader(bs, size, nsteps, seed=config["seed"] + seed_off + epoch, rank=rank, device=device)
-        return ld(epoch) if callable(ld) else ld
+    def train_epoch(epoch):
+        model.train()
+        ssim_terms.clear()
+        for batch in _loader_or_synthetic(train_loader, config, steps, 0, device, epoch):
+            st = dehazing_train_step(model, criterion, optimizer, batch, level, device, sync=sync)
+            if st is not None:
+                losses.append(st["loss"])
+                if "ssim" in st:
+                    ssim_terms.append(st["ssim"])
 
-    losses = []
-    if rank == 0:
-        os.makedirs(ck_dir, exist_ok=True)
+    def report(epoch, train_loss, val):
+        print(f"Epoch {epoch + 1}/{epochs}:\n  Val Loss: {val['val_loss']:.4f}, Val PSNR: {val['val_psnr']:.2f}, "
+              f"Val SSIM: {val['val_ssim']:.4f}")
+        if ssim_terms:                         # the opt-in loss term, mean over this rank's steps like the L1 term
+            print(f"  Train 1 - SSIM: {float(torch.stack(ssim_terms).mean()):.4f}")
+
+    def validate():
+        val_batches = _loader_or_synthetic(val_loader, config, val_steps, 500000, device)
+        return validate_dehazing(model, criterion, val_batches, level, device)
+
     try:
-        for epoch in range(start_epoch, epochs):
-            model.train()
-            ssim_terms = []
-            for batch in loader_for(train_loader, epoch, steps, 0):
-                st = dehazing_train_step(model, criterion, optimizer, batch, level, device, sync=sync)
-                if st is not None:
-                    losses.append(st["loss"])
-                    if "ssim" in st:
-                        ssim_terms.append(st["ssim"])
-            _sync_buffers_from_rank0(sync, model)
-            val = validate_dehazing(model, criterion, loader_for(val_loader, 0, val_steps, 500000), level, device)
-            scheduler.step(val["val_loss"])
-            if rank == 0:
-                print(f"Epoch {epoch + 1}/{epochs}:\n  Val Loss: {val['val_loss']:.4f}, Val PSNR: {val['val_psnr']:.2f}, "
-                      f"Val SSIM: {val['val_ssim']:.4f}")
-                if ssim_terms:                         # the opt-in loss term, mean over this rank's steps like the L1 term
-                    print(f"  Train 1 - SSIM: {float(torch.stack(ssim_terms).mean()):.4f}")
-                if val["val_psnr"] > best_val_psnr:
-                    save_checkpoint_atomic(dehazing_checkpoint(model, optimizer, scheduler, epoch, val),
-                                           os.path.join(ck_dir, "best_model.pth"))
-                    print(f"Saved best model with validation PSNR: {val['val_psnr']:.2f} dB")
-                if (epoch + 1) % 5 == 0:
-                    save_checkpoint_atomic(dehazing_checkpoint(model, optimizer, scheduler, epoch, val),
-                                           os.path.join(ck_dir, f"checkpoint_epoch_{epoch + 1}.pth"))
-            best_val_psnr = max(best_val_psnr, val["val_psnr"])
-            _barrier()   # train_all: the next stage's load_pretrained_model must not race rank 0's write
-    finally:
+        _run_epochs(start_epoch, epochs, train_epoch, validate, scheduler, loss_key="val_loss", score_key="val_psnr",
+                    best=best_val_psnr, score_text="PSNR: {:.2f} dB", ck_dir=ck_dir,
+                    checkpoint=lambda epoch, val: dehazing_checkpoint(model, optimizer, scheduler, epoch, val), report=report,
+                    sync=sync, modules=(model,))
+    finally:       # train_all: the next stage builds its own synchronizer
         if sync is not None:
             sync.uninstall()
     return model, [float(x) for x in losses]
@@ -605,6 +631,26 @@ def _eval_wait_group():
     return _EVAL_GROUP
 
 
+def _joint_system_for_evaluation(config):
+    """The routed system as an evaluator wants it: built for one process, the joint checkpoint loaded over the individually
+    loaded weights if there is one, everything in eval mode.  Returns (system, path of the joint checkpoint it loaded or
+    None)."""
+    system = build_joint_system(config, 1)
+    ck = os.path.join(config["joint_training"]["checkpoint_dir"], "best_model.pth")
+    loaded = None
+    if os.path.exists(ck):
+        system["router"].load_state_dict(torch.load(ck, map_location="cpu")["router_state_dict"])
+        loaded = ck
+        print(f"Loaded joint model from {ck}")
+    else:
+        print(f"Joint checkpoint {ck} not found. Using the individually loaded / random weights.")
+    system["classifier"].eval()
+    for m in system["models"].values():
+        m.eval()
+    system["router"].eval()
+    return system, loaded
+
+
 @_rank0_only
 def evaluate_joint_model(config, test_loader=None, steps: int = 2, use_lpips: bool = True):
     """evaluation/evaluate.py:94-177 (image-quality part): load the joint checkpoint if present, route every test
@@ -613,25 +659,10 @@ def evaluate_joint_model(config, test_loader=None, steps: int = 2, use_lpips: bo
     from .metrics import CATEGORY_BY_LABEL, ImageQualityMetrics
     # (every rank scoring its own shard and writing the same JSON concurrently was a race, ADVICE r2: rank 0 evaluates and
     # writes, the others wait for it in _rank0_only)
-    world, rank = _world_rank()
-    system = build_joint_system(config, 1)
+    system, _ = _joint_system_for_evaluation(config)
     dev = system["device"]
-    ck = os.path.join(config["joint_training"]["checkpoint_dir"], "best_model.pth")
-    if os.path.exists(ck):
-        c = torch.load(ck, map_location="cpu")
-        system["router"].load_state_dict(c["router_state_dict"])
-        print(f"Loaded joint model from {ck}")
-    else:
-        print(f"Joint checkpoint {ck} not found. Using the individually loaded / random weights.")
-    system["classifier"].eval()
-    for m in system["models"].values():
-        m.eval()
-    system["router"].eval()
     metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips)
-    if test_loader is None:
-        _warn_synthetic(config, "evaluate_joint_model", rank)
-        test_loader = synthetic_loader(config["dataset"]["batch_size"], config["dataset"]["img_size"], steps,
-                                       seed=config["seed"] + 900000, rank=rank, device=dev)
+    test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, dev, warn="evaluate_joint_model")
     with torch.no_grad():
         for batch in test_loader:
             hazy, clear = batch["hazy"].to(dev), batch["clear"].to(dev)
@@ -651,7 +682,6 @@ def evaluate_baseline_models(config, test_loader=None, steps: int = 2, use_lpips
     no router), PSNR / SSIM / LPIPS per category on the device, `<evaluation.results_dir>/baseline_results.json`.  The reference
     runs one image at a time; eval-mode branches are per-sample independent, so the images of a level go through as one batch."""
     from .metrics import CATEGORY_BY_LABEL, ImageQualityMetrics
-    world, rank = _world_rank()
     system = build_joint_system(config, 1)
     dev = system["device"]
     for level, m in system["models"].items():
@@ -659,10 +689,7 @@ def evaluate_baseline_models(config, test_loader=None, steps: int = 2, use_lpips
         m.eval()
     by_label = {0: system["models"]["low"], 1: system["models"]["medium"], 2: system["models"]["high"]}
     metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips)
-    if test_loader is None:
-        _warn_synthetic(config, "evaluate_baseline_models", rank)
-        test_loader = synthetic_loader(config["dataset"]["batch_size"], config["dataset"]["img_size"], steps,
-                                       seed=config["seed"] + 900000, rank=rank, device=dev)
+    test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, dev, warn="evaluate_baseline_models")
     with torch.no_grad():
         for batch in test_loader:
             hazy, clear = batch["hazy"].to(dev), batch["clear"].to(dev)
@@ -736,21 +763,13 @@ def evaluate_detection(config, test_loader=None, steps: int = 1, score_threshold
     import json
     from .detection import create_detection_model, create_integrated_system, filter_detections
     from .metrics import CATEGORY_BY_LABEL, DetectionMetrics
-    world, rank = _world_rank()
-    system = build_joint_system(config, 1)
-    dev = system["device"]
     # evaluation/evaluate.py:201-227: the JOINT checkpoint into classifier + router + branches, and the detector's own
     # checkpoint when there is one (this used to score 'dehazed' detections with the pre-joint weights and an always
     # random-init detector).  What was used goes into the results file.
-    weights = {"joint_checkpoint": None, "detector_checkpoint": None}
-    ck = os.path.join(config["joint_training"]["checkpoint_dir"], "best_model.pth")
-    if os.path.exists(ck):
-        c = torch.load(ck, map_location="cpu")
-        system["router"].load_state_dict(c["router_state_dict"])
-        weights["joint_checkpoint"] = ck
-        print(f"Loaded joint model from {ck}")
-    else:
-        print(f"Joint checkpoint {ck} not found. Using the individually loaded / random weights.")
+    system, joint_ck = _joint_system_for_evaluation(config)
+    dev = system["device"]
+    router = system["router"]
+    weights = {"joint_checkpoint": joint_ck, "detector_checkpoint": None}
     cfg = dict(config)
     cfg.setdefault("detection", {"model": "faster_rcnn_resnet50_fpn", "pretrained": False})
     detector = create_detection_model(cfg).to(dev).eval()
@@ -764,20 +783,13 @@ def evaluate_detection(config, test_loader=None, steps: int = 1, score_threshold
         print(f"Detection checkpoint {dck} not found: the detector runs on its "
               f"{'pretrained' if cfg['detection'].get('pretrained') else 'RANDOM-INIT'} weights (its detections carry no meaning then).")
     weights["detector_random_init"] = weights["detector_checkpoint"] is None and not cfg["detection"].get("pretrained")
-    system["classifier"].eval()
-    for m in system["models"].values():
-        m.eval()
-    router = system["router"].eval()
 
     class _Routed(torch.nn.Module):        # evaluate.py:262-286 process_batch: classifier -> router
         def forward(self, images):
             logits, _ = system["classifier"](images)
             return router(images, logits)
     integrated = create_integrated_system(_Routed(), detector)
-    if test_loader is None:
-        _warn_synthetic(config, "evaluate_detection", rank)
-        test_loader = synthetic_loader(config["dataset"]["batch_size"], config["dataset"]["img_size"], steps,
-                                       seed=config["seed"] + 910000, rank=rank, device=dev)
+    test_loader = _loader_or_synthetic(test_loader, config, steps, 910000, dev, warn="evaluate_detection")
     if annotation_file is None:
         annotation_file = os.path.join(str(config.get("dataset", {}).get("test_path", "")), "annotations", "instances.json")
     dm = None
@@ -895,8 +907,7 @@ def train_classifier(config, train_loader=None, val_loader=None, steps: int = 4,
                      val_steps: int = 2):
     """training/train_classifier.py:13-185.  Without loaders: `steps` / `val_steps` batches of synthetic foggy frames per
     epoch (labels = fog level).  Single process only (data-parallel classifier training is not built)."""
-    world, rank = _world_rank()
-    if world > 1:
+    if _world_rank()[0] > 1:
         raise RuntimeError("train_classifier runs in a single process; data-parallel classifier training is not implemented")
     device = torch.device(config["device"])
     cc = config["classifier"]
@@ -907,36 +918,34 @@ def train_classifier(config, train_loader=None, val_loader=None, steps: int = 4,
     os.makedirs(ck_dir, exist_ok=True)
     epochs = cc["epochs"] if epochs is None else epochs
     if train_loader is None or val_loader is None:
-        _warn_synthetic(config, "train_classifier", rank)
-    bs, size = config["dataset"]["batch_size"], config["dataset"]["img_size"]
+        _warn_synthetic(config, "train_classifier", _world_rank()[1])
+    tr = {}
 
-    def loader_for(ld, epoch, nsteps, seed_off):
-        if ld is None:
-            return synthetic_loader(bs, size, nsteps, seed=config["seed"] + seed_off + epoch, device=device)
-        return ld(epoch) if callable(ld) else ld
-
-    best_acc = -1.0      # (the reference starts at 0.0 and writes nothing if every epoch scores 0 %, then fails to reload)
-    best_path = os.path.join(ck_dir, "best_model.pth")
-    for epoch in range(epochs):
+    def train_epoch(epoch):
         model.train()
-        tr = _classifier_pass(model, loader_for(train_loader, epoch, steps, 0), device, optimizer)
+        train_batches = _loader_or_synthetic(train_loader, config, steps, 0, device, epoch)
+        tr.update(_classifier_pass(model, train_batches, device, optimizer))
+
+    def validate():
         model.eval()
-        val = _classifier_pass(model, loader_for(val_loader, 0, val_steps, 500000), device)   # a fixed validation set
-        val_acc = _accuracy(val["confusion_matrix"])
-        scheduler.step(val["loss"])
+        val = _classifier_pass(model, _loader_or_synthetic(val_loader, config, val_steps, 500000, device), device)
+        return {**val, "val_acc": _accuracy(val["confusion_matrix"])}
+
+    def report(epoch, train_loss, val):
         print(f"Epoch {epoch + 1}/{epochs}:")
         print(f"  Train Loss: {tr['loss']:.4f}, Train Acc: {_accuracy(tr['confusion_matrix']):.2f}%")
-        print(f"  Val Loss: {val['loss']:.4f}, Val Acc: {val_acc:.2f}%")
+        print(f"  Val Loss: {val['loss']:.4f}, Val Acc: {val['val_acc']:.2f}%")
         print(f"Confusion Matrix:\n{val['confusion_matrix']}")
         print(f"Classification Report:\n{classification_report3(val['confusion_matrix'])}")
-        ck = {"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
-              "val_acc": val_acc, "val_loss": val["loss"]}
-        if val_acc > best_acc:
-            best_acc = val_acc
-            save_checkpoint_atomic(ck, best_path)
-            print(f"Saved best model with validation accuracy: {val_acc:.2f}%")
-        if (epoch + 1) % 5 == 0:
-            save_checkpoint_atomic(ck, os.path.join(ck_dir, f"checkpoint_epoch_{epoch + 1}.pth"))
+
+    def checkpoint(epoch, val):
+        return {"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
+                "val_acc": val["val_acc"], "val_loss": val["loss"]}
+
+    # best starts at -1.0 (the reference starts at 0.0 and writes nothing if every epoch scores 0 %, then fails to reload)
+    _run_epochs(0, epochs, train_epoch, validate, scheduler, loss_key="loss", score_key="val_acc", best=-1.0,
+                score_text="accuracy: {:.2f}%", ck_dir=ck_dir, checkpoint=checkpoint, report=report)
+    best_path = os.path.join(ck_dir, "best_model.pth")
     if os.path.exists(best_path):
         model.load_state_dict(torch.load(best_path, map_location="cpu")["model_state_dict"])
     return model
@@ -947,10 +956,7 @@ def evaluate_classifier(model, config, test_loader=None, steps: int = 2) -> Dict
     (synthetic frames without a loader)."""
     device = torch.device(config["device"])
     model = model.to(device).eval()
-    if test_loader is None:
-        _warn_synthetic(config, "evaluate_classifier", _world_rank()[1])
-        test_loader = synthetic_loader(config["dataset"]["batch_size"], config["dataset"]["img_size"], steps,
-                                       seed=config["seed"] + 900000, device=device)
+    test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, device, warn="evaluate_classifier")
     res = _classifier_pass(model, test_loader, device)
     cm = res["confusion_matrix"]
     acc = _accuracy(cm)
