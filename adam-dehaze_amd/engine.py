@@ -928,7 +928,7 @@ class Engine:
     def conv(self, x: Act, w: torch.Tensor, b: Optional[torch.Tensor], bn: Optional[BNState], *, kind: str = "conv",
              k: int = 3, stride: int = 1, pad: int = 1, relu: bool = True, residual: Optional[Act] = None,
              training: bool = False, out: Optional[torch.Tensor] = None, out_alloc_C: Optional[int] = None,
-             act: Optional[int] = None, stats: Optional[list] = None) -> Act:
+             act: Optional[int] = None, stats: Optional[list] = None, capture: Optional[int] = None) -> Act:
         """ConvBlock / ConvTranspose+BN+ReLU / bare Conv2d as one fused op
         (base_model.py:4-24,26-41; medium_intensity.py:52-56).  `residual` is added after BN and before the
         ReLU (ResidualBlock tail).  `out`: optional preallocated [N,OH,OW,>=Cout] view to write into.
@@ -936,7 +936,9 @@ class Engine:
         residual, and run through adh_bn_apply after the raw conv in both modes.
         `stats`: a list, for a bare convolution (no BatchNorm, bias, residual or activation): the launch's epilogue also
         writes the per-block sums of its output and (partials [nblk][2][pitch], nblk, pitch) is appended (DenseNet's conv2,
-        whose output is a growth slice of the block buffer)."""
+        whose output is a growth slice of the block buffer).
+        `capture`: the key RELU_CAPTURE files the output under when `w` is a tensor rebuilt on every call (the LPIPS stem's
+        space-to-depth weights): id() of the parameter behind it; default id(w)."""
         if kind == "conv":
             Cout = w.shape[0]
             OH = (x.Hh + 2 * pad - k) // stride + 1
@@ -1013,7 +1015,7 @@ class Engine:
                 SYNC_BN is None:
             o.bn_src = (saved.y, saved.ss, saved.mean)
         if RELU_CAPTURE is not None and act_code in (H.ACT_RELU, H.ACT_RELU6):
-            RELU_CAPTURE[id(w)] = out
+            RELU_CAPTURE[id(w) if capture is None else capture] = out
         if self.record:
             # the parameters _conv_backward will produce a gradient for (must mirror its add_param_grad calls)
             bn_grads = bn is not None and (training or bn.weight.requires_grad or bn.bias.requires_grad)
@@ -1428,8 +1430,10 @@ class Engine:
             self._on_grad(o, bwd)
         return o
 
-    def activation(self, x: Act, act: int) -> Act:
-        """act(x) as a pass of its own (the squeeze-excitation gate, Hardsigmoid): adh_bn_apply with scale 1, shift 0."""
+    def activation(self, x: Act, act: int, capture: Optional[int] = None) -> Act:
+        """act(x) as a pass of its own (the squeeze-excitation gate, Hardsigmoid; the ReLU behind a tapped VGG conv):
+        adh_bn_apply with scale 1, shift 0.  `capture`: key RELU_CAPTURE files a ReLU / ReLU6 output under (id() of the weight
+        of the convolution in front, as Engine.conv does when it fuses the activation); None: not captured."""
         N, Hh, Ww, Cc = x.N, x.Hh, x.Ww, x.C
         C4 = _round_up(Cc, 4)
         ss = self._identity_coef(2, C4)
@@ -1437,6 +1441,8 @@ class Engine:
         H.call("adh_bn_apply", x.t.data_ptr(), x.cs, ss[0].data_ptr(), ss[1].data_ptr(), None, 0, act, out.data_ptr(), C4,
                x.pixels, C4, None)
         o = Act(out, Cc)
+        if RELU_CAPTURE is not None and capture is not None and act in (H.ACT_RELU, H.ACT_RELU6):
+            RELU_CAPTURE[capture] = out
         if self.record:
             def bwd(g):
                 gx = self._f(N, Hh, Ww, C4)

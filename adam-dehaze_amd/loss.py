@@ -200,8 +200,10 @@ class _ContentFn(torch.autograd.Function):
 class ContentLoss(nn.Module):
     """Content loss on VGG features (loss.py:7-84): ImageNet-normalise, then mean over the taps
     ['relu2_2','relu3_3','relu4_3'] of mse(features[:idx+1](x), features[:idx+1](target)) with the reference's
-    layer_mapping (idx 9/16/23 = the MaxPool layers after those relus in torchvision's vgg16.features).
-    One pass per image with three taps replaces the reference's six prefix passes (identical values).
+    layer_mapping (idx 9/16/23 = the MaxPool layers after those relus in torchvision's vgg16.features).  The mapping's
+    indices are positions in vgg16.features whatever the model: seven of its names (relu1_1 -> 2, ...) and, on vgg19, the
+    default 16 land ON a conv, whose tap is then the conv output before its relu, as features[:idx+1] gives it.
+    One pass per image over all taps replaces the reference's two prefix passes per tap (identical values).
     Weights: `model.{idx}.weight/bias` (torchvision naming); pretrained weights cannot be downloaded here,
     load them with load_state_dict.  The extractor is frozen (loss.py:27-28)."""
 
@@ -272,8 +274,9 @@ class ContentLoss(nn.Module):
                 break
             if kind == "conv":
                 p = self.model.at(idx)
-                # features[:idx+1] ending ON a conv index (never the case for the reference's mapping) would
-                # exclude the relu; the mapping's indices are relu / pool outputs, so conv+relu fuse safely
+                # features[:idx+1] ending ON a conv index excludes the relu (the mapping's relu1_1, relu2_1, relu3_1, relu3_2,
+                # relu4_1, relu4_2 and relu5_1, and index 16 of vgg19): such a tap is the raw conv output, and the relu runs
+                # as the pass of its own below; everywhere else conv+relu fuse
                 fuse_relu = (idx + 1) <= last and idx not in taps
                 h = eng.conv(h, p.weight, p.bias, None, k=3, stride=1, pad=1, relu=fuse_relu)
                 if idx in taps:
@@ -282,7 +285,12 @@ class ContentLoss(nn.Module):
                 if fuse_relu and (idx + 1) in taps:
                     feats.append(h)
                 continue
-            if kind == "pool":
+            if kind == "relu":
+                # the relu of a tapped conv: the conv output feeds the tap's MSE and this pass, Engine.accum sums the two
+                h = eng.activation(h, H.ACT_RELU, capture=id(self.model.at(idx - 1).weight))
+                if idx in taps:
+                    feats.append(h)
+            elif kind == "pool":
                 h = eng.maxpool(h, 2)
                 if idx in taps:
                     feats.append(h)
@@ -469,7 +477,7 @@ class PerceptualLoss(nn.Module):
         w[:, :, :11, :11] = c1.weight
         w1 = w.view(64, 3, 3, 4, 3, 4).permute(0, 3, 5, 1, 2, 4).reshape(64, 48, 3, 3).contiguous()
         feats = []
-        h = eng.conv(x, w1, c1.bias, None, k=3, stride=1, pad=0, relu=True)
+        h = eng.conv(x, w1, c1.bias, None, k=3, stride=1, pad=0, relu=True, capture=id(c1.weight))   # w1 is rebuilt per call
         feats.append(h)
         h = eng.maxpool(h, 3, 2, 0)
         c2 = lp.net.slice2.at(3)

@@ -4,7 +4,7 @@ import math
 
 import torch
 
-from oracle.ref_cpu import VGG16_CFG, ALEX_CFG, ALEX_SLICE_OF, DENSENET121_BLOCKS
+from oracle.ref_cpu import VGG16_CFG, VGG19_CFG, ALEX_CFG, ALEX_SLICE_OF, DENSENET121_BLOCKS
 
 
 def _conv(sd, name, cout, cin, k, g, bias=False):
@@ -114,11 +114,11 @@ def densenet121_sd(seed=0):
     return sd
 
 
-def vgg16_sd(seed=0, prefix="model."):
+def vgg16_sd(seed=0, prefix="model.", cfg=VGG16_CFG):
     g = torch.Generator().manual_seed(seed)
     sd = {}
     idx, cin = 0, 3
-    for v in VGG16_CFG:
+    for v in cfg:
         if v == "M":
             idx += 1
         else:
@@ -126,6 +126,10 @@ def vgg16_sd(seed=0, prefix="model."):
             cin = v
             idx += 2
     return sd
+
+
+def vgg19_sd(seed=0, prefix="model."):
+    return vgg16_sd(seed, prefix, VGG19_CFG)
 
 
 def lpips_alex_sd(seed=0, prefix="loss_fn."):

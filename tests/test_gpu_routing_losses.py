@@ -329,7 +329,10 @@ def test_content_loss_vs_oracle():
         dg = (p.grad.cpu() - pr.grad)
         print("VV content", float(dg.abs().max() / pr.grad.abs().max()), float(dg.norm() / pr.grad.norm()),
               int((dg.abs() > 1e-3 * pr.grad.abs().max()).sum()), dg.numel())
-    assert rel_err(p.grad, pr.grad) < 2e-3
+    # free-running fp32 oracle, kinks not matched: 1.2e-5 per convolution of the ten behind the last tap, the gradient floor of
+    # tests/test_gpu_loss_extractors.py, which holds the kink-matched gate (measured here: 4.5e-6; the fp32 oracle itself sits
+    # 2.9e-6 from its float64 twin)
+    assert rel_err(p.grad, pr.grad) < 1.2e-4
 
 
 def test_perceptual_loss_lpips_alex_vs_oracle():
@@ -348,7 +351,8 @@ def test_perceptual_loss_lpips_alex_vs_oracle():
     assert val.shape == (2, 1, 1, 1)
     assert rel_err(val, ref.detach()) < 1e-3
     val.mean().backward()
-    assert rel_err(p.grad, pr.grad) < 5e-3
+    # as for the content loss: 1.2e-5 for each of the five convolutions (measured: 2.2e-6, the fp32 oracle 1.5e-6 from float64)
+    assert rel_err(p.grad, pr.grad) < 6e-5
     with torch.no_grad():
         assert float(pl(p, p).abs().max()) < 1e-12    # identical inputs (fma contraction leaves ~1e-17)
 
