@@ -108,8 +108,47 @@ __device__ __forceinline__ void adh_mfma_operand_fence(float (&V)[4], float (&M)
                      "+v"(M[1][0]), "+v"(M[1][1]), "+v"(M[1][2]), "+v"(M[1][3]), "+v"(M[2][0]), "+v"(M[2][1]), "+v"(M[2][2]), "+v"(M[2][3]));
 }
 
-// conv_wgrad.hip: slab[0] = sum over `nsplit` partial slabs of n4 float4 each (in place, fixed order)
+// Offset of element (tap (ty, tx), k, n) of a weight tensor described by `L` (include/adam_dehaze_hip.h, adh_wlayout).  The tap
+// strides may be negative (reversed taps: tap_off0 then names the last tap).  The pack kernels read, and the weight-gradient reduce
+// kernels write, through this one expression (conv_wino43.hip's pack kernels stage the nine taps of a (k, n) pair as one window
+// from the smallest tap offset instead).  The tap part alone is for callers that hoist it out of a (k, n) loop.
+__host__ __device__ static inline int64_t adh_wlayout_tap_off(const adh_wlayout& L, int ty, int tx) {
+    return (int64_t)L.tap_off0 + ty * L.tap_off_sy + tx * L.tap_off_sx;
+}
+__host__ __device__ static inline int64_t adh_wlayout_off(const adh_wlayout& L, int ty, int tx, int k, int n) {
+    return adh_wlayout_tap_off(L, ty, tx) + (int64_t)k * L.stride_k + (int64_t)n * L.stride_n;
+}
+
+// Grid of the split-accumulating weight-gradient kernels (conv_wgrad_rows_kernel, conv_wgrad32_kernel, conv_wgrad32v2*_kernel,
+// conv_wgrad_wino43_kernel): `ngroups` workgroups (channel-block pairs) share one pixel split and so re-read the same tiles.
+// One workgroup is resident per CU and the hardware deals workgroups to the 8 XCDs round-robin (block b runs on XCD b % 8), so
+// block b is mapped to  group = (b >> 3) % ngroups,  split = (b >> 3) / ngroups * 8 + (b & 7):  the groups of one split have ids
+// congruent mod 8, land on one XCD and are served by its L2 after the first read; XCD x gets the splits = x mod 8 of every
+// group.  The split count is rounded up to a multiple of 8 for the launch; a block whose split >= nsplit returns at once.
+// (engine._rows_nsplit chooses nsplit from the cost of the rounds this mapping gives.)
+static inline int adh_split_grid_blocks(int nsplit, int ngroups) { return ((nsplit + 7) / 8) * ngroups * 8; }
+__device__ __forceinline__ void adh_split_grid_decode(int bid, int ngroups, int& group, int& split) {
+    const int q = bid >> 3;
+    group = q % ngroups;
+    split = (q / ngroups) * 8 + (bid & 7);
+}
+
+// Interpolation points +-a, +-b (and 0, infinity) of the F(4x4,3x3) weight gradient: conv_wgrad43.hip transforms with them,
+// conv_wgrad_reduce.hip inverts
+#define G4_A 0.75f
+#define G4_B 1.25f
+
+// conv_wgrad_reduce.hip: slab[0] = sum over `nsplit` partial slabs of n4 float4 each (in place, fixed order)
 void adh_wgrad_sum_splits(hipStream_t s, float* slab, int nsplit, int64_t n4);
+
+// conv_wgrad32.hip: the kernel-parity classes of the F(3x3,2x2)-domain weight gradient of `d`, for adh_wgrad_reduce_wino32:
+// output tap (hy, hx) of class c is tap index tap0[c] + ty tap_sy[c] + tx tap_sx[c] of d's KH x KW taps, (ty, tx) = (hy, hx), or
+// (1 - hy, 1 - hx) where rev[c] (taps walked backwards).  Returns 0 when `d` is not one of that path's shapes.
+struct adh_wg32_taps {
+    int ncls;
+    int tap0[4], tap_sy[4], tap_sx[4], rev[4];
+};
+int adh_wgrad32_class_taps(const adh_conv_desc* d, adh_wg32_taps* tp);
 
 // conv_rows.hip: direct forward kernel for the 2x2 / 3x3-tap gather forms (0 blocks / ADH_E_UNSUPPORTED when `d`
 // is not one of its shapes; conv_igemm.hip then takes the launch)

@@ -125,7 +125,7 @@ __global__ void pack_weights_fewout_kernel(const float* __restrict__ src, const 
         const int ty = t / 3, tx = t - ty * 3;
         float v = 0.f;
         if (co < L.Nc && k < L.K)
-            v = src[(int64_t)L.tap_off0 + ty * L.tap_off_sy + tx * L.tap_off_sx + (int64_t)k * L.stride_k + (int64_t)co * L.stride_n];
+            v = src[adh_wlayout_off(L, ty, tx, k, co)];
         wp[i] = v;
     }
 }
@@ -269,7 +269,7 @@ __global__ void pack_weights_fewin_kernel(const float* __restrict__ src, const a
         const int ty = t / 3, tx = t - ty * 3;
         float v = 0.f;
         if (co < L.Nc && ci < L.K)
-            v = src[(int64_t)L.tap_off0 + ty * L.tap_off_sy + tx * L.tap_off_sx + (int64_t)ci * L.stride_k + (int64_t)co * L.stride_n];
+            v = src[adh_wlayout_off(L, ty, tx, ci, co)];
         wp[i] = v;
     }
 }

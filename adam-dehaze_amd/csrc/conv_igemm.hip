@@ -342,13 +342,13 @@ __global__ void pack_weights_kernel(const float* __restrict__ src, const adh_wla
         const int kq = (int)(r % KQ);
         const int tap = (int)(r / KQ);
         const int tyy = tap / L.KWt, txx = tap - tyy * L.KWt;
-        const int toff = L.tap_off0 + tyy * L.tap_off_sy + txx * L.tap_off_sx;
+        const int64_t toff = adh_wlayout_tap_off(L, tyy, txx);
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (n < L.Nc) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int k = kq * 4 + j;
-                if (k < L.K) v[j] = src[(int64_t)toff + (int64_t)k * L.stride_k + (int64_t)n * L.stride_n];
+                if (k < L.K) v[j] = src[toff + (int64_t)k * L.stride_k + (int64_t)n * L.stride_n];
             }
         }
         wp[idx] = v;

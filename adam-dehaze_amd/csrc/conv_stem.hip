@@ -312,7 +312,7 @@ __global__ void pack_weights_stem_kernel(const float* __restrict__ src, const ad
         const int kx = e / 3, c = e - kx * 3;
         float v = 0.f;
         if (e < 21 && n < L.Nc && c < L.K)
-            v = src[(int64_t)L.tap_off0 + ky * L.tap_off_sy + kx * L.tap_off_sx + (int64_t)c * L.stride_k + (int64_t)n * L.stride_n];
+            v = src[adh_wlayout_off(L, ky, kx, c, n)];
         wp[idx] = v;
     }
 }

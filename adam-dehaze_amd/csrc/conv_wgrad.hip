@@ -306,6 +306,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_rows_kernel(const adh_conv_
         wr_prof_buf[bid * 32 + 7] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));   // XCC_ID
     }
 #endif
+    // adh_split_grid_decode (common.h) written out: through the helper hipcc allocates this kernel's registers differently
     const int xcd = bid & 7;
     const int q = bid >> 3;
     const int grp = q % g.ngroups;
@@ -674,7 +675,7 @@ static int wgrad_rows_plan(const adh_conv_desc* d, int nsplit, WrPlan plan[4]) {
 template <int KH, int KW, bool REV, int TN>
 static int launch_wgrad_rows(hipStream_t s, const adh_conv_desc* d, const WrArgs& a, float* slab) {
     const int lds = 2 * (((WR_TH + KH - 1) * WR_HP + TN * WR_TH * 32) * 32 * 4);
-    const int nblocks = ((a.nsplit + 7) / 8) * a.ngroups * 8;
+    const int nblocks = adh_split_grid_blocks(a.nsplit, a.ngroups);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_rows_kernel<KH, KW, REV, TN>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipLaunchKernelGGL((conv_wgrad_rows_kernel<KH, KW, REV, TN>), dim3(nblocks), dim3(256), lds, s, *d, a, slab);
@@ -719,7 +720,7 @@ extern "C" int adh_conv_wgrad_wino(void* stream, const adh_conv_desc* d, float* 
     WrPlan p;
     if (!wgrad_wino_plan(d, nsplit, &p)) return ADH_E_UNSUPPORTED;
     const int lds = 2 * (((WR_TH + 2) * WR_HP + p.TN * WR_TH * 32) * 32 * 4);
-    const int nblocks = ((nsplit + 7) / 8) * p.a.ngroups * 8;
+    const int nblocks = adh_split_grid_blocks(nsplit, p.a.ngroups);
     hipStream_t s = (hipStream_t)stream;
 #define WW_CASE(tn_) \
     if (p.TN == tn_) { \
@@ -731,111 +732,6 @@ extern "C" int adh_conv_wgrad_wino(void* stream, const adh_conv_desc* d, float* 
     WW_CASE(3) WW_CASE(2) WW_CASE(1)
 #undef WW_CASE
     return ADH_E_UNSUPPORTED;
-}
-
-// dst(layout L, 3x3) (+)= G^T (sum over splits of slab[s][16][KP][NcP], with the two deferred signs) G
-__global__ void wgrad_reduce_wino_kernel(const float* __restrict__ slab, int nsplit, int KP, int NcP, const adh_wlayout L,
-                                         float* __restrict__ dst, int accumulate) {
-    const int64_t total = (int64_t)L.K * L.Nc;
-    const int64_t fstride = (int64_t)KP * NcP, split_stride = 16 * fstride;
-    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        const int n = (int)(idx % L.Nc);
-        const int k = (int)(idx / L.Nc);
-        const float* p = slab + (int64_t)k * NcP + n;
-        // 16 frequencies x nsplit partial sums: keep 32-64 independent loads in flight (the inner loops are over
-        // frequencies, the splits advance two at a time) -- with few (k, n) pairs this kernel is latency-bound
-        float ua[16], ub[16];
-#pragma unroll
-        for (int f = 0; f < 16; ++f) ua[f] = ub[f] = 0.f;
-        int sp = 0;
-        for (; sp + 2 <= nsplit; sp += 2) {
-#pragma unroll
-            for (int f = 0; f < 16; ++f) {
-                ua[f] += p[(int64_t)sp * split_stride + f * fstride];
-                ub[f] += p[(int64_t)(sp + 1) * split_stride + f * fstride];
-            }
-        }
-        if (sp < nsplit) {
-#pragma unroll
-            for (int f = 0; f < 16; ++f) ua[f] += p[(int64_t)sp * split_stride + f * fstride];
-        }
-        float u[4][4];
-#pragma unroll
-        for (int f = 0; f < 16; ++f) {
-            const float sign = ((f >> 2) == 3) != ((f & 3) == 3) ? -1.f : 1.f;
-            u[f >> 2][f & 3] = sign * (ua[f] + ub[f]);
-        }
-        // G^T u G with G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
-        float t[3][4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            t[0][b] = u[0][b] + 0.5f * (u[1][b] + u[2][b]);
-            t[1][b] = 0.5f * (u[1][b] - u[2][b]);
-            t[2][b] = 0.5f * (u[1][b] + u[2][b]) + u[3][b];
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            float w[3];
-            w[0] = t[i][0] + 0.5f * (t[i][1] + t[i][2]);
-            w[1] = 0.5f * (t[i][1] - t[i][2]);
-            w[2] = 0.5f * (t[i][1] + t[i][2]) + t[i][3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int64_t off = (int64_t)L.tap_off0 + i * L.tap_off_sy + j * L.tap_off_sx + (int64_t)k * L.stride_k +
-                                    (int64_t)n * L.stride_n;
-                dst[off] = accumulate ? dst[off] + w[j] : w[j];
-            }
-        }
-    }
-}
-
-// slab[0] = sum over splits, in a fixed order (deterministic).  Block = 64 elements (16 bytes each) x 4 split groups: group y
-// adds splits y, y + 4, .. with eight independent loads in flight, the four partial sums meet in LDS.  (One thread per
-// element walking all the splits left the 96-channel layers -- 36,864 elements, 144 blocks -- latency-bound: 42 us.)
-__global__ __launch_bounds__(256) void wgrad_sum_splits_kernel(float* __restrict__ slab, int nsplit, int64_t n4) {
-    __shared__ f32x4 part[3][64];
-    f32x4* s4 = reinterpret_cast<f32x4*>(slab);
-    const int x = threadIdx.x & 63, y = threadIdx.x >> 6;
-    for (int64_t i0 = blockIdx.x * (int64_t)64; i0 < n4; i0 += (int64_t)gridDim.x * 64) {
-        const int64_t i = i0 + x;
-        f32x4 a[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) a[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (i < n4) {
-            int sp = y;
-            for (; sp + 28 < nsplit; sp += 32) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) a[u] += s4[(int64_t)(sp + 4 * u) * n4 + i];
-            }
-            for (; sp < nsplit; sp += 4) a[0] += s4[(int64_t)sp * n4 + i];
-        }
-        const f32x4 t = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-        if (y) part[y - 1][x] = t;
-        __syncthreads();
-        if (y == 0 && i < n4) s4[i] = ((t + part[0][x]) + (part[1][x] + part[2][x]));
-        __syncthreads();
-    }
-}
-
-// shared by the other Winograd-domain reduce entry points (conv_wgrad32.hip, conv_wgrad43.hip)
-void adh_wgrad_sum_splits(hipStream_t s, float* slab, int nsplit, int64_t n4) {
-    hipLaunchKernelGGL(wgrad_sum_splits_kernel, dim3(adh_min_i(adh_ceil_div(n4, 64), 4096)), dim3(256), 0, s, slab, nsplit, n4);
-}
-
-extern "C" int adh_wgrad_reduce_wino(void* stream, float* slab, int nsplit, int KP, int NcP, const adh_wlayout* L,
-                                     float* dst, int accumulate) {
-    if (!slab || !L || !dst || nsplit < 1 || L->KHt != 3 || L->KWt != 3 || (NcP & 3)) return ADH_E_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (nsplit > 1) {
-        // many splits x few (k, n) pairs would leave the transform kernel latency-bound: stream-sum the splits first
-        const int64_t n4 = (int64_t)16 * KP * NcP / 4;
-        adh_wgrad_sum_splits(s, slab, nsplit, n4);
-    }
-    const int64_t total = (int64_t)L->K * L->Nc;
-    hipLaunchKernelGGL(wgrad_reduce_wino_kernel, dim3(adh_min_i(adh_ceil_div(total, 64), 16384)), dim3(64), 0, s, slab, 1,
-                       KP, NcP, *L, dst, accumulate);
-    return adh_check_launch();
 }
 
 extern "C" int adh_conv_wgrad_groups(const adh_conv_desc* d) {
@@ -888,82 +784,4 @@ extern "C" int adh_conv_wgrad(void* stream, const adh_conv_desc* d, float* slab,
     WG_CASE(1, 4) WG_CASE(1, 3) WG_CASE(1, 2) WG_CASE(1, 1)
 #undef WG_CASE
     return ADH_E_UNSUPPORTED;
-}
-
-// dst(layout L) (+)= sum over splits, fixed order
-__global__ void wgrad_reduce_kernel(const float* __restrict__ slab, int nsplit, int KP, int NcP, const adh_wlayout L,
-                                    float* __restrict__ dst, int accumulate) {
-    const int T = L.KHt * L.KWt;
-    const int64_t total = (int64_t)T * L.K * L.Nc;
-    const int64_t split_stride = (int64_t)T * KP * NcP;
-    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        const int n = (int)(idx % L.Nc);
-        int64_t r = idx / L.Nc;
-        const int k = (int)(r % L.K);
-        const int tap = (int)(r / L.K);
-        const float* p = slab + ((int64_t)tap * KP + k) * NcP + n;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int s = 0;
-        for (; s + 4 <= nsplit; s += 4) {
-            s0 += p[(int64_t)(s + 0) * split_stride];
-            s1 += p[(int64_t)(s + 1) * split_stride];
-            s2 += p[(int64_t)(s + 2) * split_stride];
-            s3 += p[(int64_t)(s + 3) * split_stride];
-        }
-        for (; s < nsplit; ++s) s0 += p[(int64_t)s * split_stride];
-        const float sum = (s0 + s1) + (s2 + s3);
-        const int tyy = tap / L.KWt, txx = tap - tyy * L.KWt;
-        const int64_t off = (int64_t)L.tap_off0 + tyy * L.tap_off_sy + txx * L.tap_off_sx + (int64_t)k * L.stride_k +
-                            (int64_t)n * L.stride_n;
-        dst[off] = accumulate ? dst[off] + sum : sum;
-    }
-}
-
-extern "C" int adh_wgrad_reduce(void* stream, const float* slab, int nsplit, int KP, int NcP, const adh_wlayout* L,
-                                float* dst, int accumulate) {
-    if (!slab || !L || !dst || nsplit < 1) return ADH_E_ARG;
-    const int64_t total = (int64_t)L->KHt * L->KWt * L->K * L->Nc;
-    const int blocks = adh_min_i(adh_ceil_div(total, 256), 8192);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, slab, nsplit, KP, NcP, *L,
-                       dst, accumulate);
-    return adh_check_launch();
-}
-
-// Packed small-Cin slabs: slab[s][tap=(ky*KWg+kxg)][i=(kxl*8+ci)][NcP] -> dst OIHW [Cout][Cin][KH][KW]
-__global__ void wgrad_reduce_packed_kernel(const float* __restrict__ slab, int nsplit, int NcP, int Cin, int KH, int KW,
-                                           int Cout, float* __restrict__ dst, int accumulate) {
-    const int KWg = (KW + 3) / 4;
-    const int64_t total = (int64_t)Cout * Cin * KH * KW;
-    const int64_t split_stride = (int64_t)KH * KWg * 32 * NcP;
-    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        const int kx = (int)(idx % KW);
-        int64_t r = idx / KW;
-        const int ky = (int)(r % KH);
-        r /= KH;
-        const int ci = (int)(r % Cin);
-        const int co = (int)(r / Cin);
-        const int tap = ky * KWg + (kx >> 2);
-        const int i = (kx & 3) * 8 + ci;
-        const float* p = slab + ((int64_t)tap * 32 + i) * NcP + co;
-        float s0 = 0.f, s1 = 0.f;
-        int s = 0;
-        for (; s + 2 <= nsplit; s += 2) {
-            s0 += p[(int64_t)s * split_stride];
-            s1 += p[(int64_t)(s + 1) * split_stride];
-        }
-        if (s < nsplit) s0 += p[(int64_t)s * split_stride];
-        const float sum = s0 + s1;
-        dst[idx] = accumulate ? dst[idx] + sum : sum;
-    }
-}
-
-extern "C" int adh_wgrad_reduce_packed(void* stream, const float* slab, int nsplit, int NcP, int Cin, int KH, int KW, int Cout,
-                                       float* dst, int accumulate) {
-    if (!slab || !dst || nsplit < 1 || Cin < 1 || Cin > 8) return ADH_E_ARG;
-    const int64_t total = (int64_t)Cout * Cin * KH * KW;
-    hipLaunchKernelGGL(wgrad_reduce_packed_kernel, dim3(adh_min_i(adh_ceil_div(total, 256), 4096)), dim3(256), 0,
-                       (hipStream_t)stream, slab, nsplit, NcP, Cin, KH, KW, Cout, dst, accumulate);
-    return adh_check_launch();
 }

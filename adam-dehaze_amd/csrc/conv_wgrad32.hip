@@ -76,7 +76,8 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad32_kernel(const adh_conv_des
     const int l31 = lane & 31;
     const int h = lane >> 5;
 
-    // XCD-aware decode (conv_wgrad_rows_kernel): the workgroups that share one pixel range land on one XCD
+    // XCD-aware decode: the workgroups that share one pixel range land on one XCD.  adh_split_grid_decode (common.h) written
+    // out: through the helper hipcc allocates this kernel's registers differently
     const int bid = blockIdx.x;
     const int xcd = bid & 7;
     const int q = bid >> 3;
@@ -465,9 +466,8 @@ __device__ __forceinline__ void h2_workgroup(const adh_conv_desc& d, const Wg32v
     const int cls = g.cblocks > 0 ? (int)blockIdx.x / g.cblocks : g.cls;
     const int bid = (int)blockIdx.x - (g.cblocks > 0 ? cls * g.cblocks : 0);
     const int ymin = g.ymin[cls], xmin = g.xmin[cls];
-    const int q2 = bid >> 3;
-    const int grp = q2 % g.ngroups;
-    const int split = (q2 / g.ngroups) * 8 + (bid & 7);
+    int grp, split;
+    adh_split_grid_decode(bid, g.ngroups, grp, split);
     if (split >= g.nsplit) return;
     float* const rawx = smem;
     float* const rawg = smem + L::RAWX_F;
@@ -823,7 +823,7 @@ extern "C" int adh_conv_wgrad_wino32(void* stream, const adh_conv_desc* d, float
     if (!wgrad32_plan(d, nsplit, &p)) return ADH_E_UNSUPPORTED;
     if (((uintptr_t)d->in & 15) || ((uintptr_t)d->out & 15)) return ADH_E_ARG;
     const int lds = 2 * (G32_XF + p.TN * G32_TH * G32_GROW) * 4;
-    const int nblocks = ((nsplit + 7) / 8) * p.base.ngroups * 8;
+    const int nblocks = adh_split_grid_blocks(nsplit, p.base.ngroups);
     hipStream_t s = (hipStream_t)stream;
     if (p.v2) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad32v2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -865,60 +865,6 @@ extern "C" int adh_conv_wgrad_wino32(void* stream, const adh_conv_desc* d, float
     return ADH_OK;
 }
 
-struct Wg32Taps {
-    int ncls;
-    int tap0[4], tap_sy[4], tap_sx[4], rev[4];
-};
-
-// dst(layout L) (+)= A^T (scaled sum over splits of slab[s][cls][16][KP][NcP]) A per class, scattered to the class's taps.
-// A = [[1,0],[1,1],[1,-1],[0,-1]]; rows / columns 1, 2 of the slab carry the deferred factor 1/2 of G.
-__global__ void wgrad_reduce_wino32_kernel(const float* __restrict__ slab, int nsplit, int KP, int NcP, const adh_wlayout L,
-                                           const Wg32Taps tp, float* __restrict__ dst, int accumulate) {
-    const int64_t total = (int64_t)tp.ncls * L.K * L.Nc;
-    const int64_t fstride = (int64_t)KP * NcP, cls_stride = 16 * fstride, split_stride = tp.ncls * cls_stride;
-    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-        const int n = (int)(idx % L.Nc);
-        int64_t r = idx / L.Nc;
-        const int k = (int)(r % L.K);
-        const int c = (int)(r / L.K);
-        const float* p = slab + c * cls_stride + (int64_t)k * NcP + n;
-        float u[4][4];
-#pragma unroll
-        for (int f = 0; f < 16; ++f) {
-            float s0 = 0.f, s1 = 0.f;
-            int sp = 0;
-            for (; sp + 2 <= nsplit; sp += 2) {
-                s0 += p[(int64_t)sp * split_stride + f * fstride];
-                s1 += p[(int64_t)(sp + 1) * split_stride + f * fstride];
-            }
-            if (sp < nsplit) s0 += p[(int64_t)sp * split_stride + f * fstride];
-            const int a = f >> 2, b = f & 3;
-            const float sc = ((a == 1 || a == 2) ? 0.5f : 1.f) * ((b == 1 || b == 2) ? 0.5f : 1.f);
-            u[a][b] = sc * (s0 + s1);
-        }
-        float t[2][4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            t[0][b] = u[0][b] + u[1][b] + u[2][b];
-            t[1][b] = u[1][b] - u[2][b] - u[3][b];
-        }
-#pragma unroll
-        for (int hy = 0; hy < 2; ++hy) {
-            const float w2[2] = {t[hy][0] + t[hy][1] + t[hy][2], t[hy][1] - t[hy][2] - t[hy][3]};
-#pragma unroll
-            for (int hx = 0; hx < 2; ++hx) {
-                const int ty = tp.rev[c] ? 1 - hy : hy, tx = tp.rev[c] ? 1 - hx : hx;
-                const int tap = tp.tap0[c] + ty * tp.tap_sy[c] + tx * tp.tap_sx[c];
-                const int tyy = tap / L.KWt, txx = tap - tyy * L.KWt;
-                const int64_t off = (int64_t)L.tap_off0 + tyy * L.tap_off_sy + txx * L.tap_off_sx + (int64_t)k * L.stride_k +
-                                    (int64_t)n * L.stride_n;
-                dst[off] = accumulate ? dst[off] + w2[hx] : w2[hx];
-            }
-        }
-    }
-}
-
-
 // The class descriptors of ONE transposed layer (2 x 2-tap forms that differ in out_oy / out_ox and dy0 / dx0 only) as one grid of
 // conv_wgrad32v2_kernel: slab[split][m][16][Cin][NcP], the splits are summed here (into split 0); the caller then runs
 // adh_wgrad_reduce_wino32(slab + m * 16 * Cin * NcP, nsplit = 1, &descs[m], ..) per class.  ADH_E_UNSUPPORTED: launch them one by one.
@@ -942,7 +888,7 @@ extern "C" int adh_conv_wgrad_wino32_multi(void* stream, const adh_conv_desc* de
         a.gofs[m] = ((int64_t)d->out_oy * d->OW + d->out_ox) * d->out_cstride;
     }
     for (int m = n; m < 4; ++m) { a.ymin[m] = a.ymin[0]; a.xmin[m] = a.xmin[0]; a.gofs[m] = a.gofs[0]; }
-    const int nblocks = ((nsplit + 7) / 8) * p0.base.ngroups * 8;
+    const int nblocks = adh_split_grid_blocks(nsplit, p0.base.ngroups);
     a.xps = p0.cls[0].xps;
     a.S = p0.S; a.SX = p0.SX; a.TY = p0.TY; a.nsplit = nsplit; a.ngroups = p0.base.ngroups; a.ncob = p0.ncob;
     a.cls = 0; a.ncls = n; a.cblocks = nblocks;
@@ -957,25 +903,14 @@ extern "C" int adh_conv_wgrad_wino32_multi(void* stream, const adh_conv_desc* de
     return adh_check_launch();
 }
 
-extern "C" int adh_wgrad_reduce_wino32(void* stream, float* slab, int nsplit, const adh_conv_desc* d, int KP, int NcP,
-                                       const adh_wlayout* L, float* dst, int accumulate) {
-    if (!slab || !L || !dst || !d || nsplit < 1 || (NcP & 3)) return ADH_E_ARG;
+// the class taps of `d` for adh_wgrad_reduce_wino32 (conv_wgrad_reduce.hip)
+int adh_wgrad32_class_taps(const adh_conv_desc* d, adh_wg32_taps* tp) {
     Wg32Plan p;
-    if (!wgrad32_plan(d, nsplit, &p)) return ADH_E_UNSUPPORTED;
-    if (L->KHt * L->KWt != d->KH * d->KW) return ADH_E_ARG;
-    Wg32Taps tp;
-    tp.ncls = p.ncls;
+    if (!wgrad32_plan(d, 1, &p)) return 0;
+    tp->ncls = p.ncls;
     for (int c = 0; c < 4; ++c) {
         const Wg32Class& k = p.cls[c < p.ncls ? c : 0];
-        tp.tap0[c] = k.tap0; tp.tap_sy[c] = k.tap_sy; tp.tap_sx[c] = k.tap_sx; tp.rev[c] = k.rev;
+        tp->tap0[c] = k.tap0; tp->tap_sy[c] = k.tap_sy; tp->tap_sx[c] = k.tap_sx; tp->rev[c] = k.rev;
     }
-    hipStream_t s = (hipStream_t)stream;
-    if (nsplit > 1) {
-        const int64_t n4 = (int64_t)p.ncls * 16 * KP * NcP / 4;
-        adh_wgrad_sum_splits(s, slab, nsplit, n4);
-    }
-    const int64_t total = (int64_t)p.ncls * L->K * L->Nc;
-    hipLaunchKernelGGL(wgrad_reduce_wino32_kernel, dim3(adh_min_i(adh_ceil_div(total, 64), 16384)), dim3(64), 0, s, slab, 1, KP,
-                       NcP, *L, tp, dst, accumulate);
-    return adh_check_launch();
+    return 1;
 }

@@ -62,8 +62,6 @@ static_assert((G4_DBG & ~(1 | 4 | 8 | 16 | 32)) == 0, "unknown G4_DBG bit: the a
 #define G4_TAB_F (6 * 64)                         // per-lane global offsets of the six LDS-DMA piece patterns
 #define G4_LDS_BYTES ((G4_RAWX_F + G4_RAWG_F + G4_V_F + G4_TAB_F) * 4)     // 118,272 B
 
-#define G4_A 0.75f
-#define G4_B 1.25f
 #define G4_A2 0.5625f
 #define G4_B2 1.5625f
 #define G4_A2B2 0.87890625f
@@ -276,6 +274,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino43_kernel(const adh_con
                                                                    float* __restrict__ slab) {
     extern __shared__ __attribute__((aligned(16))) float lds[];   // rawx | rawg | V
     const int bid = blockIdx.x;
+    // adh_split_grid_decode (common.h) written out: through the helper hipcc allocates this kernel's registers differently
     const int q2 = bid >> 3;
     const int grp = q2 % g.ngroups;
     const int split = (q2 / g.ngroups) * 8 + (bid & 7);
@@ -634,65 +633,10 @@ extern "C" int adh_conv_wgrad_wino43(void* stream, const adh_conv_desc* d, float
     Wg43Args a;
     if (!wgrad43_plan(d, nsplit, &a)) return ADH_E_UNSUPPORTED;
     if (((uintptr_t)d->in & 15) || ((uintptr_t)d->out & 15)) return ADH_E_ARG;
-    const int nblocks = ((nsplit + 7) / 8) * a.ngroups * 8;
+    const int nblocks = adh_split_grid_blocks(nsplit, a.ngroups);
     hipStream_t s = (hipStream_t)stream;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_wino43_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               160 * 1024);
     hipLaunchKernelGGL(conv_wgrad_wino43_kernel, dim3(nblocks), dim3(256), G4_LDS_BYTES, s, *d, a, slab);
-    return adh_check_launch();
-}
-
-// dst(layout L, 3x3) (+)= A'^T (slab[0][a*6+b] / (N_a N_b)) A'   (slab[0] = sum over splits)
-__global__ void wgrad_reduce_wino43_kernel(const float* __restrict__ slab, int KP, int NcP, const adh_wlayout L,
-                                           float* __restrict__ dst, int accumulate) {
-    const int64_t total = (int64_t)L.K * L.Nc;
-    const int64_t fstride = (int64_t)KP * NcP;
-    const double a = G4_A, b = G4_B;
-    const double n0 = a * a * b * b, na = 2.0 * a * a * (a * a - b * b), nb = 2.0 * b * b * (b * b - a * a);
-    const double inv[6] = {1.0 / n0, 1.0 / na, 1.0 / na, 1.0 / nb, 1.0 / nb, 1.0};
-    const double AT[3][6] = {{1, 1, 1, 1, 1, 0}, {0, a, -a, b, -b, 0}, {0, a * a, a * a, b * b, b * b, 1}};
-    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        const int n = (int)(idx % L.Nc);
-        const int k = (int)(idx / L.Nc);
-        const float* p = slab + (int64_t)k * NcP + n;
-        float u[36];
-#pragma unroll
-        for (int f = 0; f < 36; ++f) u[f] = p[f * fstride];
-        double t[3][6];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int bb = 0; bb < 6; ++bb) {
-                double acc = 0.0;
-#pragma unroll
-                for (int aa = 0; aa < 6; ++aa) acc += AT[i][aa] * inv[aa] * (double)u[aa * 6 + bb];
-                t[i][bb] = acc * inv[bb];
-            }
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                double w = 0.0;
-#pragma unroll
-                for (int bb = 0; bb < 6; ++bb) w += t[i][bb] * AT[j][bb];
-                const int64_t off = (int64_t)L.tap_off0 + i * L.tap_off_sy + j * L.tap_off_sx + (int64_t)k * L.stride_k +
-                                    (int64_t)n * L.stride_n;
-                dst[off] = accumulate ? dst[off] + (float)w : (float)w;
-            }
-    }
-}
-
-extern "C" int adh_wgrad_reduce_wino43(void* stream, float* slab, int nsplit, int KP, int NcP, const adh_wlayout* L,
-                                       float* dst, int accumulate) {
-    if (!slab || !L || !dst || nsplit < 1 || L->KHt != 3 || L->KWt != 3 || (NcP & 3)) return ADH_E_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (nsplit > 1) {
-        const int64_t n4 = (int64_t)36 * KP * NcP / 4;
-        adh_wgrad_sum_splits(s, slab, nsplit, n4);
-    }
-    const int64_t total = (int64_t)L->K * L->Nc;
-    hipLaunchKernelGGL(wgrad_reduce_wino43_kernel, dim3(adh_min_i(adh_ceil_div(total, 64), 16384)), dim3(64), 0, s, slab, KP, NcP,
-                       *L, dst, accumulate);
     return adh_check_launch();
 }

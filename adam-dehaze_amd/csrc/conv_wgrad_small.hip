@@ -272,38 +272,3 @@ extern "C" int adh_conv_wgrad_small(void* stream, const adh_conv_desc* d, float*
 #undef SMALL_LAUNCH
     return adh_check_launch();
 }
-
-// dst(layout L) (+)= sum over slabs[s][tap][k][n]: one wave per output element (few outputs, hundreds of slabs: the
-// thread-per-output reduce of conv_wgrad.hip would run one long dependent chain per thread)
-__global__ __launch_bounds__(256) void wgrad_reduce_wave_kernel(const float* __restrict__ slab, int nslabs, int KP, int NcP,
-                                                                const adh_wlayout L, float* __restrict__ dst, int accumulate) {
-    const int T = L.KHt * L.KWt;
-    const int64_t total = (int64_t)T * L.K * L.Nc;
-    const int64_t split_stride = (int64_t)T * KP * NcP;
-    const int lane = threadIdx.x & 63;
-    for (int64_t idx = blockIdx.x * 4 + (threadIdx.x >> 6); idx < total; idx += (int64_t)gridDim.x * 4) {
-        const int n = (int)(idx % L.Nc);
-        int64_t r = idx / L.Nc;
-        const int k = (int)(r % L.K);
-        const int tap = (int)(r / L.K);
-        const float* p = slab + ((int64_t)tap * KP + k) * NcP + n;
-        float s = 0.f;
-        for (int i = lane; i < nslabs; i += 64) s += p[(int64_t)i * split_stride];
-        s = wave_sum(s);
-        if (lane == 0) {
-            const int tyy = tap / L.KWt, txx = tap - tyy * L.KWt;
-            const int64_t off = (int64_t)L.tap_off0 + tyy * L.tap_off_sy + txx * L.tap_off_sx + (int64_t)k * L.stride_k +
-                                (int64_t)n * L.stride_n;
-            dst[off] = accumulate ? dst[off] + s : s;
-        }
-    }
-}
-
-extern "C" int adh_wgrad_reduce_small(void* stream, const float* slab, int nslabs, int KP, int NcP, const adh_wlayout* L,
-                                      float* dst, int accumulate) {
-    if (!slab || !L || !dst || nslabs < 1) return ADH_E_ARG;
-    const int64_t total = (int64_t)L->KHt * L->KWt * L->K * L->Nc;
-    hipLaunchKernelGGL(wgrad_reduce_wave_kernel, dim3(adh_min_i(adh_ceil_div(total, 4), 4096)), dim3(256), 0, (hipStream_t)stream,
-                       slab, nslabs, KP, NcP, *L, dst, accumulate);
-    return adh_check_launch();
-}

@@ -1353,8 +1353,7 @@ __global__ void pack_weights_wino32_kernel(const float* __restrict__ src, const 
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
                     for (int b = 0; b < 2; ++b)
-                        gg[a][b] = src[(int64_t)L.tap_off0 + (a * cstep + cy) * L.tap_off_sy + (b * cstep + cx) * L.tap_off_sx +
-                                       (int64_t)k * L.stride_k + (int64_t)n * L.stride_n];
+                        gg[a][b] = src[adh_wlayout_off(L, a * cstep + cy, b * cstep + cx, k, n)];
                 float tt[4][2];   // A g
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
@@ -1416,8 +1415,7 @@ __global__ void pack_weights_wino32_bf16x3_kernel(const float* __restrict__ src,
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
                     gg[a][b] = (n < L.Nc && k < L.K)
-                                   ? src[(int64_t)L.tap_off0 + (a * cstep + cy) * L.tap_off_sy + (b * cstep + cx) * L.tap_off_sx +
-                                         (int64_t)k * L.stride_k + (int64_t)n * L.stride_n]
+                                   ? src[adh_wlayout_off(L, a * cstep + cy, b * cstep + cx, k, n)]
                                    : 0.f;
             float tt[4][2];   // A g
 #pragma unroll
@@ -1491,8 +1489,7 @@ __global__ void pack_weights_wino_kernel(const float* __restrict__ src, const ad
                 for (int a = 0; a < 3; ++a)
 #pragma unroll
                     for (int b = 0; b < 3; ++b)
-                        gg[a][b] = src[(int64_t)L.tap_off0 + a * L.tap_off_sy + b * L.tap_off_sx + (int64_t)k * L.stride_k +
-                                       (int64_t)n * L.stride_n];
+                        gg[a][b] = src[adh_wlayout_off(L, a, b, k, n)];
                 float tt[4][3];   // G g
 #pragma unroll
                 for (int b = 0; b < 3; ++b) {

@@ -155,10 +155,10 @@ _SLAB_BUDGET = 1 << 30      # bytes of split-accumulation slab a weight-gradient
 
 def _rows_nsplit(groups: int, ntiles: int, cus: int = 256, max_rounds: int = 4, max_splits: Optional[int] = None,
                  slab_bytes: int = 0, tile_us: float = 5.0, launches: int = 1) -> int:
-    """Pixel splits for the split-accumulating weight-gradient kernels.  One workgroup is resident per CU and the hardware deals
-    workgroups to the 8 XCDs round-robin (block b runs on XCD b % 8, 32 CUs each); every such kernel maps block b to
-    (group, split) = ((b >> 3) % groups, (b >> 3) / groups * 8 + (b & 7)), i.e. XCD x gets the splits = x mod 8 of every
-    group.  A launch therefore takes rounds = ceil(groups * ceil(nsplit / 8) / 32) workgroup times of ceil(ntiles / nsplit)
+    """Pixel splits for the split-accumulating weight-gradient kernels.  One workgroup is resident per CU and every such kernel
+    maps its blocks to (group, split) so that XCD x (32 CUs) gets the splits = x mod 8 of every group (csrc/common.h,
+    adh_split_grid_blocks / adh_split_grid_decode: the mapping and why).  A launch therefore takes
+    rounds = ceil(groups * ceil(nsplit / 8) / 32) workgroup times of ceil(ntiles / nsplit)
     tiles each -- NOT ceil(groups * nsplit / 256): groups = 3, nsplit = 85 is 255 workgroups but 33 on each of XCDs 0-4, two
     rounds (measured: Conv2d k4 s2 96 -> 192 weight gradient 5.92 ms with 85 splits, 3.69 with 80).  Every split also writes
     `slab_bytes` of partial sums that the reduce kernel reads back (80 -> 160 splits on the same layer: 3.69 -> 3.78 ms although

@@ -2,7 +2,8 @@
 // static __shared__ arrays and __syncthreads() be compiled by a host C++ compiler and run on CPU threads -- one OS thread per
 // GPU thread, a pthread barrier for __syncthreads(), the workgroups of a launch one after the other.  The point is to run the
 // kernel's own index arithmetic under the host sanitizers (-fsanitize=address,undefined) and against float64 without a GPU;
-// it says nothing about speed.  Used by tests/test_ssim_loss_hostemu_cpu.py on a copy of csrc/ssim_loss.hip.
+// it says nothing about speed.  Used by tests/test_ssim_loss_hostemu_cpu.py on a copy of csrc/ssim_loss.hip and, with
+// -DADH_HOST_EMU (the section at the end), by tests/test_wgrad_reduce_hostemu_cpu.py on a copy of csrc/conv_wgrad_reduce.hip.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -32,3 +33,30 @@ static inline int adh_check_launch() { return ADH_OK; }
 static inline int adh_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 void emu_launch(dim3 grid, dim3 block, std::function<void()> fn);
 #define hipLaunchKernelGGL(k, grid, block, shmem, stream, ...) emu_launch(grid, block, [&]() { k(__VA_ARGS__); })
+
+#ifdef ADH_HOST_EMU
+// What csrc/conv_wgrad_reduce.hip takes from csrc/common.h beyond the above: the public structs, the grid-stride loop's
+// blockDim, float4 arithmetic, and the helpers and internal declarations it shares with the other source files (copies of
+// csrc/common.h's: keep them the same).  Its one-wave-per-element kernel needs cross-lane shuffles and is compiled out.
+#include "adam_dehaze_hip.h"   // include/, on the include path
+#define __host__
+#define __device__
+#define __forceinline__ inline
+extern dim3 blockDim;
+typedef float f32x4 __attribute__((vector_size(16)));
+static inline int adh_min_i(int a, int b) { return a < b ? a : b; }
+static inline int64_t adh_wlayout_tap_off(const adh_wlayout& L, int ty, int tx) {
+    return (int64_t)L.tap_off0 + ty * L.tap_off_sy + tx * L.tap_off_sx;
+}
+static inline int64_t adh_wlayout_off(const adh_wlayout& L, int ty, int tx, int k, int n) {
+    return adh_wlayout_tap_off(L, ty, tx) + (int64_t)k * L.stride_k + (int64_t)n * L.stride_n;
+}
+#define G4_A 0.75f
+#define G4_B 1.25f
+void adh_wgrad_sum_splits(hipStream_t s, float* slab, int nsplit, int64_t n4);
+struct adh_wg32_taps {
+    int ncls;
+    int tap0[4], tap_sy[4], tap_sx[4], rev[4];
+};
+int adh_wgrad32_class_taps(const adh_conv_desc* d, adh_wg32_taps* tp);
+#endif
