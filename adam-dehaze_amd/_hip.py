@@ -48,6 +48,12 @@ class AdamTensor(C.Structure):
     _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("n", i64), ("step", i32), ("repeats", i32)]
 
 
+class GradCtrl(C.Structure):
+    """struct adh_grad_ctrl: the device-resident control block of the gradient guard."""
+    _fields_ = [("sumsq", f64), ("norm", f32), ("gscale_eff", f32), ("finite", i32), ("skipped", i32),
+                ("skipped_total", i32), ("reserved", i32)]
+
+
 class WLayout(C.Structure):
     """struct adh_wlayout."""
     _fields_ = [
@@ -185,6 +191,9 @@ _SIGNATURES = {
     "adh_augment_num_blocks": [i64],
     "adh_paired_augment": [vp, vp, vp, i32, i32, i32, vp, i32, vp],
     "adh_adam_multi": [vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, i32, i32, i32],
+    "adh_grad_sumsq": [vp, vp, vp, i32, f32, vp],
+    "adh_grad_guard_finalize": [vp, vp, i32, f32, f64, i32, vp],
+    "adh_adam_multi_guarded": [vp, vp, vp, i32, f32, f32, f32, f32, f32, i32, i32, i32, vp],
     "adh_apply_fog": [vp, vp, vp, vp, i32, i32, i32, vp],
     "adh_psnr_num_blocks": [i64],
     "adh_psnr": [vp, vp, vp, i32, i64, f32, vp, i32, vp, vp],

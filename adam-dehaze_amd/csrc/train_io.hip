@@ -38,10 +38,18 @@ __device__ __forceinline__ void adam_elem(float& pv, float gv0, float& mv, float
 
 #define ADAM_MAX_REPEATS 4
 
+// GUARDED (adh_adam_multi_guarded): gscale, the skip decision and the number of skipped calls come from the control block that
+// grad_guard_finalize_kernel wrote earlier on the stream (uniform loads: every lane reads the same address).
+template <bool GUARDED>
 __global__ __launch_bounds__(256) void adam_multi_kernel(const adh_adam_tensor* __restrict__ table,
                                                          const int32_t* __restrict__ chunks, float lr, float beta1,
                                                          float beta2, float eps, float wd, float gscale, int dup_mode,
-                                                         int calls_since_upload) {
+                                                         int calls_since_upload, const adh_grad_ctrl* __restrict__ ctrl) {
+    if (GUARDED) {
+        if (ctrl->finite == 0) return;               // a skipped step leaves p, m and v alone
+        gscale = ctrl->gscale_eff;
+        calls_since_upload -= ctrl->skipped;         // ... and consumes no bias-correction step
+    }
     const int ti = chunks[2 * blockIdx.x], ci = chunks[2 * blockIdx.x + 1];
     adh_adam_tensor t = table[ti];
     t.step += calls_since_upload * t.repeats;   // the table stays resident: every call advances a tensor by `repeats`
@@ -89,8 +97,107 @@ extern "C" int adh_adam_multi(void* stream, const adh_adam_tensor* table_dev, co
     if (!table_dev || !chunks_dev || nchunks < 1 || max_repeats < 1 || max_repeats > ADAM_MAX_REPEATS ||
         (dup_mode != 0 && dup_mode != 1) || calls_since_upload < 0)
         return ADH_E_ARG;
-    hipLaunchKernelGGL(adam_multi_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev, chunks_dev, lr, beta1,
-                       beta2, eps, weight_decay, grad_scale, dup_mode, calls_since_upload);
+    hipLaunchKernelGGL(adam_multi_kernel<false>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev, chunks_dev, lr,
+                       beta1, beta2, eps, weight_decay, grad_scale, dup_mode, calls_since_upload, (const adh_grad_ctrl*)nullptr);
+    return adh_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------
+// global-norm clipping and the non-finite-step guard around the Adam launch (torch.nn.utils.clip_grad_norm_'s formula; the
+// reference trains without either).  Three launches on one stream, no host read: per-chunk float64 partials of
+// sum (g * grad_scale)^2 over the Adam table, one workgroup that folds them into the control block, and the guarded Adam.
+// The extra HBM traffic is one read of g (4 B per parameter on top of Adam's 28).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const adh_adam_tensor* __restrict__ table,
+                                                         const int32_t* __restrict__ chunks, float gscale,
+                                                         double* __restrict__ partial) {
+    const int ti = chunks[2 * blockIdx.x], ci = chunks[2 * blockIdx.x + 1];
+    const int64_t tn = table[ti].n;
+    const int64_t base = (int64_t)ci * ADAM_CHUNK;
+    const int n = (int)((tn - base) < ADAM_CHUNK ? (tn - base) : ADAM_CHUNK);
+    const float* __restrict__ g = table[ti].g + base;
+    const double gs = (double)gscale;
+    double acc = 0.0;
+    const bool vec = (((uintptr_t)g) & 15) == 0;
+    const int n4 = vec ? (n >> 2) : 0;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+        const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double d = (double)gv[j] * gs;
+            acc += d * d;
+        }
+    }
+    for (int i = n4 * 4 + threadIdx.x; i < n; i += 256) {
+        const double d = (double)g[i] * gs;
+        acc += d * d;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    __shared__ double s[4];
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// one workgroup: thread t adds its run of consecutive partials in index order, thread 0 adds the 256 runs in index order
+__global__ __launch_bounds__(256) void grad_guard_finalize_kernel(const double* __restrict__ partial, int nchunks, float gscale,
+                                                                  double max_norm, int skip_nonfinite,
+                                                                  adh_grad_ctrl* __restrict__ ctrl) {
+    __shared__ double s[256];
+    const int per = (nchunks + 255) / 256;
+    const int lo = threadIdx.x * per, hi = lo + per < nchunks ? lo + per : nchunks;
+    double acc = 0.0;
+    for (int i = lo; i < hi; ++i) acc += partial[i];
+    s[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double sumsq = 0.0;
+    for (int i = 0; i < 256; ++i) sumsq += s[i];
+    const double norm = sqrt(sumsq);
+    const bool finite = isfinite(sumsq);
+    float gscale_eff = gscale;
+    if (finite && max_norm > 0.0 && isfinite(max_norm)) {
+        const double coef = max_norm / (norm + 1e-6);
+        if (coef < 1.0) gscale_eff = (float)((double)gscale * coef);
+    }
+    const bool skip = !finite && skip_nonfinite != 0;
+    ctrl->sumsq = sumsq;
+    ctrl->norm = (float)norm;
+    ctrl->gscale_eff = gscale_eff;
+    ctrl->finite = skip ? 0 : 1;
+    if (skip) {
+        ctrl->skipped += 1;
+        ctrl->skipped_total += 1;
+    }
+}
+
+extern "C" int adh_grad_sumsq(void* stream, const adh_adam_tensor* table_dev, const int32_t* chunks_dev, int nchunks,
+                              float grad_scale, double* partials_dev) {
+    if (!table_dev || !chunks_dev || !partials_dev || nchunks < 1) return ADH_E_ARG;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev, chunks_dev, grad_scale,
+                       partials_dev);
+    return adh_check_launch();
+}
+
+extern "C" int adh_grad_guard_finalize(void* stream, const double* partials_dev, int nchunks, float grad_scale, double max_norm,
+                                       int skip_nonfinite, void* ctrl_dev) {
+    if (!partials_dev || !ctrl_dev || nchunks < 1 || (skip_nonfinite != 0 && skip_nonfinite != 1) ||
+        (((uintptr_t)ctrl_dev) & 7) != 0)
+        return ADH_E_ARG;
+    hipLaunchKernelGGL(grad_guard_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials_dev, nchunks, grad_scale,
+                       max_norm, skip_nonfinite, (adh_grad_ctrl*)ctrl_dev);
+    return adh_check_launch();
+}
+
+extern "C" int adh_adam_multi_guarded(void* stream, const adh_adam_tensor* table_dev, const int32_t* chunks_dev, int nchunks,
+                                      float lr, float beta1, float beta2, float eps, float weight_decay, int dup_mode,
+                                      int max_repeats, int calls_since_upload, const void* ctrl_dev) {
+    if (!table_dev || !chunks_dev || !ctrl_dev || nchunks < 1 || max_repeats < 1 || max_repeats > ADAM_MAX_REPEATS ||
+        (dup_mode != 0 && dup_mode != 1) || calls_since_upload < 0 || (((uintptr_t)ctrl_dev) & 7) != 0)
+        return ADH_E_ARG;
+    hipLaunchKernelGGL(adam_multi_kernel<true>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev, chunks_dev, lr, beta1,
+                       beta2, eps, weight_decay, 0.f, dup_mode, calls_since_upload, (const adh_grad_ctrl*)ctrl_dev);
     return adh_check_launch();
 }
 

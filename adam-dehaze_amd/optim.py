@@ -18,10 +18,27 @@ weight decay is torch's L2 form (added to the gradient).  One kernel launch upda
 (`adh_adam_multi`); `state_dict()` / `load_state_dict()` use torch.optim.Adam's layout (duplicates share
 the index of their last occurrence, as torch packs them) so checkpoints written by either side load in
 the other (train_joint.py:280, train_dehazing.py:199).
+
+Gradient guard (opt-in: `max_grad_norm`, `skip_nonfinite`; with both at their defaults `step()` issues exactly the one
+`adh_adam_multi` launch).  With either set a step is three launches on the current stream -- `adh_grad_sumsq`,
+`adh_grad_guard_finalize`, `adh_adam_multi_guarded` -- around a 32-byte control block on the device, and never reads back:
+
+* The norm is the L2 norm over the UNIQUE tensors with `grad_scale` applied: a parameter the reference lists twice is
+  counted once (torch's clip_grad_norm_ over that list would count it twice and scale it twice), and under data parallelism
+  it is the norm of the averaged gradient.  The coefficient is torch's, min(1, max_norm / (norm + 1e-6)), folded into the
+  scalar the Adam kernel multiplies every gradient by; `max_grad_norm` 0 or inf measures without clipping.
+* After `GradientSynchronizer.finish()` every rank holds the same gradient, so every rank computes the same coefficient and
+  the same skip decision: no collective is added.  A NaN on one rank reaches all ranks through the all-reduce.
+* `skip_nonfinite`: a step whose squared norm is inf or NaN leaves p, m and v untouched and consumes no bias-correction
+  step.  The host counts steps optimistically; `_reconcile()` (from `state_dict()` and before a table re-upload) reads the
+  device's skip counter and takes the skipped steps back, so checkpoints carry the step counts the kernel used.
+* `last_grad_norm` is a 0-d device view of the block's `norm` (accumulate it on the device); `skipped_steps()` is the one
+  explicit device-to-host read.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, Iterable, List, Optional
 
 import numpy as np
@@ -32,9 +49,21 @@ from . import _hip as H
 
 class Adam:
     def __init__(self, params: Iterable[torch.Tensor], lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 duplicates: str = "sequential"):
+                 duplicates: str = "sequential", max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         if duplicates not in ("sequential", "foreach"):
             raise ValueError(f"duplicates must be 'sequential' or 'foreach', got {duplicates!r}")
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if math.isnan(max_grad_norm) or max_grad_norm < 0:
+                raise ValueError(f"max_grad_norm must be >= 0 (0 or inf: measure only), got {max_grad_norm!r}")
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
+        self.guarded = max_grad_norm is not None or self.skip_nonfinite
+        self._ctrl = None             # struct adh_grad_ctrl on the device (uint8[32]), allocated by the first guarded step
+        self._partials = None         # one float64 per (tensor, chunk)
+        self._guarded_calls = 0       # guarded launches since the skip counter was last read: 0 = nothing to reconcile
+        self.last_grad_norm: Optional[torch.Tensor] = None     # 0-d device views of the block: norm of the last step ...
+        self.skipped_total: Optional[torch.Tensor] = None      # ... and the count skipped_steps() reads
+        self.step_hook = None         # called after every guarded step (the epoch loop accumulates last_grad_norm there)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.duplicates = duplicates
         self.params: List[torch.Tensor] = []
@@ -59,6 +88,7 @@ class Adam:
         self._nchunks = 0
         self._calls_since_upload = 0
         self._table_host = None
+        self._table_ids = set()       # id(p) of the tensors in the resident table
 
     def zero_grad(self, set_to_none: bool = True):
         for p in self.params:
@@ -92,10 +122,12 @@ class Adam:
         # optimiser step a host-device sync).  The step counters advance on the device side of the ABI: the kernel adds
         # `calls_since_upload * repeats` to the uploaded value.  An upload goes through a pinned staging buffer and is
         # asynchronous on the current stream.
-        since = self._calls_since_upload
-        key = tuple((p.data_ptr(), g.data_ptr(), st["m"].data_ptr(), st["v"].data_ptr(), p.numel(), self.repeats[id(p)],
-                     st["step"] - since * self.repeats[id(p)])        # the step the resident table was uploaded with
-                    for p, g, st in live)
+        if self.guarded and self._ctrl is None:
+            self._ctrl = torch.zeros(C.sizeof(H.GradCtrl), dtype=torch.uint8, device=dev)
+            self.last_grad_norm, self.skipped_total = self._ctrl_field("norm"), self._ctrl_field("skipped_total")
+        key = self._live_key(live)
+        if key != self._table_key and self._reconcile():
+            key = self._live_key(live)                   # the skipped steps came off the host's counts
         if key != self._table_key:
             chunk = H.value("adh_adam_chunk_elems")
             table = (H.AdamTensor * len(live))()
@@ -106,7 +138,9 @@ class Adam:
             chunks = np.array([(i, c) for i, (p, _, _) in enumerate(live) for c in range((p.numel() + chunk - 1) // chunk)],
                               dtype=np.int32).reshape(-1)
             raw = np.frombuffer(bytes(table), dtype=np.uint8)
-            host = torch.empty(raw.size + chunks.size * 4, dtype=torch.uint8).pin_memory()
+            host = torch.empty(raw.size + chunks.size * 4, dtype=torch.uint8)
+            if dev.type == "cuda":
+                host = host.pin_memory()
             host[:raw.size].copy_(torch.from_numpy(raw.copy()))
             host[raw.size:].copy_(torch.from_numpy(chunks.view(np.uint8).copy()))
             both = host.to(dev, non_blocking=True)
@@ -114,18 +148,69 @@ class Adam:
             self._table_dev, self._chunks_dev = both[:raw.size], both[raw.size:]
             self._nchunks = chunks.size // 2
             self._calls_since_upload = 0
-            self._table_key = tuple(k[:6] + (st["step"],) for k, (_, _, st) in zip(key, live))
-        H.call("adh_adam_multi", self._table_dev.data_ptr(), self._chunks_dev.data_ptr(), self._nchunks, lr, self.betas[0],
-               self.betas[1], self.eps, self.weight_decay, self.grad_scale, 1 if self.duplicates == "foreach" else 0,
-               max(self.repeats[id(p)] for p, _, _ in live), self._calls_since_upload)
+            self._table_key = self._live_key(live)
+            self._table_ids = {id(p) for p, _, _ in live}
+            if self.guarded and (self._partials is None or self._partials.numel() != self._nchunks):
+                self._partials = torch.zeros(self._nchunks, dtype=torch.float64, device=dev)
+        dup_mode, max_repeats = 1 if self.duplicates == "foreach" else 0, max(self.repeats[id(p)] for p, _, _ in live)
+        if self.guarded:
+            H.call("adh_grad_sumsq", self._table_dev.data_ptr(), self._chunks_dev.data_ptr(), self._nchunks, self.grad_scale,
+                   self._partials.data_ptr())
+            H.call("adh_grad_guard_finalize", self._partials.data_ptr(), self._nchunks, self.grad_scale,
+                   0.0 if self.max_grad_norm is None else self.max_grad_norm, int(self.skip_nonfinite), self._ctrl.data_ptr())
+            H.call("adh_adam_multi_guarded", self._table_dev.data_ptr(), self._chunks_dev.data_ptr(), self._nchunks, lr,
+                   self.betas[0], self.betas[1], self.eps, self.weight_decay, dup_mode, max_repeats, self._calls_since_upload,
+                   self._ctrl.data_ptr())
+            self._guarded_calls += 1
+        else:
+            H.call("adh_adam_multi", self._table_dev.data_ptr(), self._chunks_dev.data_ptr(), self._nchunks, lr, self.betas[0],
+                   self.betas[1], self.eps, self.weight_decay, self.grad_scale, dup_mode, max_repeats, self._calls_since_upload)
         self._calls_since_upload += 1
         for p, _, st in live:
             st["step"] += self.repeats[id(p)]
         from .engine import invalidate_weight_cache   # the kernel wrote the parameters behind torch's version counter
         invalidate_weight_cache()
+        if self.guarded and self.step_hook is not None:
+            self.step_hook()
+
+    def _live_key(self, live):
+        """(pointers, size, repeats, the step the resident table was -- or would now be -- uploaded with) per live tensor"""
+        since = self._calls_since_upload
+        return tuple((p.data_ptr(), g.data_ptr(), st["m"].data_ptr(), st["v"].data_ptr(), p.numel(), self.repeats[id(p)],
+                      st["step"] - since * self.repeats[id(p)]) for p, g, st in live)
+
+    # ------------------------------------------------------------------ gradient guard
+    def _ctrl_field(self, name: str) -> torch.Tensor:
+        """0-d device view of one field of the control block"""
+        f = getattr(H.GradCtrl, name)
+        dtype = {"sumsq": torch.float64, "norm": torch.float32, "gscale_eff": torch.float32}.get(name, torch.int32)
+        return self._ctrl[f.offset:f.offset + f.size].view(dtype).reshape(())
+
+    def skipped_steps(self) -> int:
+        """Steps skipped for a non-finite gradient since construction / load_state_dict (a device-to-host read)."""
+        return 0 if self._ctrl is None else int(self.skipped_total.item())
+
+    def _reconcile(self) -> bool:
+        """Take the steps the device skipped since the last table upload back off the host's optimistic counts, zero the
+        device counter and force a re-upload.  Reads the device only when a guarded launch has run since the last time.
+        Returns whether a count changed."""
+        if self._ctrl is None or self._guarded_calls == 0:
+            return False
+        self._guarded_calls = 0
+        skipped = int(self._ctrl_field("skipped").item())
+        if skipped == 0:
+            return False
+        for p in self.params:
+            if id(p) in self._table_ids:      # only the resident table's tensors were advanced optimistically
+                self.state[id(p)]["step"] -= skipped * self.repeats[id(p)]
+        self._ctrl_field("skipped").zero_()
+        self._table_key = None
+        self._calls_since_upload = 0
+        return True
 
     # ------------------------------------------------------------------ torch.optim.Adam-compatible (de)serialisation
     def state_dict(self) -> dict:
+        self._reconcile()
         index: Dict[int, int] = {}
         for i, p in enumerate(self._listed):
             index[id(p)] = i          # torch packs a duplicated parameter under the index of its LAST occurrence
@@ -161,3 +246,7 @@ class Adam:
                                  "m": st["exp_avg"].to(device=p.device, dtype=torch.float32).clone().contiguous(),
                                  "v": st["exp_avg_sq"].to(device=p.device, dtype=torch.float32).clone().contiguous()}
         self._table_key = None
+        self._calls_since_upload = 0
+        self._guarded_calls = 0
+        if self._ctrl is not None:
+            self._ctrl.zero_()

@@ -92,6 +92,56 @@ def load_pretrained_model(model, checkpoint_path):
     return False
 
 
+def optim_guard_options(config) -> Dict:
+    """The optional `optim:` section of the config as optim.Adam keyword arguments ({} when it is absent: the plain step)."""
+    section = config.get("optim") or {}
+    unknown = set(section) - {"grad_clip_norm", "skip_nonfinite"}
+    if unknown:
+        raise ValueError(f"config optim: unknown keys {sorted(unknown)} (grad_clip_norm, skip_nonfinite)")
+    opts = {}
+    if section.get("grad_clip_norm") is not None:
+        opts["max_grad_norm"] = float(section["grad_clip_norm"])
+    if section.get("skip_nonfinite"):
+        opts["skip_nonfinite"] = True
+    return opts
+
+
+class _GuardStats:
+    """Mean and max of a guarded optimiser's `last_grad_norm` over an epoch's steps, accumulated on the device from the
+    optimiser's step hook; `read()` is the epoch's one read-back (norm sum, max, count and the skip count in one vector).  Inert for
+    an unguarded optimiser: no hook, `read()` returns {}."""
+
+    def __init__(self, optimizer):
+        self.opt = optimizer if getattr(optimizer, "guarded", False) else None
+        self.acc, self.skipped_before = None, 0
+        if self.opt is not None:
+            self.opt.step_hook = self.add
+
+    def add(self):
+        norm = self.opt.last_grad_norm
+        if self.acc is None:
+            self.acc = torch.zeros(3, device=norm.device)      # sum, max, number of finite norms
+        # a non-finite norm (a skipped step) shows in the skip count, not in the mean and the max
+        finite = torch.isfinite(norm)
+        val = torch.where(finite, norm, torch.zeros_like(norm))
+        self.acc[0] += val
+        self.acc[1] = torch.maximum(self.acc[1], val)
+        self.acc[2] += finite
+
+    def read(self) -> Dict:
+        if self.acc is None:
+            return {}
+        total, peak, count, skipped = torch.cat([self.acc.double(), self.opt.skipped_total.double().view(1)]).tolist()
+        out = {"grad_norm_mean": total / max(1.0, count), "grad_norm_max": peak,
+               "skipped_steps": int(skipped) - self.skipped_before}
+        self.acc, self.skipped_before = None, int(skipped)
+        return out
+
+    def close(self):
+        if self.opt is not None:
+            self.opt.step_hook = None
+
+
 def build_joint_system(config, world_size: int = 1, adam_duplicates: str = "sequential") -> Dict:
     device = torch.device(config["device"])
     classifier = create_classifier(config)
@@ -107,7 +157,8 @@ def build_joint_system(config, world_size: int = 1, adam_duplicates: str = "sequ
     params = list(router.parameters())
     for m in models.values():
         params.extend(list(m.parameters()))
-    optimizer = Adam(params, lr=config["joint_training"]["learning_rate"], weight_decay=0.0001, duplicates=adam_duplicates)
+    optimizer = Adam(params, lr=config["joint_training"]["learning_rate"], weight_decay=0.0001, duplicates=adam_duplicates,
+                     **optim_guard_options(config))
     scheduler = ReduceLROnPlateau(optimizer, mode="min", factor=0.5, patience=3)
     criterion = get_joint_loss(config).to(device)
     sync = None
@@ -434,22 +485,30 @@ def _run_epochs(first_epoch: int, epochs: int, train_epoch, validate, scheduler,
                 score_text: str, ck_dir: str, checkpoint, report, sync=None, modules=(), device=None):
     """The epoch loop of the three training stages: the one statement of what the ranks do in which order.  The stage plugs
     in `train_epoch(epoch)`, `validate() -> dict`, `checkpoint(epoch, val) -> dict` and `report(epoch, train_loss, val)`.
-    Returns the per-epoch records {"epoch", "train_loss", **val, "lr"}."""
+    Returns the per-epoch records {"epoch", "train_loss", **val, "lr"}; with the `optim:` guard on they also carry
+    "grad_norm_mean", "grad_norm_max" and "skipped_steps" of the epoch (this rank's; after the all-reduce every rank sees the
+    same gradient)."""
     rank = _world_rank()[1]
     history = []
+    guard = _GuardStats(scheduler.opt)
     if rank == 0:
         os.makedirs(ck_dir, exist_ok=True)
     for epoch in range(first_epoch, epochs):
         # None, or this rank's mean train loss where the stage reports the rank-averaged one (the joint stage)
         train_loss = train_epoch(epoch)
+        guard_stats = guard.read()
         _sync_buffers_from_rank0(sync, *modules)      # validation and rank 0's checkpoint see one model
         val = validate()                              # every rank enters its all-reduce, also one with nothing to validate
         if train_loss is not None:
             train_loss = all_reduce_mean_scalar(train_loss, device)
         scheduler.step(val[loss_key])                 # every rank steps on the same (rank-averaged) value
-        history.append({"epoch": epoch, "train_loss": train_loss, **val, "lr": scheduler.opt.param_groups[0]["lr"]})
+        history.append({"epoch": epoch, "train_loss": train_loss, **val, "lr": scheduler.opt.param_groups[0]["lr"],
+                        **guard_stats})
         if rank == 0:
             report(epoch, train_loss, val)
+            if guard_stats:
+                print("  Grad norm: mean {grad_norm_mean:.4f}, max {grad_norm_max:.4f}; skipped steps: {skipped_steps}"
+                      .format(**guard_stats))
             if val[score_key] > best:
                 save_checkpoint_atomic(checkpoint(epoch, val), os.path.join(ck_dir, "best_model.pth"))
                 print("Saved best model with validation " + score_text.format(val[score_key]))
@@ -458,6 +517,7 @@ def _run_epochs(first_epoch: int, epochs: int, train_epoch, validate, scheduler,
         best = max(best, val[score_key])
         # nobody runs ahead (into the next stage's load_pretrained_model, a --resume) while rank 0 is still writing
         _barrier()
+    guard.close()
     return history
 
 
@@ -522,7 +582,8 @@ def train_dehazing_model(config, intensity_level: str, train_loader=None, val_lo
                "high": create_high_intensity_model}[intensity_level]
     model = (factory(config) if model is None else model).to(device).train()
     criterion = get_dehazing_loss(config).to(device)
-    optimizer = Adam(model.parameters(), lr=config["dehazing"][intensity_level]["learning_rate"], weight_decay=1e-4)
+    optimizer = Adam(model.parameters(), lr=config["dehazing"][intensity_level]["learning_rate"], weight_decay=1e-4,
+                     **optim_guard_options(config))
     scheduler = ReduceLROnPlateau(optimizer, mode="min", factor=0.5, patience=5)
     level = LEVELS[intensity_level]
     ck_dir = os.path.join(config["dehazing"]["checkpoint_dir"], intensity_level)
@@ -912,7 +973,8 @@ def train_classifier(config, train_loader=None, val_loader=None, steps: int = 4,
     device = torch.device(config["device"])
     cc = config["classifier"]
     model = create_classifier(config).to(device)
-    optimizer = Adam(list(model.parameters()), lr=cc["learning_rate"], weight_decay=cc["weight_decay"])
+    optimizer = Adam(list(model.parameters()), lr=cc["learning_rate"], weight_decay=cc["weight_decay"],
+                     **optim_guard_options(config))
     scheduler = ReduceLROnPlateau(optimizer, mode="min", factor=0.5, patience=5)
     ck_dir = cc["checkpoint_dir"]
     os.makedirs(ck_dir, exist_ok=True)

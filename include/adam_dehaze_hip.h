@@ -488,6 +488,36 @@ int adh_adam_chunk_elems(void);
 int adh_adam_multi(void* stream, const adh_adam_tensor* table_dev, const int32_t* chunks_dev, int nchunks, float lr,
                    float beta1, float beta2, float eps, float weight_decay, float grad_scale, int dup_mode,
                    int max_repeats, int calls_since_upload);
+/* Global-norm gradient clipping and a non-finite-step guard around adh_adam_multi, on the device, without a host read:
+ *   adh_grad_sumsq            one float64 partial per (tensor, chunk) of the Adam table: sum (double(g) * double(grad_scale))^2.
+ *                             The table lists every tensor once, so a tensor with repeats > 1 is counted once.
+ *   adh_grad_guard_finalize   sums the partials in index order (float64) and writes the control block: sumsq, norm =
+ *                             (float)sqrt(sumsq), gscale_eff = (float)(grad_scale * coef) with coef = min(1, max_norm /
+ *                             (sqrt(sumsq) + 1e-6)) in double (torch's clip_grad_norm_), coef = 1 exactly when max_norm is not
+ *                             > 0 or is infinite (measure only).  A non-finite sum: with skip_nonfinite finite = 0 and both skip
+ *                             counters advance; without it finite = 1 and gscale_eff = grad_scale (the unguarded behaviour).
+ *   adh_adam_multi_guarded    adh_adam_multi with gscale = ctrl->gscale_eff; returns before it touches p, m or v when
+ *                             ctrl->finite == 0, and advances every tensor by (calls_since_upload - ctrl->skipped) * repeats:
+ *                             a skipped step consumes no bias-correction step.
+ * The three are enqueued in that order on one stream.  `skipped` counts the skips since the host last uploaded the table (the
+ * host zeroes it then), `skipped_total` the skips since the block was zeroed.  ctrl_dev points to one adh_grad_ctrl in device
+ * memory (void* in the prototypes: the block is the host's to lay out, like the partials). */
+typedef struct adh_grad_ctrl {
+    double sumsq;
+    float norm;
+    float gscale_eff;
+    int32_t finite;
+    int32_t skipped;
+    int32_t skipped_total;
+    int32_t reserved;
+} adh_grad_ctrl;
+int adh_grad_sumsq(void* stream, const adh_adam_tensor* table_dev, const int32_t* chunks_dev, int nchunks, float grad_scale,
+                   double* partials_dev);
+int adh_grad_guard_finalize(void* stream, const double* partials_dev, int nchunks, float grad_scale, double max_norm,
+                            int skip_nonfinite, void* ctrl_dev);
+int adh_adam_multi_guarded(void* stream, const adh_adam_tensor* table_dev, const int32_t* chunks_dev, int nchunks, float lr,
+                           float beta1, float beta2, float eps, float weight_decay, int dup_mode, int max_repeats,
+                           int calls_since_upload, const void* ctrl_dev);
 /* ---- detector stage (csrc/detect.hip): what torchvision's Faster R-CNN -- the detector
  * /root/reference models/detection.py:23-29 instantiates, consumed by evaluation/evaluate.py:288-344 -- does between its
  * convolutions.  torchvision is a third-party dependency absent from /root/reference: the algorithms follow its published
