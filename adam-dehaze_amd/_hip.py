@@ -54,6 +54,16 @@ class GradCtrl(C.Structure):
                 ("skipped_total", i32), ("reserved", i32)]
 
 
+class EmaTensor(C.Structure):
+    """struct adh_ema_tensor."""
+    _fields_ = [("p", vp), ("ema", vp), ("n", i64)]
+
+
+class EmaCtrl(C.Structure):
+    """struct adh_ema_ctrl: the device-resident control block of the weight EMA."""
+    _fields_ = [("updates", i32), ("active", i32), ("w", f32), ("reserved", i32)]
+
+
 class WLayout(C.Structure):
     """struct adh_wlayout."""
     _fields_ = [
@@ -194,6 +204,9 @@ _SIGNATURES = {
     "adh_grad_sumsq": [vp, vp, vp, i32, f32, vp],
     "adh_grad_guard_finalize": [vp, vp, i32, f32, f64, i32, vp],
     "adh_adam_multi_guarded": [vp, vp, vp, i32, f32, f32, f32, f32, f32, i32, i32, i32, vp],
+    "adh_ema_begin": [vp, vp, f64, i32, vp],
+    "adh_ema_multi": [vp, vp, vp, i32, vp],
+    "adh_ema_swap": [vp, vp, vp, i32],
     "adh_apply_fog": [vp, vp, vp, vp, i32, i32, i32, vp],
     "adh_psnr_num_blocks": [i64],
     "adh_psnr": [vp, vp, vp, i32, i64, f32, vp, i32, vp, vp],

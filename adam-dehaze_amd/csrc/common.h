@@ -9,6 +9,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define ADH_WAVE 64
 
+// floats per workgroup of the multi-tensor kernels (train_io.hip: Adam and the gradient guard; ema.hip): adh_adam_chunk_elems()
+#define ADH_ADAM_CHUNK 16384
+
 static inline int adh_check_launch() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ADH_OK : ADH_E_LAUNCH;

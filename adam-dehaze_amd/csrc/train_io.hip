@@ -7,7 +7,7 @@
 // ------------------------------------------------------------------------------------------------
 // multi-tensor Adam (training/train_joint.py:86-90, training/train_dehazing.py:52-57)
 // ------------------------------------------------------------------------------------------------
-#define ADAM_CHUNK 16384   // floats per workgroup
+#define ADAM_CHUNK ADH_ADAM_CHUNK   // floats per workgroup (common.h: ema.hip walks the same chunks)
 
 // one update of `repeats` listed copies of a tensor; dup_mode 0: the single-tensor loop of torch.optim.Adam (CPU default,
 // every torch < 2.0): `repeats` consecutive full updates; dup_mode 1: torch >= 2.0's foreach form on CUDA, where the

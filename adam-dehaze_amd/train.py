@@ -18,6 +18,12 @@ ignores it, main.py:50-51), `_validation_sums` for `validate_joint` / `validate_
 for the evaluators.  Checkpoints carry the reference's keys (train_joint.py:272-283, train_dehazing.py:196-203) plus
 `scheduler_state_dict`.
 
+Weight EMA (opt-in: the `ema:` config section, `ema_options`; absent, nothing below happens): each stage keeps an `ema.WeightEMA`
+of its model, built after the replicas were made identical, and updates it right after every `optimizer.step()`.  With
+`validate` the epoch's validation -- and so the scheduler metric and the best-checkpoint decision -- runs on the EMA weights
+(`WeightEMA.applied()`).  Checkpoints keep the raw weights under their usual keys, which is what training resumes from, and
+gain `ema_state_dict` / `ema_updates`; with `evaluate` the evaluators load the EMA set (`load_pretrained_model(prefer_ema=True)`).
+
 Data-parallel runs (torchrun, one process per GPU): replicas are made identical by broadcasting rank 0's parameters and
 buffers after construction / checkpoint loading; gradients go through `parallel.GradientSynchronizer`; every host-side
 decision that steers training -- the metric given to ReduceLROnPlateau, "skip this step, the sub-batch is empty" -- is
@@ -25,6 +31,7 @@ agreed across ranks first, so learning rates and step counts cannot diverge.
 """
 from __future__ import annotations
 
+import contextlib
 import glob
 import os
 import re
@@ -36,6 +43,7 @@ import torch
 from .classifier import create_classifier
 from .data import synthetic_loader  # noqa: F401  (re-exported: round-1 callers import it from here)
 from .dehazing import create_high_intensity_model, create_low_intensity_model, create_medium_intensity_model
+from .ema import WeightEMA
 from .loss import get_dehazing_loss, get_joint_loss
 from .metrics import psnr_batch, ssim_batch
 from .optim import Adam
@@ -81,12 +89,17 @@ def _world_rank():
     return int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
 
 
-def load_pretrained_model(model, checkpoint_path):
-    """train_joint.py:18-27: missing checkpoints are not errors."""
+def load_pretrained_model(model, checkpoint_path, prefer_ema: bool = False):
+    """train_joint.py:18-27: missing checkpoints are not errors.  `prefer_ema`: the file's `ema_state_dict` (the EMA weights a
+    run with the `ema:` section writes next to the raw ones) when it has one."""
     if os.path.exists(checkpoint_path):
         checkpoint = torch.load(checkpoint_path, map_location="cpu")
+        if prefer_ema and "ema_state_dict" in checkpoint:
+            model.load_state_dict(checkpoint["ema_state_dict"])
+            print(f"Loaded EMA weights from {checkpoint_path}")
+            return True
         model.load_state_dict(checkpoint["model_state_dict"])
-        print(f"Loaded pretrained weights from {checkpoint_path}")
+        print(f"Loaded pretrained weights from {checkpoint_path}" + (" (the file has no EMA weights)" if prefer_ema else ""))
         return True
     print(f"Checkpoint {checkpoint_path} not found. Starting with random weights.")
     return False
@@ -104,6 +117,31 @@ def optim_guard_options(config) -> Dict:
     if section.get("skip_nonfinite"):
         opts["skip_nonfinite"] = True
     return opts
+
+
+def ema_options(config) -> Optional[Dict]:
+    """The optional `ema:` section of the config with its defaults filled in; None when it is absent or null (no EMA)."""
+    section = config.get("ema")
+    if section is None:
+        return None
+    known = ("decay", "warmup", "validate", "evaluate")
+    if not isinstance(section, dict):
+        raise ValueError(f"config ema: expected a mapping with keys among ({', '.join(known)}), got {section!r}")
+    unknown = set(section) - set(known)
+    if unknown:
+        raise ValueError(f"config ema: unknown keys {sorted(unknown)} ({', '.join(known)})")
+    return {"decay": float(section.get("decay", 0.999)), "warmup": bool(section.get("warmup", True)),
+            "validate": bool(section.get("validate", True)), "evaluate": bool(section.get("evaluate", False))}
+
+
+def _weight_ema(config, params) -> Optional[WeightEMA]:
+    """The stage's WeightEMA over `params`, or None without the `ema:` section.  Built after the replicas were made identical."""
+    opts = ema_options(config)
+    return None if opts is None else WeightEMA(params, decay=opts["decay"], warmup=opts["warmup"])
+
+
+def _evaluate_ema(config) -> bool:
+    return bool((ema_options(config) or {}).get("evaluate", False))
 
 
 class _GuardStats:
@@ -128,13 +166,22 @@ class _GuardStats:
         self.acc[1] = torch.maximum(self.acc[1], val)
         self.acc[2] += finite
 
-    def read(self) -> Dict:
-        if self.acc is None:
+    def read(self, ema: Optional[WeightEMA] = None) -> Dict:
+        """`ema`: its update counter comes back in the same read ("ema_updates")."""
+        parts = [] if self.acc is None else [self.acc.double(), self.opt.skipped_total.double().view(1)]
+        if ema is not None:
+            parts.append(ema.updates_dev.double().view(1))
+        if not parts:
             return {}
-        total, peak, count, skipped = torch.cat([self.acc.double(), self.opt.skipped_total.double().view(1)]).tolist()
-        out = {"grad_norm_mean": total / max(1.0, count), "grad_norm_max": peak,
-               "skipped_steps": int(skipped) - self.skipped_before}
-        self.acc, self.skipped_before = None, int(skipped)
+        host = torch.cat(parts).tolist()
+        out = {}
+        if self.acc is not None:
+            total, peak, count, skipped = host[:4]
+            out = {"grad_norm_mean": total / max(1.0, count), "grad_norm_max": peak,
+                   "skipped_steps": int(skipped) - self.skipped_before}
+            self.acc, self.skipped_before = None, int(skipped)
+        if ema is not None:
+            out["ema_updates"] = int(host[-1])
         return out
 
     def close(self):
@@ -142,7 +189,8 @@ class _GuardStats:
             self.opt.step_hook = None
 
 
-def build_joint_system(config, world_size: int = 1, adam_duplicates: str = "sequential") -> Dict:
+def build_joint_system(config, world_size: int = 1, adam_duplicates: str = "sequential", with_ema: bool = True) -> Dict:
+    """`with_ema=False` (the evaluators: they only run the router) builds no WeightEMA whatever the config says."""
     device = torch.device(config["device"])
     classifier = create_classifier(config)
     low = create_low_intensity_model(config)
@@ -176,8 +224,10 @@ def build_joint_system(config, world_size: int = 1, adam_duplicates: str = "sequ
         sync = GradientSynchronizer(list(router.parameters()), world_size, detect_unused=hard, sync_bn=_sync_bn(config))
         sync.broadcast_parameters(router)
         sync.install()
+    # every unique parameter once (router.parameters() holds classifier + branches); after the broadcast: one seed for all ranks
+    ema = _weight_ema(config, router.parameters()) if with_ema else None
     return {"classifier": classifier, "models": models, "router": router, "optimizer": optimizer,
-            "scheduler": scheduler, "criterion": criterion, "sync": sync, "device": device}
+            "scheduler": scheduler, "criterion": criterion, "sync": sync, "device": device, "ema": ema}
 
 
 def joint_train_step(system: Dict, batch: Dict) -> Dict:
@@ -195,6 +245,8 @@ def joint_train_step(system: Dict, batch: Dict) -> Dict:
     if sync is not None:
         sync.finish()
     system["optimizer"].step()
+    if system.get("ema") is not None:
+        system["ema"].update(system["optimizer"])
     stats = {"loss": loss.detach(), "dehazing": comps["dehazing"].detach(),
              "classification": comps["classification"].detach()}
     if "ssim" in comps["dehazing_components"]:         # loss.lambda_ssim > 0 only
@@ -202,10 +254,11 @@ def joint_train_step(system: Dict, batch: Dict) -> Dict:
     return stats
 
 
-def dehazing_train_step(model, criterion, optimizer, batch: Dict, level: Optional[int], device, sync=None):
+def dehazing_train_step(model, criterion, optimizer, batch: Dict, level: Optional[int], device, sync=None, ema=None):
     """One iteration of train_dehazing.py:71-106: keep only the images of this branch's fog level.  Under data
     parallelism a rank whose sub-batch is empty still takes part in the gradient all-reduce (with zeros) unless the
-    sub-batch is empty on EVERY rank, so no rank is left waiting in a collective."""
+    sub-batch is empty on EVERY rank, so no rank is left waiting in a collective.  `ema`: updated after every optimiser step (a
+    step that returns early because the sub-batch is empty everywhere takes none)."""
     hazy, clear, labels = batch["hazy"], batch["clear"], batch["intensity"]
     if level is not None:
         keep = labels == level
@@ -230,6 +283,8 @@ def dehazing_train_step(model, criterion, optimizer, batch: Dict, level: Optiona
     if sync is not None:
         sync.finish()
     optimizer.step()
+    if ema is not None:
+        ema.update(optimizer)
     if empty:
         return None
     stats = {"loss": loss.detach(), "l1": comps["l1"].detach()}
@@ -430,10 +485,11 @@ def checkpoint_stage(path: str, config) -> str:
     raise ValueError(f"--resume {path}: model_state_dict matches none of the configured branches")
 
 
-def _restore_training_state(ck: Dict, optimizer, scheduler, sync, module) -> int:
+def _restore_training_state(ck: Dict, optimizer, scheduler, sync, module, ema=None) -> int:
     """What every resume does once its stage has checked `ck` and loaded the weights into `module`: optimiser and scheduler
-    state, the packed copies of the old weights dropped, the replicas made identical again.  Returns the epoch to continue
-    with; the best score so far is `_best_psnr_on_disk` of the stage's directory."""
+    state, the packed copies of the old weights dropped, the replicas made identical again, the EMA shadow and its counter (a
+    checkpoint without them seeds the shadow from the loaded weights).  Returns the epoch to continue with; the best score so
+    far is `_best_psnr_on_disk` of the stage's directory."""
     if "optimizer_state_dict" in ck:
         optimizer.load_state_dict(ck["optimizer_state_dict"])
     if "scheduler_state_dict" in ck:
@@ -442,6 +498,12 @@ def _restore_training_state(ck: Dict, optimizer, scheduler, sync, module) -> int
     invalidate_weight_cache()
     if sync is not None:
         sync.broadcast_parameters(module)
+    if ema is not None:
+        if "ema_state_dict" in ck and "ema_updates" in ck:
+            ema.load_state_dict(module, ck["ema_state_dict"], int(ck["ema_updates"]))
+        else:
+            ema.reseed()
+            print("Checkpoint has no EMA weights: the EMA starts from the loaded weights")
     return int(ck["epoch"]) + 1
 
 
@@ -452,7 +514,8 @@ def resume_joint(system: Dict, path: str) -> int:
         raise ValueError(f"--resume {path}: not a joint-training checkpoint (keys {sorted(ck)[:6]} ...); a branch "
                          "checkpoint resumes `--mode train_dehazing`, not this stage")
     system["router"].load_state_dict(ck["router_state_dict"])   # holds the classifier and the three branches
-    start_epoch = _restore_training_state(ck, system["optimizer"], system["scheduler"], system["sync"], system["router"])
+    start_epoch = _restore_training_state(ck, system["optimizer"], system["scheduler"], system["sync"], system["router"],
+                                          ema=system.get("ema"))
     print(f"Resumed joint training from {path} (epoch {ck['epoch'] + 1} done)")
     return start_epoch
 
@@ -482,23 +545,32 @@ def _loader_or_synthetic(loader, config, steps: int, seed_offset: int, device, e
 
 
 def _run_epochs(first_epoch: int, epochs: int, train_epoch, validate, scheduler, loss_key: str, score_key: str, best: float,
-                score_text: str, ck_dir: str, checkpoint, report, sync=None, modules=(), device=None):
+                score_text: str, ck_dir: str, checkpoint, report, sync=None, modules=(), device=None, ema=None, ema_model=None,
+                ema_validate: bool = True):
     """The epoch loop of the three training stages: the one statement of what the ranks do in which order.  The stage plugs
     in `train_epoch(epoch)`, `validate() -> dict`, `checkpoint(epoch, val) -> dict` and `report(epoch, train_loss, val)`.
     Returns the per-epoch records {"epoch", "train_loss", **val, "lr"}; with the `optim:` guard on they also carry
     "grad_norm_mean", "grad_norm_max" and "skipped_steps" of the epoch (this rank's; after the all-reduce every rank sees the
-    same gradient)."""
+    same gradient).  With a WeightEMA (`ema`, over the parameters of `ema_model`) they carry "ema_updates", read back together
+    with the guard's statistics; validation runs inside `ema.applied()` when `ema_validate`, and every checkpoint gains
+    "ema_state_dict" and "ema_updates" next to the raw weights."""
     rank = _world_rank()[1]
     history = []
     guard = _GuardStats(scheduler.opt)
+
+    def with_ema(ck, stats):
+        if ema is not None:
+            ck["ema_state_dict"], ck["ema_updates"] = ema.state_dict(ema_model), stats["ema_updates"]
+        return ck
     if rank == 0:
         os.makedirs(ck_dir, exist_ok=True)
     for epoch in range(first_epoch, epochs):
         # None, or this rank's mean train loss where the stage reports the rank-averaged one (the joint stage)
         train_loss = train_epoch(epoch)
-        guard_stats = guard.read()
+        guard_stats = guard.read(ema)                 # the epoch-end read-back of the step statistics, EMA counter included
         _sync_buffers_from_rank0(sync, *modules)      # validation and rank 0's checkpoint see one model
-        val = validate()                              # every rank enters its all-reduce, also one with nothing to validate
+        with ema.applied() if ema is not None and ema_validate else contextlib.nullcontext():
+            val = validate()                          # every rank enters its all-reduce, also one with nothing to validate
         if train_loss is not None:
             train_loss = all_reduce_mean_scalar(train_loss, device)
         scheduler.step(val[loss_key])                 # every rank steps on the same (rank-averaged) value
@@ -506,14 +578,18 @@ def _run_epochs(first_epoch: int, epochs: int, train_epoch, validate, scheduler,
                         **guard_stats})
         if rank == 0:
             report(epoch, train_loss, val)
-            if guard_stats:
+            if "grad_norm_mean" in guard_stats:
                 print("  Grad norm: mean {grad_norm_mean:.4f}, max {grad_norm_max:.4f}; skipped steps: {skipped_steps}"
                       .format(**guard_stats))
+            if ema is not None:
+                print(f"  EMA updates: {guard_stats['ema_updates']}" + (" (validated on the EMA weights)" if ema_validate else ""))
             if val[score_key] > best:
-                save_checkpoint_atomic(checkpoint(epoch, val), os.path.join(ck_dir, "best_model.pth"))
+                save_checkpoint_atomic(with_ema(checkpoint(epoch, val), guard_stats),
+                                       os.path.join(ck_dir, "best_model.pth"))
                 print("Saved best model with validation " + score_text.format(val[score_key]))
             if (epoch + 1) % 5 == 0:
-                save_checkpoint_atomic(checkpoint(epoch, val), os.path.join(ck_dir, f"checkpoint_epoch_{epoch + 1}.pth"))
+                save_checkpoint_atomic(with_ema(checkpoint(epoch, val), guard_stats),
+                                       os.path.join(ck_dir, f"checkpoint_epoch_{epoch + 1}.pth"))
         best = max(best, val[score_key])
         # nobody runs ahead (into the next stage's load_pretrained_model, a --resume) while rank 0 is still writing
         _barrier()
@@ -567,7 +643,8 @@ def train_joint_model(config, train_loader=None, val_loader=None, steps_per_epoc
     history = _run_epochs(start_epoch, epochs, train_epoch, validate, system["scheduler"], loss_key="val_loss",
                           score_key="val_psnr", best=best_val_psnr, score_text="PSNR: {:.2f} dB", ck_dir=ck_dir,
                           checkpoint=lambda epoch, val: joint_checkpoint(system, epoch, val), report=report,
-                          sync=system["sync"], modules=(system["router"],), device=dev)
+                          sync=system["sync"], modules=(system["router"],), device=dev, ema=system["ema"],
+                          ema_model=system["router"], ema_validate=(ema_options(config) or {}).get("validate", True))
     return system, history
 
 
@@ -592,6 +669,7 @@ def train_dehazing_model(config, intensity_level: str, train_loader=None, val_lo
         sync = GradientSynchronizer(list(model.parameters()), world, sync_bn=_sync_bn(config))
         sync.broadcast_parameters(model)
         sync.install()
+    ema = _weight_ema(config, model.parameters())         # after the broadcast: every rank seeds from the same weights
     start_epoch, best_val_psnr = 0, 0.0
     path = _resolve_resume(resume, ck_dir)
     if path is not None:
@@ -604,7 +682,7 @@ def train_dehazing_model(config, intensity_level: str, train_loader=None, val_lo
             raise ValueError(f"--resume {path}: checkpoint does not belong to the '{intensity_level}' branch "
                              f"({len(missing)} state_dict keys differ, e.g. {sorted(missing)[:3]})")
         model.load_state_dict(ck["model_state_dict"])
-        start_epoch = _restore_training_state(ck, optimizer, scheduler, sync, model)
+        start_epoch = _restore_training_state(ck, optimizer, scheduler, sync, model, ema=ema)
         best_val_psnr = _best_psnr_on_disk(ck_dir)
     if train_loader is None or val_loader is None:
         _warn_synthetic(config, f"train_dehazing_model[{intensity_level}]", _world_rank()[1])
@@ -614,7 +692,7 @@ def train_dehazing_model(config, intensity_level: str, train_loader=None, val_lo
         model.train()
         ssim_terms.clear()
         for batch in _loader_or_synthetic(train_loader, config, steps, 0, device, epoch):
-            st = dehazing_train_step(model, criterion, optimizer, batch, level, device, sync=sync)
+            st = dehazing_train_step(model, criterion, optimizer, batch, level, device, sync=sync, ema=ema)
             if st is not None:
                 losses.append(st["loss"])
                 if "ssim" in st:
@@ -634,7 +712,8 @@ def train_dehazing_model(config, intensity_level: str, train_loader=None, val_lo
         _run_epochs(start_epoch, epochs, train_epoch, validate, scheduler, loss_key="val_loss", score_key="val_psnr",
                     best=best_val_psnr, score_text="PSNR: {:.2f} dB", ck_dir=ck_dir,
                     checkpoint=lambda epoch, val: dehazing_checkpoint(model, optimizer, scheduler, epoch, val), report=report,
-                    sync=sync, modules=(model,))
+                    sync=sync, modules=(model,), ema=ema, ema_model=model,
+                    ema_validate=(ema_options(config) or {}).get("validate", True))
     finally:       # train_all: the next stage builds its own synchronizer
         if sync is not None:
             sync.uninstall()
@@ -696,13 +775,18 @@ def _joint_system_for_evaluation(config):
     """The routed system as an evaluator wants it: built for one process, the joint checkpoint loaded over the individually
     loaded weights if there is one, everything in eval mode.  Returns (system, path of the joint checkpoint it loaded or
     None)."""
-    system = build_joint_system(config, 1)
+    system = build_joint_system(config, 1, with_ema=False)
     ck = os.path.join(config["joint_training"]["checkpoint_dir"], "best_model.pth")
     loaded = None
     if os.path.exists(ck):
-        system["router"].load_state_dict(torch.load(ck, map_location="cpu")["router_state_dict"])
+        checkpoint = torch.load(ck, map_location="cpu")
+        if _evaluate_ema(config) and "ema_state_dict" in checkpoint:
+            system["router"].load_state_dict(checkpoint["ema_state_dict"])    # the router's state dict with the EMA weights
+            print(f"Loaded joint model (EMA weights) from {ck}")
+        else:
+            system["router"].load_state_dict(checkpoint["router_state_dict"])
+            print(f"Loaded joint model from {ck}")
         loaded = ck
-        print(f"Loaded joint model from {ck}")
     else:
         print(f"Joint checkpoint {ck} not found. Using the individually loaded / random weights.")
     system["classifier"].eval()
@@ -743,10 +827,11 @@ def evaluate_baseline_models(config, test_loader=None, steps: int = 2, use_lpips
     no router), PSNR / SSIM / LPIPS per category on the device, `<evaluation.results_dir>/baseline_results.json`.  The reference
     runs one image at a time; eval-mode branches are per-sample independent, so the images of a level go through as one batch."""
     from .metrics import CATEGORY_BY_LABEL, ImageQualityMetrics
-    system = build_joint_system(config, 1)
+    system = build_joint_system(config, 1, with_ema=False)
     dev = system["device"]
     for level, m in system["models"].items():
-        load_pretrained_model(m, os.path.join(config["dehazing"]["checkpoint_dir"], level, "best_model.pth"))
+        load_pretrained_model(m, os.path.join(config["dehazing"]["checkpoint_dir"], level, "best_model.pth"),
+                              prefer_ema=_evaluate_ema(config))
         m.eval()
     by_label = {0: system["models"]["low"], 1: system["models"]["medium"], 2: system["models"]["high"]}
     metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips)
@@ -934,7 +1019,7 @@ def classification_report3(cm) -> str:
     return "\n".join(lines) + "\n"
 
 
-def _classifier_pass(model, loader: Iterable[Dict], device, optimizer=None) -> Dict:
+def _classifier_pass(model, loader: Iterable[Dict], device, optimizer=None, ema=None) -> Dict:
     """One pass over `loader`: a training epoch when `optimizer` is given, else a no-grad evaluation.  Returns the mean
     batch loss, the confusion matrix (numpy int64 [3, 3], rows = truth) and the sample count."""
     from .loss import cross_entropy3
@@ -952,6 +1037,8 @@ def _classifier_pass(model, loader: Iterable[Dict], device, optimizer=None) -> D
             if optimizer is not None:
                 loss.backward()
                 optimizer.step()
+                if ema is not None:
+                    ema.update(optimizer)
             loss_sum += loss.detach().reshape(())
             cm += torch.bincount(y * 3 + logits.detach().argmax(1), minlength=9)
             nb += 1
@@ -976,6 +1063,7 @@ def train_classifier(config, train_loader=None, val_loader=None, steps: int = 4,
     optimizer = Adam(list(model.parameters()), lr=cc["learning_rate"], weight_decay=cc["weight_decay"],
                      **optim_guard_options(config))
     scheduler = ReduceLROnPlateau(optimizer, mode="min", factor=0.5, patience=5)
+    ema = _weight_ema(config, model.parameters())
     ck_dir = cc["checkpoint_dir"]
     os.makedirs(ck_dir, exist_ok=True)
     epochs = cc["epochs"] if epochs is None else epochs
@@ -986,7 +1074,7 @@ def train_classifier(config, train_loader=None, val_loader=None, steps: int = 4,
     def train_epoch(epoch):
         model.train()
         train_batches = _loader_or_synthetic(train_loader, config, steps, 0, device, epoch)
-        tr.update(_classifier_pass(model, train_batches, device, optimizer))
+        tr.update(_classifier_pass(model, train_batches, device, optimizer, ema=ema))
 
     def validate():
         model.eval()
@@ -1006,10 +1094,14 @@ def train_classifier(config, train_loader=None, val_loader=None, steps: int = 4,
 
     # best starts at -1.0 (the reference starts at 0.0 and writes nothing if every epoch scores 0 %, then fails to reload)
     _run_epochs(0, epochs, train_epoch, validate, scheduler, loss_key="loss", score_key="val_acc", best=-1.0,
-                score_text="accuracy: {:.2f}%", ck_dir=ck_dir, checkpoint=checkpoint, report=report)
+                score_text="accuracy: {:.2f}%", ck_dir=ck_dir, checkpoint=checkpoint, report=report, ema=ema, ema_model=model,
+                ema_validate=(ema_options(config) or {}).get("validate", True))
     best_path = os.path.join(ck_dir, "best_model.pth")
     if os.path.exists(best_path):
-        model.load_state_dict(torch.load(best_path, map_location="cpu")["model_state_dict"])
+        if _evaluate_ema(config):         # the model handed to evaluate_classifier carries the EMA weights
+            load_pretrained_model(model, best_path, prefer_ema=True)
+        else:
+            model.load_state_dict(torch.load(best_path, map_location="cpu")["model_state_dict"])
     return model
 
 

@@ -518,6 +518,32 @@ int adh_grad_guard_finalize(void* stream, const double* partials_dev, int nchunk
 int adh_adam_multi_guarded(void* stream, const adh_adam_tensor* table_dev, const int32_t* chunks_dev, int nchunks, float lr,
                            float beta1, float beta2, float eps, float weight_decay, int dup_mode, int max_repeats,
                            int calls_since_upload, const void* ctrl_dev);
+/* Exponential moving average of the weights (csrc/ema.hip), driven by the optimiser's control block, without a host read.
+ * table_dev lists every UNIQUE parameter once (a parameter the optimiser lists twice still advances once per step) with its
+ * fp32 shadow; chunks_dev holds nchunks pairs (tensor index, chunk index) of adh_adam_chunk_elems() floats, as for
+ * adh_adam_multi.  ema_ctrl_dev points to one adh_ema_ctrl in device memory, 8-byte aligned, the host's to lay out.
+ *   adh_ema_begin   one workgroup, before every adh_ema_multi.  guard_ctrl_dev non-null (the adh_grad_ctrl that
+ *                   adh_grad_guard_finalize wrote earlier on the stream; only read) with finite == 0: active = 0, `updates`
+ *                   stays.  Otherwise updates += 1, active = 1 and, in double, d = warmup ? min(decay, (1 + updates) /
+ *                   (10 + updates)) : decay, w = (float)(1.0 - d).  decay in [0, 1).
+ *   adh_ema_multi   returns without touching memory when active == 0; otherwise ema = ema + w * (p - ema) per element in
+ *                   fp32: p and ema read, ema written, 12 bytes per parameter.
+ *   adh_ema_swap    exchanges the contents of p and ema in place, bit for bit (16 bytes per parameter); no pointer moves, so
+ *                   every resident table stays valid.  The host drops its packed weight copies afterwards. */
+typedef struct adh_ema_tensor {
+    float* p;
+    float* ema;
+    int64_t n;
+} adh_ema_tensor;
+typedef struct adh_ema_ctrl {
+    int32_t updates;
+    int32_t active;
+    float w;
+    int32_t reserved;
+} adh_ema_ctrl;
+int adh_ema_begin(void* stream, void* ema_ctrl_dev, double decay, int warmup, const void* guard_ctrl_dev);
+int adh_ema_multi(void* stream, const void* table_dev, const int32_t* chunks_dev, int nchunks, const void* ema_ctrl_dev);
+int adh_ema_swap(void* stream, const void* table_dev, const int32_t* chunks_dev, int nchunks);
 /* ---- detector stage (csrc/detect.hip): what torchvision's Faster R-CNN -- the detector
  * /root/reference models/detection.py:23-29 instantiates, consumed by evaluation/evaluate.py:288-344 -- does between its
  * convolutions.  torchvision is a third-party dependency absent from /root/reference: the algorithms follow its published

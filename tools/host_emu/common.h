@@ -3,7 +3,8 @@
 // GPU thread, a pthread barrier for __syncthreads(), the workgroups of a launch one after the other.  The point is to run the
 // kernel's own index arithmetic under the host sanitizers (-fsanitize=address,undefined) and against float64 without a GPU;
 // it says nothing about speed.  Used by tests/test_ssim_loss_hostemu_cpu.py on a copy of csrc/ssim_loss.hip and, with
-// -DADH_HOST_EMU (the section at the end), by tests/test_wgrad_reduce_hostemu_cpu.py on a copy of csrc/conv_wgrad_reduce.hip.
+// -DADH_HOST_EMU (the section at the end), by tests/test_wgrad_reduce_hostemu_cpu.py on a copy of csrc/conv_wgrad_reduce.hip and
+// by tests/test_ema_hostemu_cpu.py on a copy of csrc/ema.hip.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -59,4 +60,5 @@ struct adh_wg32_taps {
     int tap0[4], tap_sy[4], tap_sx[4], rev[4];
 };
 int adh_wgrad32_class_taps(const adh_conv_desc* d, adh_wg32_taps* tp);
+#define ADH_ADAM_CHUNK 16384   // csrc/ema.hip: floats per workgroup (csrc/common.h's)
 #endif
