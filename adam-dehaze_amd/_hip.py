@@ -213,6 +213,9 @@ _SIGNATURES = {
     "adh_ssim_num_blocks": [i32, i32],
     "adh_ssim_gray": [vp, vp, vp, i32, i32, i32, f32, vp, i32, vp],
     "adh_ssim_gray_bwd": [vp, vp, vp, i32, i32, i32, f32, vp, vp],
+    "adh_fft_l1_workspace_bytes": [i32, i32, i32],
+    "adh_fft_l1_num_partials": [i32, i32, i32],
+    "adh_fft_l1": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp],
     "adh_add_inplace": [vp, vp, vp, i64],
     "adh_axpby_strided": [vp, vp, i32, vp, i32, i64, i32, f32, f32],
     "adh_maxpool": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp],
@@ -244,7 +247,7 @@ _VALUE_FUNCS = {"adh_version", "adh_conv_fewout_supported", "adh_conv_fewin_supp
                 "adh_conv_wino32_num_blocks", "adh_conv_wgrad_wino_groups", "adh_conv_wgrad_wino32_groups", "adh_conv_wgrad_wino32_classes", "adh_conv_wgrad_wino32_tiles", "adh_conv_wgrad_wino43_groups", "adh_conv_wgrad_wino43_strips", "adh_conv_wgrad_small_slabs", "adh_conv_wgrad_stem_slabs", "adh_conv_stem_num_blocks", "adh_conv_wgrad_slabs", "adh_conv_wgrad_groups", "adh_conv_lds_bytes", "adh_conv_num_blocks", "adh_bn_bwd_num_blocks",
                 "adh_cbam_pool_num_blocks", "adh_cbam_bwd_b_num_blocks", "adh_head_blend_bwd_num_blocks",
                 "adh_reduce_num_blocks", "adh_lpips_layer_num_blocks", "adh_adam_chunk_elems", "adh_nms_words", "adh_augment_num_blocks", "adh_psnr_num_blocks", "adh_cbam_bwd_d_scratch_floats",
-                "adh_ssim_num_blocks", "adh_dwconv_num_blocks", "adh_dwconv_wgrad_num_blocks", "adh_channel_scale_bwd_num_blocks",
+                "adh_ssim_num_blocks", "adh_fft_l1_workspace_bytes", "adh_fft_l1_num_partials", "adh_dwconv_num_blocks", "adh_dwconv_wgrad_num_blocks", "adh_channel_scale_bwd_num_blocks",
                 "adh_bn_slice_stats_num_blocks"}
 
 _ERRORS = {-1: "ADH_E_ARG (bad argument: shape / alignment / null pointer)",

@@ -12,6 +12,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // floats per workgroup of the multi-tensor kernels (train_io.hip: Adam and the gradient guard; ema.hip): adh_adam_chunk_elems()
 #define ADH_ADAM_CHUNK 16384
 
+// the launch's dynamic LDS as an array of T (a macro so that tools/host_emu/common.h can stand in a heap block for it)
+#define ADH_DYN_LDS(T, name) extern __shared__ __attribute__((aligned(16))) T name[]
+
 static inline int adh_check_launch() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ADH_OK : ADH_E_LAUNCH;

@@ -1,7 +1,8 @@
 """Losses of the hot path (/root/reference training/loss.py) on the HIP kernels.
 
-`DehazingLoss` = 1.0*L1 + 0.1*content(VGG16 taps) + 0.1*LPIPS(alex) (+ lambda_ssim * (1 - SSIM), off by default: a
-structural term that needs no pretrained weights, not in the reference); `JointLoss` adds 0.2*CE
+`DehazingLoss` = 1.0*L1 + 0.1*content(VGG16 taps) + 0.1*LPIPS(alex) (+ lambda_ssim * (1 - SSIM) and lambda_fft * the L1
+distance of the 2-D Fourier spectra, both off by default: terms that need no pretrained weights, not in the reference);
+`JointLoss` adds 0.2*CE
 (+ 0.5 * detection, always 0 in the drivers).  Forward signatures and returned dict keys follow
 loss.py:125-162 and :179-224.  The third-party feature networks (VGG16 / LPIPS-AlexNet) are built here
 with torchvision / lpips parameter names; their pretrained weights cannot be downloaded offline, so they
@@ -143,6 +144,63 @@ def ssim_per_image(pred: torch.Tensor, target: torch.Tensor, data_range: float =
     """Differentiable per-image SSIM [N] (channel-mean grayscale, skimage defaults): the value of metrics.ssim_batch, bit
     for bit, with a gradient for `pred`; `target` gets none."""
     return _SSIMFn.apply(pred, target.detach(), data_range)
+
+
+FFT_MIN, FFT_MAX = 8, 4096                                 # csrc/fft_loss.hip: each of H and W a power of two in this range
+FFT_NORMS = ("backward", "ortho")
+
+
+def _check_fft_norm(norm):
+    if norm not in FFT_NORMS:
+        raise ValueError(f"fft_norm must be one of {FFT_NORMS}, got {norm!r}")
+    return norm
+
+
+class _FreqFn(torch.autograd.Function):
+    """mean(|Re D| + |Im D|) / 2 over D = fft2(pred - target) from csrc/fft_loss.hip.  When `pred` needs a gradient the one
+    launch computes it as well (the spectrum is in LDS anyway) and it is kept: the backward is one product with the upstream
+    scalar.  Otherwise the sign and adjoint passes are skipped and no gradient buffer exists."""
+
+    @staticmethod
+    def forward(ctx, pred, target, ortho, want_grad):
+        pred, target = pred.contiguous(), target.contiguous()
+        N, _, Hh, Ww = pred.shape
+        dev = pred.device
+        ws = torch.empty(H.value("adh_fft_l1_workspace_bytes", N, Hh, Ww) // 4, device=dev, dtype=torch.float32)
+        partial = torch.empty(H.value("adh_fft_l1_num_partials", N, Hh, Ww), device=dev, dtype=torch.float64)
+        out = torch.empty((), device=dev, dtype=torch.float32)
+        grad = torch.empty_like(pred) if want_grad else None
+        H.call("adh_fft_l1", pred.data_ptr(), target.data_ptr(), N, Hh, Ww, int(ortho), ws.data_ptr(), partial.data_ptr(),
+               out.data_ptr(), H.ptr(grad))
+        if want_grad:
+            ctx.save_for_backward(grad)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0] or not ctx.saved_tensors:
+            return None, None, None, None
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None, None
+
+
+def frequency_l1(pred: torch.Tensor, target: torch.Tensor, norm: str = "backward") -> torch.Tensor:
+    """F.l1_loss(view_as_real(fft2(pred, norm=norm)), view_as_real(fft2(target, norm=norm))) for [N,3,H,W] float32 images on
+    the device, H and W each a power of two in [8, 4096], with a gradient for `pred`; `target` gets none.  The imaginary
+    part of the four self-conjugate bins is exactly 0 and d|x|/dx = 0 at 0.  "backward" is the unnormalised transform (the
+    value grows with sqrt(H W)), "ortho" divides by sqrt(H W)."""
+    _check_fft_norm(norm)
+    if pred.dim() != 4 or pred.shape[1] != 3 or pred.shape != target.shape:
+        raise ValueError(f"frequency_l1 takes two [N,3,H,W] images of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    for name, v in (("H", pred.shape[2]), ("W", pred.shape[3])):
+        if v < FFT_MIN or v > FFT_MAX or v & (v - 1):
+            raise ValueError(f"frequency_l1: {name} = {v}, but H and W must each be a power of two in [{FFT_MIN}, {FFT_MAX}] "
+                             "(mixed-radix sizes are not implemented)")
+    H.require_cuda(pred, "prediction")
+    H.require_cuda(target, "target")
+    want_grad = torch.is_grad_enabled() and pred.requires_grad
+    return _FreqFn.apply(pred, target.detach(), norm == "ortho", want_grad)
 
 
 def l1_loss(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -508,20 +566,37 @@ class SSIMLoss(nn.Module):
         return 1.0 - ssim_per_image(pred, target, self.data_range).mean()
 
 
+class FrequencyLoss(nn.Module):
+    """L1 distance between the 2-D Fourier spectra of prediction and target (frequency_l1): 0 for identical images."""
+
+    def __init__(self, norm="backward"):
+        super().__init__()
+        self.norm = _check_fft_norm(norm)
+
+    def forward(self, pred, target):
+        return frequency_l1(pred, target, self.norm)
+
+
 class DehazingLoss(nn.Module):
     """Combined loss for image dehazing (loss.py:110-162)."""
 
     def __init__(self, lambda_l1=1.0, lambda_content=0.1, lambda_perceptual=0.1, content=True, perceptual=True,
-                 lambda_ssim=0.0):
+                 lambda_ssim=0.0, lambda_fft=0.0, fft_norm="backward"):
         """`content` / `perceptual` = False drop the VGG16 / LPIPS terms (their pretrained weights cannot be
         downloaded here: the extractors are randomly initialised until a checkpoint is loaded).  `lambda_ssim` > 0 adds
-        lambda_ssim * (1 - mean SSIM) and the key 'ssim' to the returned dict; 0 (the reference) launches nothing extra."""
+        lambda_ssim * (1 - mean SSIM) and the key 'ssim' to the returned dict; 0 (the reference) launches nothing extra.
+        `lambda_fft` > 0 likewise adds lambda_fft * frequency_l1(pred, target, fft_norm) and the key 'fft'."""
         super().__init__()
         self.lambda_l1, self.lambda_content, self.lambda_perceptual = lambda_l1, lambda_content, lambda_perceptual
         self.lambda_ssim = float(lambda_ssim)
         if self.lambda_ssim < 0:
             raise ValueError(f"lambda_ssim must be >= 0, got {lambda_ssim}")
         self.ssim_loss = SSIMLoss() if self.lambda_ssim > 0 else None
+        self.lambda_fft = float(lambda_fft)
+        if self.lambda_fft < 0:
+            raise ValueError(f"lambda_fft must be >= 0, got {lambda_fft}")
+        self.fft_norm = _check_fft_norm(fft_norm)
+        self.fft_loss = FrequencyLoss(self.fft_norm) if self.lambda_fft > 0 else None
         self.content_loss = ContentLoss() if content else None
         self.perceptual_loss = PerceptualLoss() if perceptual else None
 
@@ -533,11 +608,15 @@ class DehazingLoss(nn.Module):
         if perceptual.dim() > 0:
             perceptual = perceptual.mean()
         total = self.lambda_l1 * l1 + self.lambda_content * content + self.lambda_perceptual * perceptual
-        if self.ssim_loss is None:
-            return total, {"l1": l1, "content": content, "perceptual": perceptual, "total": total}
-        ssim = self.ssim_loss(pred, target)
-        total = total + self.lambda_ssim * ssim
-        return total, {"l1": l1, "content": content, "perceptual": perceptual, "ssim": ssim, "total": total}
+        comps = {"l1": l1, "content": content, "perceptual": perceptual}
+        if self.ssim_loss is not None:
+            comps["ssim"] = self.ssim_loss(pred, target)
+            total = total + self.lambda_ssim * comps["ssim"]
+        if self.fft_loss is not None:
+            comps["fft"] = self.fft_loss(pred, target)
+            total = total + self.lambda_fft * comps["fft"]
+        comps["total"] = total
+        return total, comps
 
 
 class JointLoss(nn.Module):
@@ -548,7 +627,7 @@ class JointLoss(nn.Module):
         self.lambda_dehazing = lambda_dehazing
         self.lambda_classification = lambda_classification
         self.lambda_detection = lambda_detection
-        self.dehazing_loss = DehazingLoss(lambda_ssim=_lambda_ssim(config))
+        self.dehazing_loss = DehazingLoss(lambda_ssim=_lambda_ssim(config), **_lambda_fft(config))
 
     def forward(self, pred, target_clear, pred_intensity=None, target_intensity=None, detection_loss=None):
         dehazing_loss, comps = self.dehazing_loss(pred, target_clear)
@@ -568,9 +647,17 @@ def _lambda_ssim(config) -> float:
     return float(((config or {}).get("loss") or {}).get("lambda_ssim", 0.0))
 
 
+def _lambda_fft(config) -> dict:
+    """`loss.lambda_fft` and `loss.fft_norm` of the config as DehazingLoss's keywords (absent in the reference's: 0, the
+    term is off)."""
+    sec = (config or {}).get("loss") or {}
+    return {"lambda_fft": float(sec.get("lambda_fft", 0.0)), "fft_norm": sec.get("fft_norm", "backward")}
+
+
 def get_dehazing_loss(config):
     """loss.py:226-232."""
-    return DehazingLoss(lambda_l1=1.0, lambda_content=0.1, lambda_perceptual=0.1, lambda_ssim=_lambda_ssim(config))
+    return DehazingLoss(lambda_l1=1.0, lambda_content=0.1, lambda_perceptual=0.1, lambda_ssim=_lambda_ssim(config),
+                        **_lambda_fft(config))
 
 
 def get_joint_loss(config):

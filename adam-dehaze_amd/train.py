@@ -230,6 +230,10 @@ def build_joint_system(config, world_size: int = 1, adam_duplicates: str = "sequ
             "scheduler": scheduler, "criterion": criterion, "sync": sync, "device": device, "ema": ema}
 
 
+# the opt-in terms of DehazingLoss: the key a step reports them under (when the config turns them on) -> the epoch report's label
+_OPT_IN_TERMS = {"ssim": "1 - SSIM", "fft": "FFT L1"}
+
+
 def joint_train_step(system: Dict, batch: Dict) -> Dict:
     """One iteration of train_joint.py:129-166.  Losses stay on the device (no .item() sync)."""
     dev = system["device"]
@@ -249,8 +253,9 @@ def joint_train_step(system: Dict, batch: Dict) -> Dict:
         system["ema"].update(system["optimizer"])
     stats = {"loss": loss.detach(), "dehazing": comps["dehazing"].detach(),
              "classification": comps["classification"].detach()}
-    if "ssim" in comps["dehazing_components"]:         # loss.lambda_ssim > 0 only
-        stats["ssim"] = comps["dehazing_components"]["ssim"].detach()
+    for k in _OPT_IN_TERMS:                            # loss.lambda_ssim / loss.lambda_fft > 0 only
+        if k in comps["dehazing_components"]:
+            stats[k] = comps["dehazing_components"][k].detach()
     return stats
 
 
@@ -288,8 +293,9 @@ def dehazing_train_step(model, criterion, optimizer, batch: Dict, level: Optiona
     if empty:
         return None
     stats = {"loss": loss.detach(), "l1": comps["l1"].detach()}
-    if "ssim" in comps:                                # loss.lambda_ssim > 0 only
-        stats["ssim"] = comps["ssim"].detach()
+    for k in _OPT_IN_TERMS:                            # loss.lambda_ssim / loss.lambda_fft > 0 only
+        if k in comps:
+            stats[k] = comps[k].detach()
     return stats
 
 
@@ -613,26 +619,28 @@ def train_joint_model(config, train_loader=None, val_loader=None, steps_per_epoc
         start_epoch, best_val_psnr = resume_joint(system, path), _best_psnr_on_disk(ck_dir)
     if train_loader is None or val_loader is None:
         _warn_synthetic(config, "train_joint_model", _world_rank()[1])
-    ssim_total, n = None, 0      # the opt-in loss term summed over the epoch's steps on this rank, for the report
+    term_totals, n = {}, 0       # the opt-in loss terms summed over the epoch's steps on this rank, for the report
 
     def train_epoch(epoch):
-        nonlocal ssim_total, n
+        nonlocal n
         system["classifier"].train()
         for m in system["models"].values():
             m.train()
         system["router"].train()
-        total, ssim_total, n = None, None, 0
+        total, n = None, 0
+        term_totals.clear()
         for batch in _loader_or_synthetic(train_loader, config, steps_per_epoch, 0, dev, epoch):
             stats = joint_train_step(system, batch)
             total = stats["loss"] if total is None else total + stats["loss"]
-            if "ssim" in stats:
-                ssim_total = stats["ssim"] if ssim_total is None else ssim_total + stats["ssim"]
+            for k in _OPT_IN_TERMS:
+                if k in stats:
+                    term_totals[k] = stats[k] if k not in term_totals else term_totals[k] + stats[k]
             n += 1
         return float(total) / max(1, n) if total is not None else 0.0
 
     def report(epoch, train_loss, val):
-        ssim_part = "" if ssim_total is None else f" (1 - SSIM: {float(ssim_total) / max(1, n):.4f}, this rank)"
-        print(f"Epoch {epoch + 1}/{epochs}:\n  Train Loss: {train_loss:.4f}{ssim_part}\n  Val Loss: {val['val_loss']:.4f} "
+        terms_part = "".join(f" ({_OPT_IN_TERMS[k]}: {float(v) / max(1, n):.4f}, this rank)" for k, v in term_totals.items())
+        print(f"Epoch {epoch + 1}/{epochs}:\n  Train Loss: {train_loss:.4f}{terms_part}\n  Val Loss: {val['val_loss']:.4f} "
               f"(Dehaze: {val['val_dehaze_loss']:.4f}, Class: {val['val_class_loss']:.4f})\n"
               f"  Val PSNR: {val['val_psnr']:.2f} dB, Val SSIM: {val['val_ssim']:.4f}")
 
@@ -686,23 +694,26 @@ def train_dehazing_model(config, intensity_level: str, train_loader=None, val_lo
         best_val_psnr = _best_psnr_on_disk(ck_dir)
     if train_loader is None or val_loader is None:
         _warn_synthetic(config, f"train_dehazing_model[{intensity_level}]", _world_rank()[1])
-    losses, ssim_terms = [], []
+    losses, opt_in_terms = [], {k: [] for k in _OPT_IN_TERMS}
 
     def train_epoch(epoch):
         model.train()
-        ssim_terms.clear()
+        for terms in opt_in_terms.values():
+            terms.clear()
         for batch in _loader_or_synthetic(train_loader, config, steps, 0, device, epoch):
             st = dehazing_train_step(model, criterion, optimizer, batch, level, device, sync=sync, ema=ema)
             if st is not None:
                 losses.append(st["loss"])
-                if "ssim" in st:
-                    ssim_terms.append(st["ssim"])
+                for k, terms in opt_in_terms.items():
+                    if k in st:
+                        terms.append(st[k])
 
     def report(epoch, train_loss, val):
         print(f"Epoch {epoch + 1}/{epochs}:\n  Val Loss: {val['val_loss']:.4f}, Val PSNR: {val['val_psnr']:.2f}, "
               f"Val SSIM: {val['val_ssim']:.4f}")
-        if ssim_terms:                         # the opt-in loss term, mean over this rank's steps like the L1 term
-            print(f"  Train 1 - SSIM: {float(torch.stack(ssim_terms).mean()):.4f}")
+        for k, terms in opt_in_terms.items():  # the opt-in loss terms, mean over this rank's steps like the L1 term
+            if terms:
+                print(f"  Train {_OPT_IN_TERMS[k]}: {float(torch.stack(terms).mean()):.4f}")
 
     def validate():
         val_batches = _loader_or_synthetic(val_loader, config, val_steps, 500000, device)

@@ -608,6 +608,23 @@ int adh_ssim_gray(void* stream, const float* pred_nchw, const float* target_nchw
 int adh_ssim_gray_bwd(void* stream, const float* pred_nchw, const float* target_nchw, int N, int H, int W, float data_range,
                       const float* g_ssim, float* g_pred_nchw);
 
+/* Frequency-domain L1 loss term (csrc/fft_loss.hip): for d = pred - target [N,3,H,W] and D = fft2(d) over the last two dims
+ * (unnormalised, e^{-2 pi i (uy/H + vx/W)}),
+ *   loss = sum over (n, c, u, v) of (|Re D| + |Im D|) / (2 N 3 H W),   divided once more by sqrt(H W) when ortho = 1;
+ *   g_pred = Re(F^H s) / (2 N 3 H W) (likewise for ortho), s = sign(Re D) + i sign(Im D) with sign(0) = 0.
+ * That is F.l1_loss(view_as_real(fft2(pred, norm)), view_as_real(fft2(target, norm))) and its gradient for pred; target gets
+ * none.  The imaginary part of the four self-conjugate bins is exactly 0.  H and W are each a power of two in [8, 4096], 3 N <=
+ * 65535 and 3 N H W * 4 bytes < 2^31: ADH_E_UNSUPPORTED otherwise (from the two queries as well; mixed-radix sizes are not
+ * implemented).  workspace: adh_fft_l1_workspace_bytes(N, H, W) bytes (the size of one image tensor), 8-byte aligned, the half
+ * spectrum, overwritten; partial: double[adh_fft_l1_num_partials(N, H, W)], summed in a fixed order by the last kernel: no
+ * atomics, the same bits every run; loss: one float on the device.  g_pred null: value only (the sign and adjoint passes are
+ * skipped); otherwise float[N*3*H*W], written, not accumulated.  The launch transforms with its own radix-2/4 FFT in LDS; no
+ * FFT library is involved. */
+int adh_fft_l1_workspace_bytes(int N, int H, int W);
+int adh_fft_l1_num_partials(int N, int H, int W);
+int adh_fft_l1(void* stream, const float* pred_nchw, const float* target_nchw, int N, int H, int W, int ortho, void* workspace,
+               double* partial, float* loss, float* g_pred_nchw);
+
 /* ---- Depthwise convolution and squeeze-excitation (torchvision MobileNetV2 / V3; depthwise.hip) ------------------------
  * Conv2d(C, C, k, stride, padding (k-1)/2, groups=C, bias=False) on NHWC fp32 activations with channel strides x_cs /
  * out_cs; C % 4 == 0, C <= 4096, k in {3, 5}, stride in {1, 2}.  Weights are packed once per weight version:

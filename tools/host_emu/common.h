@@ -4,7 +4,8 @@
 // kernel's own index arithmetic under the host sanitizers (-fsanitize=address,undefined) and against float64 without a GPU;
 // it says nothing about speed.  Used by tests/test_ssim_loss_hostemu_cpu.py on a copy of csrc/ssim_loss.hip and, with
 // -DADH_HOST_EMU (the section at the end), by tests/test_wgrad_reduce_hostemu_cpu.py on a copy of csrc/conv_wgrad_reduce.hip and
-// by tests/test_ema_hostemu_cpu.py on a copy of csrc/ema.hip.
+// by tests/test_ema_hostemu_cpu.py on a copy of csrc/ema.hip; with -DADH_HOST_EMU_DYN_LDS on top (the last section), by
+// tests/test_fft_loss_hostemu_cpu.py on a copy of csrc/fft_loss.hip.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -61,4 +62,31 @@ struct adh_wg32_taps {
 };
 int adh_wgrad32_class_taps(const adh_conv_desc* d, adh_wg32_taps* tp);
 #define ADH_ADAM_CHUNK 16384   // csrc/ema.hip: floats per workgroup (csrc/common.h's)
+#endif
+
+#ifdef ADH_HOST_EMU_DYN_LDS
+// What csrc/fft_loss.hip takes beyond the ADH_HOST_EMU section (tests/test_fft_loss_hostemu_cpu.py defines both): dynamic LDS,
+// which every launch gets as a heap block of exactly the bytes it asked for, so that an LDS index out of range is the
+// sanitizer's to report as well; the attribute call that lifts the 64 KiB limit on the device; bit reversal; and sincospif,
+// here the float64 functions rounded once.
+extern void* emu_dyn_lds;
+#define ADH_DYN_LDS(T, name) T* name = (T*)emu_dyn_lds
+#undef hipLaunchKernelGGL
+#define hipLaunchKernelGGL(k, grid, block, shmem, stream, ...)     \
+    do {                                                           \
+        emu_dyn_lds = malloc((shmem) ? (shmem) : 1);               \
+        emu_launch(grid, block, [&]() { k(__VA_ARGS__); });        \
+        free(emu_dyn_lds);                                         \
+    } while (0)
+#define hipFuncAttributeMaxDynamicSharedMemorySize 0
+static inline int hipFuncSetAttribute(const void*, int, int) { return 0; }
+static inline unsigned __brev(unsigned v) {
+    unsigned r = 0;
+    for (int i = 0; i < 32; ++i) r |= ((v >> i) & 1u) << (31 - i);
+    return r;
+}
+static inline void sincospif(float x, float* s, float* c) {
+    *s = (float)sin(3.14159265358979323846 * (double)x);
+    *c = (float)cos(3.14159265358979323846 * (double)x);
+}
 #endif
