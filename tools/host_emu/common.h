@@ -5,7 +5,8 @@
 // it says nothing about speed.  Used by tests/test_ssim_loss_hostemu_cpu.py on a copy of csrc/ssim_loss.hip and, with
 // -DADH_HOST_EMU (the section at the end), by tests/test_wgrad_reduce_hostemu_cpu.py on a copy of csrc/conv_wgrad_reduce.hip and
 // by tests/test_ema_hostemu_cpu.py on a copy of csrc/ema.hip; with -DADH_HOST_EMU_DYN_LDS on top (the last section), by
-// tests/test_fft_loss_hostemu_cpu.py on a copy of csrc/fft_loss.hip.
+// tests/test_fft_loss_hostemu_cpu.py on a copy of csrc/fft_loss.hip; with -DADH_HOST_EMU_STREAM on top of ADH_HOST_EMU (the section
+// after it), by tests/test_{bn_act,depthwise,densenet}_hostemu_cpu.py on copies of the three streaming kernel files.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -88,5 +89,58 @@ static inline unsigned __brev(unsigned v) {
 static inline void sincospif(float x, float* s, float* c) {
     *s = (float)sin(3.14159265358979323846 * (double)x);
     *c = (float)cos(3.14159265358979323846 * (double)x);
+}
+#endif
+
+#ifdef ADH_HOST_EMU_STREAM
+// What csrc/bn_act.hip, csrc/depthwise.hip and csrc/densenet.hip take beyond the ADH_HOST_EMU section; their drivers link
+// stream_rt.cpp, whose emu_launch walks grid.x, grid.y and grid.z.  The non-temporal builtins are plain loads and stores.  The
+// activation helpers are copies of csrc/common.h's: keep them the same.
+#include <atomic>
+#define __builtin_nontemporal_load(p) (*(p))
+#define __builtin_nontemporal_store(v, p) (*(p) = (v))
+static inline int adh_max_i(int a, int b) { return a > b ? a : b; }
+static inline bool adh_act_valid(int act) {
+    return act == ADH_ACT_NONE || act == ADH_ACT_RELU || act == ADH_ACT_RELU6 || act == ADH_ACT_HARDSWISH ||
+           act == ADH_ACT_HARDSIGMOID;
+}
+static inline float adh_act_fwd(int act, float z) {
+    switch (act) {
+        case ADH_ACT_RELU: return fmaxf(z, 0.f);
+        case ADH_ACT_RELU6: return fminf(fmaxf(z, 0.f), 6.f);
+        case ADH_ACT_HARDSWISH: return z * fminf(fmaxf(z + 3.f, 0.f), 6.f) / 6.f;
+        case ADH_ACT_HARDSIGMOID: return fminf(fmaxf(z + 3.f, 0.f), 6.f) / 6.f;
+        default: return z;
+    }
+}
+static inline float adh_act_bwd(int act, float z, float g) {
+    switch (act) {
+        case ADH_ACT_RELU: return z > 0.f ? g : 0.f;
+        case ADH_ACT_RELU6: return (z > 0.f && z < 6.f) ? g : 0.f;
+        case ADH_ACT_HARDSWISH: return z <= -3.f ? 0.f : (z < 3.f ? g * (z / 3.f + 0.5f) : g);
+        case ADH_ACT_HARDSIGMOID: return (z > -3.f && z < 3.f) ? g / 6.f : 0.f;
+        default: return g;
+    }
+}
+static inline bool adh_act_host_valid(int act) { return adh_act_valid(act); }
+// __shfl_xor(v, mask, 64): lanes t and t ^ mask exchange through one mailbox per lane and wait for nobody else, so a pair may
+// shuffle inside a loop the rest of its workgroup has already left (bn_apply_kernel).  A lane's n-th shuffle posts into slot
+// n & 1 and publishes n + 1; its partner cannot post n + 2 before it has read n, so two slots are enough.  A lane whose
+// partner has left the kernel waits for ever: the tests run every driver under a timeout.
+struct emu_mailbox {
+    std::atomic<unsigned> seq;
+    int val[2];
+};
+extern emu_mailbox emu_mail[1024];           // stream_rt.cpp clears them before every launch
+extern thread_local unsigned emu_shfl_count;
+static inline int __shfl_xor(int v, int mask, int width) {
+    (void)width;
+    const unsigned n = emu_shfl_count++;
+    emu_mailbox& mine = emu_mail[threadIdx.x];
+    emu_mailbox& theirs = emu_mail[threadIdx.x ^ (unsigned)mask];
+    mine.val[n & 1] = v;
+    mine.seq.store(n + 1, std::memory_order_release);
+    while (theirs.seq.load(std::memory_order_acquire) < n + 1) std::this_thread::yield();
+    return theirs.val[n & 1];
 }
 #endif
