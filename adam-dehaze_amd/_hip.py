@@ -240,6 +240,8 @@ _SIGNATURES = {
     "adh_bn_fold_moments": [vp, i32, vp, vp, f64, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp],
     "adh_avgpool2_bwd": [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32],
     "adh_bn_preact_bwd_accum": [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, i32, i64, i32, i32],
+    "adh_u8_to_image": [vp, vp, i64, i64, i32, i32, i32, i32, vp],
+    "adh_image_to_u8": [vp, vp, i32, i32, i32, vp, i64, i64, i32],
 }
 
 # functions that return a count / size rather than a status code

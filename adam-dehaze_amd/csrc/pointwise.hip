@@ -310,9 +310,26 @@ __global__ __launch_bounds__(256) void soft_blend_kernel(const float* __restrict
     }
 }
 
+// per % 4 != 0 (an image file whose H * W is no multiple of 4: inference only): the images of a batch do not all start on
+// 16-byte boundaries, so every lane moves single floats; the expression is soft_blend_kernel's
+__global__ __launch_bounds__(256) void soft_blend_scalar_kernel(const float* __restrict__ w, const float* __restrict__ o0,
+                                                                const float* __restrict__ o1, const float* __restrict__ o2,
+                                                                int64_t per, float* __restrict__ out) {
+    const int n = blockIdx.y;
+    const float w0 = w[n * 3], w1 = w[n * 3 + 1], w2 = w[n * 3 + 2];
+    const int64_t base = (int64_t)n * per;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per; i += (int64_t)gridDim.x * blockDim.x)
+        out[base + i] = (o0[base + i] * w0 + o1[base + i] * w1) + o2[base + i] * w2;
+}
+
 extern "C" int adh_soft_blend(void* stream, const float* weights, const float* o0, const float* o1, const float* o2, int N,
                               int64_t per, float* out) {
-    if (!weights || !o0 || !o1 || !o2 || !out || N < 1 || per < 4 || (per & 3)) return ADH_E_ARG;
+    if (!weights || !o0 || !o1 || !o2 || !out || N < 1 || per < 1) return ADH_E_ARG;
+    if (per & 3) {
+        hipLaunchKernelGGL(soft_blend_scalar_kernel, dim3(adh_min_i(adh_ceil_div(per, 256), 2048), N), dim3(256), 0,
+                           (hipStream_t)stream, weights, o0, o1, o2, per, out);
+        return adh_check_launch();
+    }
     const int64_t per4 = per / 4;
     hipLaunchKernelGGL(soft_blend_kernel, dim3(adh_min_i(adh_ceil_div(per4, 256), 2048), N), dim3(256), 0,
                        (hipStream_t)stream, weights, o0, o1, o2, per4, out);
@@ -409,15 +426,34 @@ __global__ __launch_bounds__(256) void gather_images_kernel(const float* __restr
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per4; i += (int64_t)gridDim.x * blockDim.x) d[i] = s[i];
 }
 
+// per % 4 != 0: single floats, as in soft_blend_scalar_kernel
+__global__ __launch_bounds__(256) void gather_images_scalar_kernel(const float* __restrict__ src, const int32_t* __restrict__ sel,
+                                                                   int64_t per, float* __restrict__ dst, int scatter) {
+    const int j = blockIdx.y;
+    const int n = sel[j];
+    const float* s = src + (int64_t)(scatter ? j : n) * per;
+    float* d = dst + (int64_t)(scatter ? n : j) * per;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per; i += (int64_t)gridDim.x * blockDim.x) d[i] = s[i];
+}
+
+static int gather_images_scalar(void* stream, const float* src, const int32_t* sel, int count, int64_t per, float* dst,
+                                int scatter) {
+    hipLaunchKernelGGL(gather_images_scalar_kernel, dim3(adh_min_i(adh_ceil_div(per, 256), 1024), count), dim3(256), 0,
+                       (hipStream_t)stream, src, sel, per, dst, scatter);
+    return adh_check_launch();
+}
+
 extern "C" int adh_gather_images(void* stream, const float* src, const int32_t* sel, int count, int64_t per, float* dst) {
-    if (!src || !sel || !dst || count < 1 || per < 4 || (per & 3)) return ADH_E_ARG;
+    if (!src || !sel || !dst || count < 1 || per < 1) return ADH_E_ARG;
+    if (per & 3) return gather_images_scalar(stream, src, sel, count, per, dst, 0);
     hipLaunchKernelGGL(gather_images_kernel, dim3(adh_min_i(adh_ceil_div(per / 4, 256), 1024), count), dim3(256), 0,
                        (hipStream_t)stream, src, sel, per / 4, dst, 0);
     return adh_check_launch();
 }
 
 extern "C" int adh_scatter_images(void* stream, const float* src, const int32_t* sel, int count, int64_t per, float* dst) {
-    if (!src || !sel || !dst || count < 1 || per < 4 || (per & 3)) return ADH_E_ARG;
+    if (!src || !sel || !dst || count < 1 || per < 1) return ADH_E_ARG;
+    if (per & 3) return gather_images_scalar(stream, src, sel, count, per, dst, 1);
     hipLaunchKernelGGL(gather_images_kernel, dim3(adh_min_i(adh_ceil_div(per / 4, 256), 1024), count), dim3(256), 0,
                        (hipStream_t)stream, src, sel, per / 4, dst, 1);
     return adh_check_launch();

@@ -1,0 +1,181 @@
+"""Image files through the routed system: 8-bit interleaved pixels to the fp32 planes of the branches and back on the HIP kernels of
+csrc/image_io.hip, Pillow for the files themselves, and `dehaze_files`, the body of `main.py --mode demo --input ...`.
+
+The kernels take a base pointer and two byte pitches, so a crop of an 8-bit tensor is read, and one pane of a side-by-side panel
+is written, in place: `u8_to_image` / `image_to_u8` turn the strides of a view into those pitches.  Images are processed at their
+own size; nothing is resized."""
+from __future__ import annotations
+
+import os
+import warnings
+from typing import Dict, Iterable, List, Optional, Tuple
+
+import torch
+
+from . import _hip as H
+
+_NAMES = ("low", "medium", "high")
+MIN_SIDE = 16          # the branches halve the frame more than once: smaller files are skipped
+
+
+def _u8_view(t: torch.Tensor, what: str) -> Tuple[torch.Tensor, int, int]:
+    """`t` as a 4-D view with its (row_pitch, image_pitch) in bytes"""
+    if not t.is_cuda or t.dtype != torch.uint8:
+        raise RuntimeError(f"adam-dehaze_amd: {what} must be a uint8 tensor on a cuda device, got {t.dtype} on {t.device} "
+                           "(no CPU fallback)")
+    if t.dim() == 3:
+        t = t.unsqueeze(0)
+    if t.dim() != 4:
+        raise ValueError(f"{what} must be [N,H,W,C] or [H,W,C], got {tuple(t.shape)}")
+    N, h, w, c = t.shape
+    if t.stride(3) != 1 or t.stride(2) != c:
+        raise ValueError(f"{what}: the last two dimensions must be dense (strides {t.stride()} for shape {tuple(t.shape)})")
+    row_pitch = t.stride(1) if h > 1 else w * c        # the stride of a dimension of size 1 means nothing
+    return t, row_pitch, t.stride(0) if N > 1 else h * row_pitch
+
+
+def u8_to_image(t: torch.Tensor) -> torch.Tensor:
+    """uint8 [N,H,W,C] or [H,W,C] on the device (C = 1 grey, 3 RGB, 4 RGBA with alpha ignored), or any view of one whose last
+    two dimensions are dense -> float32 [N,3,H,W], each value exactly v / 255."""
+    t, row_pitch, image_pitch = _u8_view(t, "u8_to_image input")
+    N, h, w, c = t.shape
+    out = torch.empty((N, 3, h, w), device=t.device, dtype=torch.float32)
+    H.call("adh_u8_to_image", t.data_ptr(), row_pitch, image_pitch, N, h, w, c, out.data_ptr())
+    return out
+
+
+def image_to_u8(x: torch.Tensor, out: Optional[torch.Tensor] = None, channels: int = 3) -> torch.Tensor:
+    """float32 [N,3,H,W] -> uint8 [N,H,W,C], round-half-even of clamp(x, 0, 1) * 255 (NaN gives 0), alpha 255 when C = 4.
+    `out`: a uint8 [N,H,W,C] (or [H,W,C] for N = 1) view to write into, e.g. one pane of a wider panel; bytes of its storage
+    outside the view are left alone.  Returns `out`, or a new dense tensor."""
+    H.require_cuda(x, "image_to_u8 input")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"image_to_u8 input must be [N,3,H,W], got {tuple(x.shape)}")
+    x = x.contiguous()
+    N, _, h, w = x.shape
+    if out is None:
+        out = torch.empty((N, h, w, channels), device=x.device, dtype=torch.uint8)
+    view, row_pitch, image_pitch = _u8_view(out, "image_to_u8 output")
+    if tuple(view.shape[:3]) != (N, h, w):
+        raise ValueError(f"image_to_u8: output view {tuple(out.shape)} does not match input {tuple(x.shape)}")
+    H.call("adh_image_to_u8", x.data_ptr(), N, h, w, view.data_ptr(), row_pitch, image_pitch, view.shape[3])
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- files
+def _pil():
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise RuntimeError("reading and writing image files needs Pillow (the PIL package), which is not installed") from e
+    return Image
+
+
+def image_size(path: str) -> Tuple[int, int]:
+    """(height, width) from the file's header"""
+    with _pil().open(path) as im:
+        return im.height, im.width
+
+
+def load_image(path: str) -> torch.Tensor:
+    """An image file as a uint8 [H,W,C] CPU tensor.  Modes L, RGB and RGBA arrive as they are (C = 1, 3, 4); every other mode
+    (palette, CMYK, 16-bit, ...) goes through Pillow's convert("RGB") on the host.  The EXIF orientation tag is NOT applied:
+    pixels come in file order."""
+    import numpy as np
+    with _pil().open(path) as im:
+        if im.mode not in ("L", "RGB", "RGBA"):
+            im = im.convert("RGB")
+        a = np.array(im, dtype=np.uint8)
+    t = torch.from_numpy(a)
+    return t.unsqueeze(-1) if t.dim() == 2 else t
+
+
+def save_image(path: str, u8: torch.Tensor) -> None:
+    """uint8 [H,W,C] (C = 1, 3 or 4) to a file whose format the extension of `path` names"""
+    if u8.dim() != 3 or u8.shape[2] not in (1, 3, 4) or u8.dtype != torch.uint8:
+        raise ValueError(f"save_image takes uint8 [H,W,C] with C = 1, 3 or 4, got {u8.dtype} {tuple(u8.shape)}")
+    a = u8.cpu().contiguous().numpy()
+    _pil().fromarray(a[:, :, 0] if a.shape[2] == 1 else a).save(path)      # L, RGB or RGBA from the array's shape
+
+
+# ---------------------------------------------------------------------------------------------------------------- routing
+def routing_records(aux: Dict) -> List[Dict]:
+    """One record per image from what any of the three routers returns beside its output: `routing` (hard | soft | gated),
+    `weights` (three floats: one-hot for the hard router, the blend weights otherwise) and `intensity` (the arg-max's name)."""
+    if "intensity" in aux:
+        kind, w = "hard", torch.nn.functional.one_hot(aux["intensity"].to(torch.int64), 3).to(torch.float32)
+    elif "weights" in aux:
+        kind, w = "soft", aux["weights"]
+    elif "gate_weights" in aux:
+        kind, w = "gated", aux["gate_weights"]
+    else:
+        raise KeyError(f"no routing decision among the router's keys {sorted(aux)}")
+    rows = w.detach().cpu().tolist()                    # one read-back per batch
+    return [{"routing": kind, "weights": [float(v) for v in r], "intensity": _NAMES[max(range(3), key=r.__getitem__)]}
+            for r in rows]
+
+
+# ---------------------------------------------------------------------------------------------------------------- demo
+def plan_chunks(sizes: Dict[str, Tuple[int, int]], batch_size: int) -> List[List[str]]:
+    """The paths of `sizes` (path -> (H, W)) sorted, grouped by size in sorted order, each group cut into chunks of at most
+    `batch_size`; files whose shorter side is under MIN_SIDE are left out with a warning that names them."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be at least 1, got {batch_size}")
+    groups: Dict[Tuple[int, int], List[str]] = {}
+    for p in sorted(sizes):
+        if min(sizes[p]) < MIN_SIDE:
+            warnings.warn(f"{p}: {sizes[p][0]}x{sizes[p][1]} is smaller than {MIN_SIDE} pixels on a side; skipped")
+            continue
+        groups.setdefault(tuple(sizes[p]), []).append(p)
+    return [g[i:i + batch_size] for g in groups.values() for i in range(0, len(g), batch_size)]
+
+
+def _stack(images: List[torch.Tensor]) -> torch.Tensor:
+    """[N,H,W,C] from images of one size; where their channel counts differ, all become RGB on the host (grey replicated, alpha
+    dropped: what the kernel would have done)"""
+    if len({im.shape[2] for im in images}) > 1:
+        images = [im.expand(-1, -1, 3) if im.shape[2] == 1 else im[:, :, :3] for im in images]
+    return torch.stack(images)
+
+
+def dehaze_batch(system: Dict, u8: torch.Tensor, panels: bool = False):
+    """uint8 [N,H,W,C] on the host -> (dehazed uint8 [N,H,W,3] on the host, hazy | dehazed panels [N,H,2W,3] or None, routing
+    records).  One copy to the device, the unpack kernel, the router, the pack kernel, one copy back; with `panels` the pack
+    kernel writes both panes into one buffer through pointer and pitch, and the dehazed image is the right pane."""
+    dev = system["device"]
+    x = u8_to_image(u8.to(dev))
+    with torch.no_grad():
+        y, aux = system["router"](x)
+    if not panels:
+        return image_to_u8(y).cpu(), None, routing_records(aux)
+    N, _, h, w = x.shape
+    panel = torch.empty((N, h, 2 * w, 3), device=dev, dtype=torch.uint8)
+    image_to_u8(x, out=panel[:, :, :w])                # v -> v / 255 -> v: the hazy pane is the file's pixels again
+    image_to_u8(y, out=panel[:, :, w:])
+    panel = panel.cpu()
+    return panel[:, :, w:], panel, routing_records(aux)
+
+
+def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: int = 4, panels: bool = False) -> List[Dict]:
+    """Dehaze image files through `system["router"]` (eval mode, no_grad) at their own size and write `<out_dir>/<name>.png` --
+    with `panels` also `<name>_panel.png`, hazy | dehazed -- for every input `<name>.<ext>`.  Files of equal size go through
+    together, `batch_size` at a time.  Returns one dict per processed file, in sorted order: `file`, `height`, `width` and the
+    routing decision of `routing_records`."""
+    paths = sorted(str(p) for p in paths)
+    names = [os.path.splitext(os.path.basename(p))[0] for p in paths]
+    twice = sorted({n for n in names if names.count(n) > 1})
+    if twice:
+        raise ValueError(f"input files share a base name and would overwrite each other's output: {', '.join(twice)}")
+    sizes = {p: image_size(p) for p in paths}
+    os.makedirs(out_dir, exist_ok=True)
+    system["router"].eval()
+    results = []
+    for chunk in plan_chunks(sizes, batch_size):
+        out, panel, records = dehaze_batch(system, _stack([load_image(p) for p in chunk]), panels)
+        for i, (p, rec) in enumerate(zip(chunk, records)):
+            name = os.path.splitext(os.path.basename(p))[0]
+            save_image(os.path.join(out_dir, name + ".png"), out[i])
+            if panel is not None:
+                save_image(os.path.join(out_dir, name + "_panel.png"), panel[i])
+            results.append({"file": p, "height": sizes[p][0], "width": sizes[p][1], **rec})
+    return sorted(results, key=lambda r: r["file"])

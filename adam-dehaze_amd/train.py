@@ -907,6 +907,39 @@ def run_comprehensive_evaluation(config, steps: int = 2, use_lpips: bool = True)
     return comprehensive
 
 
+DEMO_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp")
+
+
+def run_demo(config, input: str, output: str = "demo", panels: bool = False):
+    """main.py:152-217 of the reference loads every checkpoint and stops at a TODO (load sample hazy images, classify, dehaze
+    through the router, visualise); this is that mode.  `input` is one image file or a directory whose *.png / *.jpg / *.jpeg /
+    *.bmp files are taken; every image goes through the routed system at its own size (image_io.dehaze_files, `demo.batch_size`
+    of the config at a time) and comes out as `<output>/<name>.png`, with `panels` also as `<name>_panel.png` (hazy | dehazed).
+    `<output>/demo_results.json` lists file, size and routing decision per image.  Single process only."""
+    import json
+    from .image_io import dehaze_files
+    if _world_rank()[0] > 1:
+        raise SystemExit("--mode demo runs in a single process.  Run it without torchrun (WORLD_SIZE=1).")
+    if os.path.isdir(input):
+        paths = sorted(os.path.join(input, f) for f in os.listdir(input) if f.lower().endswith(DEMO_EXTENSIONS))
+    elif os.path.isfile(input):
+        paths = [input]
+    else:
+        raise SystemExit(f"--input {input}: no such file or directory")
+    if not paths:
+        raise SystemExit(f"--input {input}: no {' / '.join('*' + e for e in DEMO_EXTENSIONS)} files")
+    system, _ = _joint_system_for_evaluation(config)
+    batch_size = int((config.get("demo") or {}).get("batch_size", 4))
+    results = dehaze_files(system, paths, output, batch_size=batch_size, panels=panels)
+    for r in results:
+        print(f"{r['file']}: {r['height']}x{r['width']}  {r['routing']} routing -> {r['intensity']}  weights "
+              + " ".join(f"{w:.3f}" for w in r["weights"]))
+    with open(os.path.join(output, "demo_results.json"), "w") as f:
+        json.dump(results, f, indent=2)
+    print(f"{len(results)} of {len(paths)} images dehazed into {output}/ (demo_results.json lists them)")
+    return results
+
+
 @_rank0_only
 def evaluate_detection(config, test_loader=None, steps: int = 1, score_threshold: float = 0.5, annotation_file=None):
     """Detection half of evaluation/evaluate.py:179-383 on device: the detector on the hazy frames and on the routed (dehazed)

@@ -390,7 +390,9 @@ int adh_head_blend_bwd(void* stream, int mode, const float* g_out_nchw, const fl
 int adh_head_blend_bwd_num_blocks(int N, int H, int W);
 
 /* ---- routing (models/routing.py:41-61,110-127) ----------------------------------------------------- */
-/* weights[n][3] = softmax(logits[n]/T); out = sum_i weights[n][i]*branch_i  (NCHW images, per = 3*H*W) */
+/* weights[n][3] = softmax(logits[n]/T); out = sum_i weights[n][i]*branch_i  (NCHW images, per = 3*H*W).  adh_soft_blend,
+ * adh_gather_images and adh_scatter_images take any per >= 1 (a per that is no multiple of 4 moves single floats: image files of
+ * odd size at inference); adh_soft_blend_bwd needs per % 4 == 0. */
 int adh_softmax3(void* stream, const float* logits, float temperature, int N, float* weights);
 /* g_logits[n][3] from the blend's weight gradients: gw[n][i] = sum_blk gw_partial[n][blk][i];
  * g_logits = w * (gw - sum_j gw_j w_j) / T  (softmax backward, routing.py:111) */
@@ -681,6 +683,24 @@ int adh_avgpool2_bwd(void* stream, const float* g, int g_cs, int N, int H, int W
 int adh_bn_preact_bwd_accum(void* stream, const float* dA, int dA_cs, const float* x, int x_cs, const float* ss,
                             const float* mean, const float* invstd, const float* coef, int training, float* dbuf, int dbuf_cs,
                             int64_t P, int C, int accumulate);
+
+/* ---- 8-bit image files (csrc/image_io.hip): what stands between a decoded image file and the fp32 planes of the branches ---
+ * The 8-bit side is interleaved: pixel (n, y, x) is the C bytes at base + n * image_pitch + y * row_pitch + x * C.  Both
+ * pitches are in bytes and may exceed W * C and H * row_pitch; the base may have any byte alignment, so a crop or one pane of
+ * a side-by-side panel is a pointer offset plus the pitch of the whole.  Bytes between W * C and row_pitch, and everything
+ * outside the addressed rectangle, are never read by adh_u8_to_image and never written by adh_image_to_u8.  The fp32 side is
+ * dense [N,3,H,W].  image_pitch is not looked at when N == 1.  One launch covers the batch.
+ *   adh_u8_to_image   value = (float)v / 255.0f, correctly rounded, for every v in 0..255.  C == 1 replicates grey into the
+ *                     three planes, C == 3 is RGB, C == 4 ignores the alpha byte.
+ *   adh_image_to_u8   byte = rint(min(max(x, 0), 1) * 255) in fp32: one rounding for the product, halves to even: what torch
+ *                     computes on the CPU for (x.clamp(0, 1) * 255).round().to(torch.uint8), for every finite x and +-inf.
+ *                     NaN writes 0.  C == 3, or C == 4 with alpha = 255.
+ * ADH_E_ARG (nothing is launched) for N, H or W <= 0, a C outside these sets, row_pitch < W * C, image_pitch < H * row_pitch
+ * when N > 1, or a null pointer. */
+int adh_u8_to_image(void* stream, const uint8_t* src, int64_t row_pitch, int64_t image_pitch, int N, int H, int W, int C,
+                    float* dst_nchw);
+int adh_image_to_u8(void* stream, const float* src_nchw, int N, int H, int W, uint8_t* dst, int64_t row_pitch,
+                    int64_t image_pitch, int C);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@ the hot path run on the HIP engine; dataset preprocessing is outside this build'
     python main.py --mode train_classifier                         # fog-intensity classifier: train, then evaluate
     python main.py --mode train_joint --resume                     # continue from the latest checkpoint
     torchrun --nproc-per-node 8 main.py --mode train_joint        # data-parallel over RCCL
+    python main.py --mode demo --input DIR --output OUT --panels   # dehaze image files at their own size
 
 `--resume` is the reference's flag (main.py:50-51 parses it and never reads it); here it restores model, optimiser,
 scheduler, epoch and best-PSNR from the latest checkpoint of the mode's checkpoint directory (or from the file given
@@ -34,6 +35,10 @@ def parse_args():
                    help="resume training from the latest checkpoint (or from the given checkpoint file)")
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--epochs", type=int, default=None, help="override the configured number of epochs")
+    p.add_argument("--input", type=str, default=None,
+                   help="--mode demo: an image file, or a directory of *.png / *.jpg / *.jpeg / *.bmp files, to dehaze")
+    p.add_argument("--output", type=str, default="demo", help="--mode demo: where the dehazed images and demo_results.json go")
+    p.add_argument("--panels", action="store_true", help="--mode demo: also write <name>_panel.png, hazy | dehazed")
     return p.parse_args()
 
 
@@ -69,6 +74,8 @@ def main():
         if args.resume is not None:
             raise SystemExit("--resume is not supported for --mode train_classifier: the classifier stage always trains from "
                              "scratch (drop --resume).")
+    if args.mode == "demo" and args.input and world > 1:
+        raise SystemExit("--mode demo runs in a single process.  Run it without torchrun (WORLD_SIZE=1).")
     if world > 1:
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -132,13 +139,17 @@ def main():
         # evaluate.py:464-540 (the reference first rewrites the checkpoint paths to a hard-coded experiment directory, main.py:143-145:
         # here the paths of the config are used as they are)
         T.run_comprehensive_evaluation(config)   # baseline branches, routed system, detector on hazy vs dehazed frames
+    elif args.mode == "demo" and args.input:
+        T.run_demo(config, args.input, args.output, args.panels)
     elif args.mode == "demo":
+        # without --input: one synthetic batch through the router
+        from adam_dehaze_amd.image_io import routing_records
         system = T.build_joint_system(config)
         system["router"].eval()
         batch = next(T.synthetic_loader(2, config["dataset"]["img_size"], 1, seed=config["seed"], device=config["device"]))
         with torch.no_grad():
             out, aux = system["router"](batch["hazy"])
-        print("dehazed", tuple(out.shape), "weights", aux["weights"].cpu().tolist())
+        print("dehazed", tuple(out.shape), "weights", [r["weights"] for r in routing_records(aux)])
     else:
         raise SystemExit(f"mode '{args.mode}' is outside the hot path this build covers (see DESIGN.md section 7)")
     if world > 1:

@@ -6,7 +6,7 @@
 // -DADH_HOST_EMU (the section at the end), by tests/test_wgrad_reduce_hostemu_cpu.py on a copy of csrc/conv_wgrad_reduce.hip and
 // by tests/test_ema_hostemu_cpu.py on a copy of csrc/ema.hip; with -DADH_HOST_EMU_DYN_LDS on top (the last section), by
 // tests/test_fft_loss_hostemu_cpu.py on a copy of csrc/fft_loss.hip; with -DADH_HOST_EMU_STREAM on top of ADH_HOST_EMU (the section
-// after it), by tests/test_{bn_act,depthwise,densenet}_hostemu_cpu.py on copies of the three streaming kernel files.
+// after it), by tests/test_{bn_act,depthwise,densenet,image_io}_hostemu_cpu.py on copies of the four streaming kernel files.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -93,13 +93,14 @@ static inline void sincospif(float x, float* s, float* c) {
 #endif
 
 #ifdef ADH_HOST_EMU_STREAM
-// What csrc/bn_act.hip, csrc/depthwise.hip and csrc/densenet.hip take beyond the ADH_HOST_EMU section; their drivers link
+// What csrc/bn_act.hip, csrc/depthwise.hip, csrc/densenet.hip and csrc/image_io.hip take beyond the ADH_HOST_EMU section; their drivers link
 // stream_rt.cpp, whose emu_launch walks grid.x, grid.y and grid.z.  The non-temporal builtins are plain loads and stores.  The
 // activation helpers are copies of csrc/common.h's: keep them the same.
 #include <atomic>
 #define __builtin_nontemporal_load(p) (*(p))
 #define __builtin_nontemporal_store(v, p) (*(p) = (v))
 static inline int adh_max_i(int a, int b) { return a > b ? a : b; }
+static inline float __fmul_rn(float a, float b) { return a * b; }   // csrc/image_io.hip: a product nothing is contracted into
 static inline bool adh_act_valid(int act) {
     return act == ADH_ACT_NONE || act == ADH_ACT_RELU || act == ADH_ACT_RELU6 || act == ADH_ACT_HARDSWISH ||
            act == ADH_ACT_HARDSIGMOID;
