@@ -1,5 +1,6 @@
 """Image files through the routed system: 8-bit interleaved pixels to the fp32 planes of the branches and back on the HIP kernels of
-csrc/image_io.hip, Pillow for the files themselves, and `dehaze_files`, the body of `main.py --mode demo --input ...`.
+csrc/image_io.hip, Pillow for the files themselves, and `dehaze_files`, the body of `main.py --mode demo --input ...`; with `--target`,
+`pair_targets` finds each input's ground-truth file and `score_batch` scores the written file against it (PSNR, SSIM, CIEDE2000).
 
 The kernels take a base pointer and two byte pitches, so a crop of an 8-bit tensor is read, and one pane of a side-by-side panel
 is written, in place: `u8_to_image` / `image_to_u8` turn the strides of a view into those pitches.  Images are processed at their
@@ -138,29 +139,125 @@ def _stack(images: List[torch.Tensor]) -> torch.Tensor:
     return torch.stack(images)
 
 
-def dehaze_batch(system: Dict, u8: torch.Tensor, panels: bool = False):
-    """uint8 [N,H,W,C] on the host -> (dehazed uint8 [N,H,W,3] on the host, hazy | dehazed panels [N,H,2W,3] or None, routing
-    records).  One copy to the device, the unpack kernel, the router, the pack kernel, one copy back; with `panels` the pack
-    kernel writes both panes into one buffer through pointer and pitch, and the dehazed image is the right pane."""
+def _dehaze_on_device(system: Dict, u8: torch.Tensor, panels: bool):
+    """uint8 [N,H,W,C] on the host -> (hazy fp32 [N,3,H,W], dehazed uint8 [N,H,W,3] view, panel uint8 [N,H,2W,3] or None, routing
+    records), the tensors on the device.  One copy to the device, the unpack kernel, the router, the pack kernel; with `panels`
+    the pack kernel writes both panes into one buffer through pointer and pitch, and the dehazed image is the right pane."""
     dev = system["device"]
     x = u8_to_image(u8.to(dev))
     with torch.no_grad():
         y, aux = system["router"](x)
     if not panels:
-        return image_to_u8(y).cpu(), None, routing_records(aux)
+        return x, image_to_u8(y), None, routing_records(aux)
     N, _, h, w = x.shape
     panel = torch.empty((N, h, 2 * w, 3), device=dev, dtype=torch.uint8)
     image_to_u8(x, out=panel[:, :, :w])                # v -> v / 255 -> v: the hazy pane is the file's pixels again
     image_to_u8(y, out=panel[:, :, w:])
+    return x, panel[:, :, w:], panel, routing_records(aux)
+
+
+def dehaze_batch(system: Dict, u8: torch.Tensor, panels: bool = False):
+    """uint8 [N,H,W,C] on the host -> (dehazed uint8 [N,H,W,3] on the host, hazy | dehazed panels [N,H,2W,3] or None, routing
+    records): `_dehaze_on_device` and one copy back."""
+    _, out, panel, records = _dehaze_on_device(system, u8, panels)
+    if panel is None:
+        return out.cpu(), None, records
     panel = panel.cpu()
-    return panel[:, :, w:], panel, routing_records(aux)
+    return panel[:, :, panel.shape[2] // 2:], panel, records
 
 
-def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: int = 4, panels: bool = False) -> List[Dict]:
+# ---------------------------------------------------------------------------------------------------------------- ground truth
+DEMO_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp")
+SCORE_KEYS = ("psnr", "ssim", "ciede2000", "hazy_psnr", "hazy_ssim", "hazy_ciede2000")
+
+
+def pair_targets(paths: Iterable[str], target: str) -> Dict[str, Dict]:
+    """The ground-truth file of every input of `--mode demo --target`: input path -> the fields its record gains.  `target` is a
+    directory, whose *.png / *.jpg / *.jpeg / *.bmp files are matched to the inputs by base name without extension (hazy
+    `x.jpg` finds clear `x.png`), or one file, which is the target of a single input whatever its name and otherwise of the
+    input that shares its base name.
+        {"target": path}                                                   to be scored
+        {"target": path, "scored": False, "reason": "size HxW != HxW"}     the target is of another size (input != target)
+        {"target": None}                                                   no target; warned about
+    Two files of one base name in the target directory are a ValueError that names them.  Only file headers are read."""
+    paths = [str(p) for p in paths]
+    base = lambda p: os.path.splitext(os.path.basename(p))[0]
+    if os.path.isdir(target):
+        found: Dict[str, List[str]] = {}
+        for f in sorted(os.listdir(target)):
+            if f.lower().endswith(DEMO_EXTENSIONS):
+                found.setdefault(base(f), []).append(os.path.join(target, f))
+        twice = [fs for n, fs in sorted(found.items()) if len(fs) > 1]
+        if twice:
+            raise ValueError("target files share a base name, so the ground truth of an input would be ambiguous: "
+                             + "; ".join(", ".join(fs) for fs in twice))
+        by_name = {n: fs[0] for n, fs in found.items()}
+    elif os.path.isfile(target):
+        by_name = {base(target): target}
+        if len(paths) == 1:
+            by_name[base(paths[0])] = target
+    else:
+        raise ValueError(f"--target {target}: no such file or directory")
+    pairs: Dict[str, Dict] = {}
+    for p in paths:
+        t = by_name.get(base(p))
+        if t is None:
+            warnings.warn(f"{p}: no target named {base(p)}.* under {target}; dehazed but not scored")
+            pairs[p] = {"target": None}
+            continue
+        (h, w), (th, tw) = image_size(p), image_size(t)
+        pairs[p] = {"target": t} if (h, w) == (th, tw) else \
+            {"target": t, "scored": False, "reason": f"size {h}x{w} != {th}x{tw}"}
+    return pairs
+
+
+def score_batch(hazy: torch.Tensor, dehazed_u8: torch.Tensor, target_u8: torch.Tensor) -> List[Dict]:
+    """The six scores of every image of a chunk, all on the device with one read-back: `hazy` fp32 [n,3,H,W] (the unpacked
+    input), `dehazed_u8` uint8 [n,H,W,3] (the packed output, i.e. the pixels of the written file) and `target_u8` uint8
+    [n,H,W,C], both on the device.  The dehazed side is `u8_to_image` of the packed bytes, exactly v / 255, not the router's
+    fp32 output: a score can be recomputed from the two files alone.  An infinite PSNR (identical images) becomes None."""
+    from .metrics import ciede2000_batch, psnr_batch, ssim_batch
+    tgt = u8_to_image(target_u8)
+    rows = []
+    for img in (u8_to_image(dehazed_u8), hazy):
+        rows += [psnr_batch(img, tgt), ssim_batch(img, tgt), ciede2000_batch(img, tgt)]
+    host = torch.stack(rows).double().cpu().tolist()                        # [6][n]
+    return [{k: (None if k.endswith("psnr") and host[j][i] == float("inf") else host[j][i]) for j, k in enumerate(SCORE_KEYS)}
+            for i in range(tgt.shape[0])]
+
+
+def summarize_scores(records: Iterable[Dict]) -> Dict:
+    """`demo_scores.json`: the schema of ImageQualityMetrics.save_results twice over, {"dehazed": {category: {psnr, ssim,
+    ciede2000, samples}}, "hazy": {...}}, over the scored records; the category is the routed intensity (`low_intensity`, ...)
+    plus `all`.  Infinite PSNRs (None in the records) are left out of the PSNR mean and counted as `psnr_infinite`, a key that
+    appears only where there are any; a category in which every PSNR is infinite has `psnr: null`."""
+    scored = [r for r in records if r.get("scored")]
+    out: Dict[str, Dict] = {"dehazed": {}, "hazy": {}}
+    for side, prefix in (("dehazed", ""), ("hazy", "hazy_")):
+        for cat in sorted({r["intensity"] + "_intensity" for r in scored}) + ["all"]:
+            rs = [r for r in scored if cat == "all" or r["intensity"] + "_intensity" == cat]
+            if not rs:
+                continue
+            finite = [r[prefix + "psnr"] for r in rs if r[prefix + "psnr"] is not None]
+            entry = {"psnr": sum(finite) / len(finite) if finite else None,
+                     "ssim": sum(r[prefix + "ssim"] for r in rs) / len(rs),
+                     "ciede2000": sum(r[prefix + "ciede2000"] for r in rs) / len(rs), "samples": len(rs)}
+            if len(finite) < len(rs):
+                entry["psnr_infinite"] = len(rs) - len(finite)
+            out[side][cat] = entry
+    return out
+
+
+def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: int = 4, panels: bool = False,
+                 targets: Optional[Dict[str, Dict]] = None) -> List[Dict]:
     """Dehaze image files through `system["router"]` (eval mode, no_grad) at their own size and write `<out_dir>/<name>.png` --
     with `panels` also `<name>_panel.png`, hazy | dehazed -- for every input `<name>.<ext>`.  Files of equal size go through
     together, `batch_size` at a time.  Returns one dict per processed file, in sorted order: `file`, `height`, `width` and the
-    routing decision of `routing_records`."""
+    routing decision of `routing_records`.
+    `targets` (what `pair_targets` returns): every record also gains the fields of its entry there, and each input with a target
+    of its size is scored against it -- `scored: True` and the six numbers of `score_batch`: `psnr`, `ssim`, `ciede2000` of the
+    written file, `hazy_psnr`, `hazy_ssim`, `hazy_ciede2000` of the input.  A chunk's targets go to the device once and its
+    scores come back in one read."""
     paths = sorted(str(p) for p in paths)
     names = [os.path.splitext(os.path.basename(p))[0] for p in paths]
     twice = sorted({n for n in names if names.count(n) > 1})
@@ -171,11 +268,31 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
     system["router"].eval()
     results = []
     for chunk in plan_chunks(sizes, batch_size):
-        out, panel, records = dehaze_batch(system, _stack([load_image(p) for p in chunk]), panels)
+        u8 = _stack([load_image(p) for p in chunk])
+        extra: List[Dict] = [{} for _ in chunk]
+        if targets is None:
+            out, panel, records = dehaze_batch(system, u8, panels)
+        else:
+            hazy, out, panel, records = _dehaze_on_device(system, u8, panels)
+            extra = [dict(targets.get(p) or {"target": None}) for p in chunk]
+            sel = [i for i, e in enumerate(extra) if e["target"] is not None and e.get("scored", True)]
+            if sel:
+                idx = torch.tensor(sel, device=hazy.device)
+                tgt = _stack([load_image(extra[i]["target"]) for i in sel]).to(hazy.device)
+                whole = len(sel) == len(chunk)
+                scores = score_batch(hazy if whole else hazy.index_select(0, idx),
+                                     out if whole else out.index_select(0, idx), tgt)
+                for i, sc in zip(sel, scores):
+                    extra[i].update(scored=True, **sc)
+            if panel is None:
+                out = out.cpu()
+            else:                                      # one copy back: the dehazed image is the panel's right pane
+                panel = panel.cpu()
+                out = panel[:, :, panel.shape[2] // 2:]
         for i, (p, rec) in enumerate(zip(chunk, records)):
             name = os.path.splitext(os.path.basename(p))[0]
             save_image(os.path.join(out_dir, name + ".png"), out[i])
             if panel is not None:
                 save_image(os.path.join(out_dir, name + "_panel.png"), panel[i])
-            results.append({"file": p, "height": sizes[p][0], "width": sizes[p][1], **rec})
+            results.append({"file": p, "height": sizes[p][0], "width": sizes[p][1], **rec, **extra[i]})
     return sorted(results, key=lambda r: r["file"])

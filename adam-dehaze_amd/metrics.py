@@ -57,19 +57,40 @@ def ssim_batch(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0
     return out
 
 
-def calculate_image_metrics(pred: torch.Tensor, target: torch.Tensor) -> Dict[str, torch.Tensor]:
-    """metrics.py:13-36 for a batch (or one [3,H,W] image): {'psnr': [N], 'ssim': [N]} device tensors."""
+def ciede2000_batch(pred: torch.Tensor, target: torch.Tensor, lab_input: bool = False, return_map: bool = False):
+    """Per-image mean CIEDE2000 colour difference [N] (device tensor) between two sRGB [0,1] batches -- or, with `lab_input`,
+    two batches whose planes are L, a, b -- on the float64 kernel of csrc/ciede2000.hip.  With `return_map` also
+    the per-pixel dE00 [N,H,W].  Not in the reference, which has no colour metric; no gradient."""
+    pred, target = _check_pair(pred, target)
+    N, _, Hh, Ww = pred.shape
+    nblk = H.value("adh_ciede2000_num_blocks", Hh * Ww)
+    partial = torch.empty(N * nblk, device=pred.device, dtype=torch.float64)
+    out = torch.empty(N, device=pred.device, dtype=torch.float32)
+    dmap = torch.empty((N, Hh, Ww), device=pred.device, dtype=torch.float32) if return_map else None
+    H.call("adh_ciede2000", pred.data_ptr(), target.data_ptr(), N, Hh, Ww, 1 if lab_input else 0, partial.data_ptr(), nblk,
+           H.ptr(dmap), out.data_ptr())
+    return (out, dmap) if return_map else out
+
+
+def calculate_image_metrics(pred: torch.Tensor, target: torch.Tensor, ciede2000: bool = False) -> Dict[str, torch.Tensor]:
+    """metrics.py:13-36 for a batch (or one [3,H,W] image): {'psnr': [N], 'ssim': [N]} device tensors; with `ciede2000` also
+    that key."""
     if pred.dim() == 3:
         pred, target = pred.unsqueeze(0), target.unsqueeze(0)
-    return {"psnr": psnr_batch(pred, target), "ssim": ssim_batch(pred, target)}
+    m = {"psnr": psnr_batch(pred, target), "ssim": ssim_batch(pred, target)}
+    if ciede2000:
+        m["ciede2000"] = ciede2000_batch(pred, target)
+    return m
 
 
 class ImageQualityMetrics:
     """metrics.py:38-124: accumulate per-image metrics per category, average, print, save as JSON
-    ({category: {psnr, ssim, lpips, samples}})."""
+    ({category: {psnr, ssim, lpips, samples}}).  `use_ciede2000` adds the key `ciede2000` to every chunk, and so to `results`,
+    the averages, the printed lines and the saved JSON; off by default, which leaves the reference's key sets."""
 
-    def __init__(self, device="cuda", lpips_fn=None, use_lpips: bool = True):
+    def __init__(self, device="cuda", lpips_fn=None, use_lpips: bool = True, use_ciede2000: bool = False):
         self.device = torch.device(device)
+        self.use_ciede2000 = bool(use_ciede2000)
         self.lpips_fn = lpips_fn
         if lpips_fn is None and use_lpips:
             from .loss import PerceptualLoss
@@ -91,7 +112,7 @@ class ImageQualityMetrics:
     def add_batch(self, pred: torch.Tensor, target: torch.Tensor, categories: Optional[Sequence[str]] = None):
         """Whole [N,3,H,W] batches at once; `categories`: one name per image (or None -> 'all').  No host sync."""
         with torch.no_grad():
-            m = calculate_image_metrics(pred, target)
+            m = calculate_image_metrics(pred, target, ciede2000=self.use_ciede2000)
             if self.lpips_fn is not None:
                 # loss.PerceptualLoss maps [0,1] -> [-1,1] itself, i.e. it IS lpips.LPIPS(net='alex')(2p-1, 2t-1) of
                 # metrics.py:69-75

@@ -44,6 +44,7 @@ from .classifier import create_classifier
 from .data import synthetic_loader  # noqa: F401  (re-exported: round-1 callers import it from here)
 from .dehazing import create_high_intensity_model, create_low_intensity_model, create_medium_intensity_model
 from .ema import WeightEMA
+from .image_io import DEMO_EXTENSIONS  # noqa: F401  (the extensions --mode demo lists: .png .jpg .jpeg .bmp)
 from .loss import get_dehazing_loss, get_joint_loss
 from .metrics import psnr_batch, ssim_batch
 from .optim import Adam
@@ -807,6 +808,12 @@ def _joint_system_for_evaluation(config):
     return system, loaded
 
 
+def _ciede2000_switch(config):
+    """`evaluation.ciede2000: true` adds the CIEDE2000 column to the image-quality results; absent or false, the
+    metrics object is built exactly as before and the result files keep the reference's keys."""
+    return {"use_ciede2000": True} if (config.get("evaluation") or {}).get("ciede2000") else {}
+
+
 @_rank0_only
 def evaluate_joint_model(config, test_loader=None, steps: int = 2, use_lpips: bool = True):
     """evaluation/evaluate.py:94-177 (image-quality part): load the joint checkpoint if present, route every test
@@ -817,7 +824,7 @@ def evaluate_joint_model(config, test_loader=None, steps: int = 2, use_lpips: bo
     # writes, the others wait for it in _rank0_only)
     system, _ = _joint_system_for_evaluation(config)
     dev = system["device"]
-    metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips)
+    metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips, **_ciede2000_switch(config))
     test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, dev, warn="evaluate_joint_model")
     with torch.no_grad():
         for batch in test_loader:
@@ -845,7 +852,7 @@ def evaluate_baseline_models(config, test_loader=None, steps: int = 2, use_lpips
                               prefer_ema=_evaluate_ema(config))
         m.eval()
     by_label = {0: system["models"]["low"], 1: system["models"]["medium"], 2: system["models"]["high"]}
-    metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips)
+    metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips, **_ciede2000_switch(config))
     test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, dev, warn="evaluate_baseline_models")
     with torch.no_grad():
         for batch in test_loader:
@@ -907,17 +914,18 @@ def run_comprehensive_evaluation(config, steps: int = 2, use_lpips: bool = True)
     return comprehensive
 
 
-DEMO_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp")
-
-
-def run_demo(config, input: str, output: str = "demo", panels: bool = False):
+def run_demo(config, input: str, output: str = "demo", panels: bool = False, target: Optional[str] = None):
     """main.py:152-217 of the reference loads every checkpoint and stops at a TODO (load sample hazy images, classify, dehaze
     through the router, visualise); this is that mode.  `input` is one image file or a directory whose *.png / *.jpg / *.jpeg /
     *.bmp files are taken; every image goes through the routed system at its own size (image_io.dehaze_files, `demo.batch_size`
     of the config at a time) and comes out as `<output>/<name>.png`, with `panels` also as `<name>_panel.png` (hazy | dehazed).
-    `<output>/demo_results.json` lists file, size and routing decision per image.  Single process only."""
+    `<output>/demo_results.json` lists file, size and routing decision per image.  Single process only.
+    `target`: the ground truth, a directory (matched to the inputs by base name, image_io.pair_targets) or one file.  Every
+    written file is then scored against its target -- PSNR, SSIM and CIEDE2000, and the same three for the hazy input -- the
+    scores are printed and recorded per file, and `<output>/demo_scores.json` holds their means per routed intensity
+    (image_io.summarize_scores).  No LPIPS here: without pretrained weights it would score with a random extractor."""
     import json
-    from .image_io import dehaze_files
+    from . import image_io as IO
     if _world_rank()[0] > 1:
         raise SystemExit("--mode demo runs in a single process.  Run it without torchrun (WORLD_SIZE=1).")
     if os.path.isdir(input):
@@ -928,15 +936,37 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False):
         raise SystemExit(f"--input {input}: no such file or directory")
     if not paths:
         raise SystemExit(f"--input {input}: no {' / '.join('*' + e for e in DEMO_EXTENSIONS)} files")
+    if target is not None and not os.path.exists(target):
+        raise SystemExit(f"--target {target}: no such file or directory")
+    pairs = None if target is None else IO.pair_targets(paths, target)      # before anything is built
     system, _ = _joint_system_for_evaluation(config)
     batch_size = int((config.get("demo") or {}).get("batch_size", 4))
-    results = dehaze_files(system, paths, output, batch_size=batch_size, panels=panels)
+    if pairs is None:
+        results = IO.dehaze_files(system, paths, output, batch_size=batch_size, panels=panels)
+    else:
+        results = IO.dehaze_files(system, paths, output, batch_size=batch_size, panels=panels, targets=pairs)
     for r in results:
         print(f"{r['file']}: {r['height']}x{r['width']}  {r['routing']} routing -> {r['intensity']}  weights "
               + " ".join(f"{w:.3f}" for w in r["weights"]))
+        if r.get("scored"):
+            db = lambda v: "inf" if v is None else f"{v:.2f}"
+            print(f"    against {r['target']}: PSNR {db(r['psnr'])} dB  SSIM {r['ssim']:.4f}  CIEDE2000 {r['ciede2000']:.3f}"
+                  f"   (hazy input: {db(r['hazy_psnr'])} dB  {r['hazy_ssim']:.4f}  {r['hazy_ciede2000']:.3f})")
+        elif pairs is not None:
+            print("    not scored: " + (r.get("reason") or "no target"))
     with open(os.path.join(output, "demo_results.json"), "w") as f:
         json.dump(results, f, indent=2)
     print(f"{len(results)} of {len(paths)} images dehazed into {output}/ (demo_results.json lists them)")
+    if pairs is not None:
+        summary = IO.summarize_scores(results)
+        with open(os.path.join(output, "demo_scores.json"), "w") as f:
+            json.dump(summary, f, indent=2)
+        for side in ("dehazed", "hazy"):
+            m = summary[side].get("all")
+            if m:
+                print(f"{side:>7}: {m['samples']} scored  PSNR " + ("inf" if m["psnr"] is None else f"{m['psnr']:.2f}")
+                      + f" dB  SSIM {m['ssim']:.4f}  CIEDE2000 {m['ciede2000']:.3f}")
+        print(f"{sum(1 for r in results if r.get('scored'))} of {len(results)} scored against {target} (demo_scores.json)")
     return results
 
 

@@ -702,6 +702,23 @@ int adh_u8_to_image(void* stream, const uint8_t* src, int64_t row_pitch, int64_t
 int adh_image_to_u8(void* stream, const float* src_nchw, int N, int H, int W, uint8_t* dst, int64_t row_pitch,
                     int64_t image_pitch, int C);
 
+/* ---- CIEDE2000 (csrc/ciede2000.hip): the per-pixel colour difference dE00 of Sharma, Wu and Dalal (2005), kL = kC = kH = 1,
+ * between two dense fp32 [N,3,H,W] batches, and its mean per image.  lab_input == 0: the planes are sRGB in [0,1] (clamped as
+ * adh_image_to_u8 clamps, NaN = 0) and go through skimage's rgb2lab constants (sRGB decoding, the 0.412453... matrix, the D65
+ * white 0.95047 / 1 / 1.08883); lab_input == 1: the planes are L, a, b as they are.  The whole definition, with the hue
+ * conventions, heads the source file.  float64 from the clamp to the stores; the mean is a fixed-order two-stage float64
+ * reduction without atomics, so the result is bit-reproducible and that of image i does not depend on N.
+ *   partial  double[N * adh_ciede2000_num_blocks(H * W)], workspace
+ *   map      float[N*H*W] (dE per pixel) or NULL; it may not overlap pred or target
+ *   mean     float[N]
+ * 16-byte accesses where pred, target (and map) are 16-byte aligned and H * W % 4 == 0, single floats otherwise; the values are
+ * the same either way.  ADH_E_ARG (nothing is launched) for a null pred / target / partial / mean, N outside [1, 65535], H or
+ * W < 1, lab_input other than 0 or 1, nblk other than adh_ciede2000_num_blocks(H * W), or a map that overlaps an input.  No
+ * gradient. */
+int adh_ciede2000_num_blocks(int64_t pixels);          /* pixels = H*W of one image; ADH_E_ARG for pixels < 1 */
+int adh_ciede2000(void* stream, const float* pred_nchw, const float* target_nchw, int N, int H, int W, int lab_input,
+                  double* partial, int nblk, float* map, float* mean);
+
 #ifdef __cplusplus
 }
 #endif

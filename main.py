@@ -7,6 +7,7 @@ the hot path run on the HIP engine; dataset preprocessing is outside this build'
     python main.py --mode train_joint --resume                     # continue from the latest checkpoint
     torchrun --nproc-per-node 8 main.py --mode train_joint        # data-parallel over RCCL
     python main.py --mode demo --input DIR --output OUT --panels   # dehaze image files at their own size
+    python main.py --mode demo --input HAZY --target CLEAR         # ... and score them: PSNR, SSIM, CIEDE2000 per file
 
 `--resume` is the reference's flag (main.py:50-51 parses it and never reads it); here it restores model, optimiser,
 scheduler, epoch and best-PSNR from the latest checkpoint of the mode's checkpoint directory (or from the file given
@@ -39,6 +40,9 @@ def parse_args():
                    help="--mode demo: an image file, or a directory of *.png / *.jpg / *.jpeg / *.bmp files, to dehaze")
     p.add_argument("--output", type=str, default="demo", help="--mode demo: where the dehazed images and demo_results.json go")
     p.add_argument("--panels", action="store_true", help="--mode demo: also write <name>_panel.png, hazy | dehazed")
+    p.add_argument("--target", type=str, default=None,
+                   help="--mode demo --input ...: the ground truth, a directory matched to the inputs by base name, or one "
+                        "file; scores every dehazed file (PSNR, SSIM, CIEDE2000) and writes demo_scores.json")
     return p.parse_args()
 
 
@@ -53,6 +57,10 @@ def seed_everything(seed):
 
 def main():
     args = parse_args()
+    if args.target and not (args.mode == "demo" and args.input):
+        # refused before anything is built: there would be nothing to score
+        raise SystemExit("--target needs --mode demo --input DIR_OR_FILE: it names the ground truth of the image files "
+                         "given with --input.")
     with open(args.config) as f:
         config = yaml.safe_load(f)
     if args.data_dir:   # main.py:66-69
@@ -140,7 +148,10 @@ def main():
         # here the paths of the config are used as they are)
         T.run_comprehensive_evaluation(config)   # baseline branches, routed system, detector on hazy vs dehazed frames
     elif args.mode == "demo" and args.input:
-        T.run_demo(config, args.input, args.output, args.panels)
+        if args.target:
+            T.run_demo(config, args.input, args.output, args.panels, target=args.target)
+        else:
+            T.run_demo(config, args.input, args.output, args.panels)
     elif args.mode == "demo":
         # without --input: one synthetic batch through the router
         from adam_dehaze_amd.image_io import routing_records

@@ -6,7 +6,8 @@
 // -DADH_HOST_EMU (the section at the end), by tests/test_wgrad_reduce_hostemu_cpu.py on a copy of csrc/conv_wgrad_reduce.hip and
 // by tests/test_ema_hostemu_cpu.py on a copy of csrc/ema.hip; with -DADH_HOST_EMU_DYN_LDS on top (the last section), by
 // tests/test_fft_loss_hostemu_cpu.py on a copy of csrc/fft_loss.hip; with -DADH_HOST_EMU_STREAM on top of ADH_HOST_EMU (the section
-// after it), by tests/test_{bn_act,depthwise,densenet,image_io}_hostemu_cpu.py on copies of the four streaming kernel files.
+// after it), by tests/test_{bn_act,depthwise,densenet,image_io}_hostemu_cpu.py on copies of the four streaming kernel files and by
+// tests/test_ciede2000_hostemu_cpu.py on a copy of csrc/ciede2000.hip (which reduces through LDS and barriers: no shuffle).
 #pragma once
 #include <cmath>
 #include <cstdint>
