@@ -244,6 +244,7 @@ _SIGNATURES = {
     "adh_image_to_u8": [vp, vp, i32, i32, i32, vp, i64, i64, i32],
     "adh_ciede2000_num_blocks": [i64],
     "adh_ciede2000": [vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp],
+    "adh_d4_apply": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, f32],
 }
 
 # functions that return a count / size rather than a status code

@@ -4,7 +4,11 @@ csrc/image_io.hip, Pillow for the files themselves, and `dehaze_files`, the body
 
 The kernels take a base pointer and two byte pitches, so a crop of an 8-bit tensor is read, and one pane of a side-by-side panel
 is written, in place: `u8_to_image` / `image_to_u8` turn the strides of a view into those pitches.  Images are processed at their
-own size; nothing is resized."""
+own size; nothing is resized.
+
+Two options of the demo path ride on the D4 kernels of csrc/d4.hip (d4.py, whose names are re-exported here): `self_ensemble`
+('flip' | 'd8') averages the router's output over the symmetries of its input, and `exif` turns every file (and every target)
+upright by its EXIF orientation tag before anything else sees it."""
 from __future__ import annotations
 
 import os
@@ -14,6 +18,8 @@ from typing import Dict, Iterable, List, Optional, Tuple
 import torch
 
 from . import _hip as H
+from . import d4 as _d4
+from .d4 import D4_OPS, EXIF_TO_D4, d4_apply, d4_inverse, exif_tag, self_ensemble  # noqa: F401
 
 _NAMES = ("low", "medium", "high")
 MIN_SIDE = 16          # the branches halve the frame more than once: smaller files are skipped
@@ -72,23 +78,42 @@ def _pil():
     return Image
 
 
-def image_size(path: str) -> Tuple[int, int]:
-    """(height, width) from the file's header"""
+ORIENTATION_TAG = 0x0112
+
+
+def _orientation(im) -> int:
+    """the EXIF orientation of an open Pillow image: 1..8; a missing tag, or a value outside 1..8, reads as 1"""
+    try:
+        return exif_tag(im.getexif().get(ORIENTATION_TAG))
+    except Exception:                                   # a damaged EXIF block is no reason not to dehaze the pixels
+        return 1
+
+
+def image_size(path: str, orientation: bool = False):
+    """(height, width) of the stored pixels from the file's header; with `orientation` (height, width, EXIF tag 1..8)"""
     with _pil().open(path) as im:
-        return im.height, im.width
+        return (im.height, im.width, _orientation(im)) if orientation else (im.height, im.width)
 
 
-def load_image(path: str) -> torch.Tensor:
+def upright_size(h: int, w: int, tag: int) -> Tuple[int, int]:
+    """the size of an h x w file once its EXIF orientation `tag` is applied"""
+    return (w, h) if EXIF_TO_D4[tag][0] else (h, w)
+
+
+def load_image(path: str, orientation: bool = False):
     """An image file as a uint8 [H,W,C] CPU tensor.  Modes L, RGB and RGBA arrive as they are (C = 1, 3, 4); every other mode
-    (palette, CMYK, 16-bit, ...) goes through Pillow's convert("RGB") on the host.  The EXIF orientation tag is NOT applied:
-    pixels come in file order."""
+    (palette, CMYK, 16-bit, ...) goes through Pillow's convert("RGB") on the host.  The EXIF orientation tag is not applied
+    here: pixels come in file order, and with `orientation` the result is (tensor, tag 1..8) for the caller to apply on the
+    device (`dehaze_files(..., exif=True)` does, through EXIF_TO_D4 and d4_apply)."""
     import numpy as np
     with _pil().open(path) as im:
+        tag = _orientation(im) if orientation else 1
         if im.mode not in ("L", "RGB", "RGBA"):
             im = im.convert("RGB")
         a = np.array(im, dtype=np.uint8)
     t = torch.from_numpy(a)
-    return t.unsqueeze(-1) if t.dim() == 2 else t
+    t = t.unsqueeze(-1) if t.dim() == 2 else t
+    return (t, tag) if orientation else t
 
 
 def save_image(path: str, u8: torch.Tensor) -> None:
@@ -117,17 +142,20 @@ def routing_records(aux: Dict) -> List[Dict]:
 
 
 # ---------------------------------------------------------------------------------------------------------------- demo
-def plan_chunks(sizes: Dict[str, Tuple[int, int]], batch_size: int) -> List[List[str]]:
+def plan_chunks(sizes: Dict[str, Tuple[int, int]], batch_size: int, tags: Optional[Dict[str, int]] = None) -> List[List[str]]:
     """The paths of `sizes` (path -> (H, W)) sorted, grouped by size in sorted order, each group cut into chunks of at most
-    `batch_size`; files whose shorter side is under MIN_SIDE are left out with a warning that names them."""
+    `batch_size`; files whose shorter side is under MIN_SIDE are left out with a warning that names them.  `tags` (path -> EXIF
+    orientation 1..8; `sizes` are then those of the stored pixels): files are grouped by size and by whether their orientation
+    transposes, since one launch turns a chunk upright and has one output shape."""
     if batch_size < 1:
         raise ValueError(f"batch_size must be at least 1, got {batch_size}")
-    groups: Dict[Tuple[int, int], List[str]] = {}
+    groups: Dict[Tuple, List[str]] = {}
     for p in sorted(sizes):
         if min(sizes[p]) < MIN_SIDE:
             warnings.warn(f"{p}: {sizes[p][0]}x{sizes[p][1]} is smaller than {MIN_SIDE} pixels on a side; skipped")
             continue
-        groups.setdefault(tuple(sizes[p]), []).append(p)
+        key = tuple(sizes[p]) if tags is None else tuple(sizes[p]) + (EXIF_TO_D4[tags[p]][0],)
+        groups.setdefault(key, []).append(p)
     return [g[i:i + batch_size] for g in groups.values() for i in range(0, len(g), batch_size)]
 
 
@@ -139,27 +167,50 @@ def _stack(images: List[torch.Tensor]) -> torch.Tensor:
     return torch.stack(images)
 
 
-def _dehaze_on_device(system: Dict, u8: torch.Tensor, panels: bool):
+def _orient(x: torch.Tensor, tags: List[int]) -> torch.Tensor:
+    """fp32 [N,3,H,W] in file order -> upright by the EXIF orientation of every image (all transposing, or none): one launch with
+    per-image flip codes; none where every image is upright already"""
+    ops = [EXIF_TO_D4[t] for t in tags]
+    if len({t for t, _ in ops}) != 1:
+        raise ValueError(f"one chunk holds transposing and non-transposing orientations: {tags}")
+    if all(op == (0, 0) for op in ops):
+        return x
+    return d4_apply(x, (ops[0][0], 0), flip_ops=torch.tensor([f for _, f in ops], dtype=torch.int32, device=x.device))
+
+
+def _dehaze_on_device(system: Dict, u8: torch.Tensor, panels: bool, self_ensemble: Optional[str] = None,
+                      tags: Optional[List[int]] = None):
     """uint8 [N,H,W,C] on the host -> (hazy fp32 [N,3,H,W], dehazed uint8 [N,H,W,3] view, panel uint8 [N,H,2W,3] or None, routing
     records), the tensors on the device.  One copy to the device, the unpack kernel, the router, the pack kernel; with `panels`
-    the pack kernel writes both panes into one buffer through pointer and pitch, and the dehazed image is the right pane."""
+    the pack kernel writes both panes into one buffer through pointer and pitch, and the dehazed image is the right pane.
+    `tags`: the EXIF orientation of every image; the unpacked batch is turned upright first, and everything returned is upright.
+    `self_ensemble` ('flip' | 'd8'): the router's output is averaged over the symmetries of its input (d4.self_ensemble: every
+    variant through classifier and router; the records are the upright pass's and gain `self_ensemble`: 4 | 8)."""
     dev = system["device"]
     x = u8_to_image(u8.to(dev))
-    with torch.no_grad():
-        y, aux = system["router"](x)
+    if tags is not None:
+        x = _orient(x, tags)
+    if self_ensemble is None:
+        with torch.no_grad():
+            y, aux = system["router"](x)
+        records = lambda: routing_records(aux)         # read back behind the pack launches, as before
+    else:
+        y, aux = _d4.self_ensemble(lambda b: system["router"](b), x, self_ensemble)
+        records = lambda: [dict(r, self_ensemble=len(_d4.SELF_ENSEMBLE_MODES[self_ensemble])) for r in routing_records(aux)]
     if not panels:
-        return x, image_to_u8(y), None, routing_records(aux)
+        return x, image_to_u8(y), None, records()
     N, _, h, w = x.shape
     panel = torch.empty((N, h, 2 * w, 3), device=dev, dtype=torch.uint8)
     image_to_u8(x, out=panel[:, :, :w])                # v -> v / 255 -> v: the hazy pane is the file's pixels again
     image_to_u8(y, out=panel[:, :, w:])
-    return x, panel[:, :, w:], panel, routing_records(aux)
+    return x, panel[:, :, w:], panel, records()
 
 
-def dehaze_batch(system: Dict, u8: torch.Tensor, panels: bool = False):
+def dehaze_batch(system: Dict, u8: torch.Tensor, panels: bool = False, self_ensemble: Optional[str] = None,
+                 tags: Optional[List[int]] = None):
     """uint8 [N,H,W,C] on the host -> (dehazed uint8 [N,H,W,3] on the host, hazy | dehazed panels [N,H,2W,3] or None, routing
-    records): `_dehaze_on_device` and one copy back."""
-    _, out, panel, records = _dehaze_on_device(system, u8, panels)
+    records): `_dehaze_on_device` (which explains `self_ensemble` and `tags`) and one copy back."""
+    _, out, panel, records = _dehaze_on_device(system, u8, panels, self_ensemble, tags)
     if panel is None:
         return out.cpu(), None, records
     panel = panel.cpu()
@@ -171,7 +222,7 @@ DEMO_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp")
 SCORE_KEYS = ("psnr", "ssim", "ciede2000", "hazy_psnr", "hazy_ssim", "hazy_ciede2000")
 
 
-def pair_targets(paths: Iterable[str], target: str) -> Dict[str, Dict]:
+def pair_targets(paths: Iterable[str], target: str, exif: bool = False) -> Dict[str, Dict]:
     """The ground-truth file of every input of `--mode demo --target`: input path -> the fields its record gains.  `target` is a
     directory, whose *.png / *.jpg / *.jpeg / *.bmp files are matched to the inputs by base name without extension (hazy
     `x.jpg` finds clear `x.png`), or one file, which is the target of a single input whatever its name and otherwise of the
@@ -179,7 +230,8 @@ def pair_targets(paths: Iterable[str], target: str) -> Dict[str, Dict]:
         {"target": path}                                                   to be scored
         {"target": path, "scored": False, "reason": "size HxW != HxW"}     the target is of another size (input != target)
         {"target": None}                                                   no target; warned about
-    Two files of one base name in the target directory are a ValueError that names them.  Only file headers are read."""
+    Two files of one base name in the target directory are a ValueError that names them.  Only file headers are read.
+    `exif`: the sizes compared are the upright ones, each file's by its own EXIF orientation tag."""
     paths = [str(p) for p in paths]
     base = lambda p: os.path.splitext(os.path.basename(p))[0]
     if os.path.isdir(target):
@@ -205,19 +257,26 @@ def pair_targets(paths: Iterable[str], target: str) -> Dict[str, Dict]:
             warnings.warn(f"{p}: no target named {base(p)}.* under {target}; dehazed but not scored")
             pairs[p] = {"target": None}
             continue
-        (h, w), (th, tw) = image_size(p), image_size(t)
+        if exif:
+            (h, w), (th, tw) = upright_size(*image_size(p, orientation=True)), upright_size(*image_size(t, orientation=True))
+        else:
+            (h, w), (th, tw) = image_size(p), image_size(t)
         pairs[p] = {"target": t} if (h, w) == (th, tw) else \
             {"target": t, "scored": False, "reason": f"size {h}x{w} != {th}x{tw}"}
     return pairs
 
 
-def score_batch(hazy: torch.Tensor, dehazed_u8: torch.Tensor, target_u8: torch.Tensor) -> List[Dict]:
+def score_batch(hazy: torch.Tensor, dehazed_u8: torch.Tensor, target_u8: torch.Tensor,
+                target_tags: Optional[List[int]] = None) -> List[Dict]:
     """The six scores of every image of a chunk, all on the device with one read-back: `hazy` fp32 [n,3,H,W] (the unpacked
     input), `dehazed_u8` uint8 [n,H,W,3] (the packed output, i.e. the pixels of the written file) and `target_u8` uint8
     [n,H,W,C], both on the device.  The dehazed side is `u8_to_image` of the packed bytes, exactly v / 255, not the router's
-    fp32 output: a score can be recomputed from the two files alone.  An infinite PSNR (identical images) becomes None."""
+    fp32 output: a score can be recomputed from the two files alone.  An infinite PSNR (identical images) becomes None.
+    `target_tags`: the EXIF orientation of every target, whose pixels are in file order and are turned upright here."""
     from .metrics import ciede2000_batch, psnr_batch, ssim_batch
     tgt = u8_to_image(target_u8)
+    if target_tags is not None:
+        tgt = _orient(tgt, target_tags)
     rows = []
     for img in (u8_to_image(dehazed_u8), hazy):
         rows += [psnr_batch(img, tgt), ssim_batch(img, tgt), ciede2000_batch(img, tgt)]
@@ -249,7 +308,7 @@ def summarize_scores(records: Iterable[Dict]) -> Dict:
 
 
 def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: int = 4, panels: bool = False,
-                 targets: Optional[Dict[str, Dict]] = None) -> List[Dict]:
+                 targets: Optional[Dict[str, Dict]] = None, self_ensemble: Optional[str] = None, exif: bool = False) -> List[Dict]:
     """Dehaze image files through `system["router"]` (eval mode, no_grad) at their own size and write `<out_dir>/<name>.png` --
     with `panels` also `<name>_panel.png`, hazy | dehazed -- for every input `<name>.<ext>`.  Files of equal size go through
     together, `batch_size` at a time.  Returns one dict per processed file, in sorted order: `file`, `height`, `width` and the
@@ -257,26 +316,43 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
     `targets` (what `pair_targets` returns): every record also gains the fields of its entry there, and each input with a target
     of its size is scored against it -- `scored: True` and the six numbers of `score_batch`: `psnr`, `ssim`, `ciede2000` of the
     written file, `hazy_psnr`, `hazy_ssim`, `hazy_ciede2000` of the input.  A chunk's targets go to the device once and its
-    scores come back in one read."""
+    scores come back in one read.
+    `self_ensemble` ('flip' | 'd8'): every chunk goes through the router under 4 or 8 symmetries and the outputs are averaged
+    (d4.self_ensemble); every record gains `self_ensemble`: 4 | 8.
+    `exif`: every file is turned upright by its EXIF orientation tag on the device (one d4_apply launch per chunk) before the
+    router sees it; files are grouped by stored size and by whether the orientation transposes, `height` / `width` are the
+    upright ones, every record gains `orientation` (the tag, 1 where there is none), the written PNG is upright and carries no
+    tag, panels show the upright input, and every target is turned upright by its own tag (`targets` from
+    `pair_targets(..., exif=True)`, which compares upright sizes).  Without it pixels are taken in file order, as before."""
+    if self_ensemble is not None and self_ensemble not in _d4.SELF_ENSEMBLE_MODES:
+        raise ValueError(f"self_ensemble must be one of {sorted(_d4.SELF_ENSEMBLE_MODES)}, got {self_ensemble!r}")
     paths = sorted(str(p) for p in paths)
     names = [os.path.splitext(os.path.basename(p))[0] for p in paths]
     twice = sorted({n for n in names if names.count(n) > 1})
     if twice:
         raise ValueError(f"input files share a base name and would overwrite each other's output: {', '.join(twice)}")
-    sizes = {p: image_size(p) for p in paths}
+    tags: Optional[Dict[str, int]] = None
+    if exif:
+        sized = {p: image_size(p, orientation=True) for p in paths}
+        sizes, tags = {p: v[:2] for p, v in sized.items()}, {p: v[2] for p, v in sized.items()}
+    else:
+        sizes = {p: image_size(p) for p in paths}
+    kw = {} if self_ensemble is None else {"self_ensemble": self_ensemble}     # absent options: exactly the plain calls
     os.makedirs(out_dir, exist_ok=True)
     system["router"].eval()
     results = []
-    for chunk in plan_chunks(sizes, batch_size):
+    for chunk in (plan_chunks(sizes, batch_size) if tags is None else plan_chunks(sizes, batch_size, tags)):
         u8 = _stack([load_image(p) for p in chunk])
+        if tags is not None:
+            kw["tags"] = [tags[p] for p in chunk]
         extra: List[Dict] = [{} for _ in chunk]
         if targets is None:
-            out, panel, records = dehaze_batch(system, u8, panels)
+            out, panel, records = dehaze_batch(system, u8, panels, **kw)
         else:
-            hazy, out, panel, records = _dehaze_on_device(system, u8, panels)
+            hazy, out, panel, records = _dehaze_on_device(system, u8, panels, **kw)
             extra = [dict(targets.get(p) or {"target": None}) for p in chunk]
             sel = [i for i, e in enumerate(extra) if e["target"] is not None and e.get("scored", True)]
-            if sel:
+            if sel and tags is None:
                 idx = torch.tensor(sel, device=hazy.device)
                 tgt = _stack([load_image(extra[i]["target"]) for i in sel]).to(hazy.device)
                 whole = len(sel) == len(chunk)
@@ -284,6 +360,21 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
                                      out if whole else out.index_select(0, idx), tgt)
                 for i, sc in zip(sel, scores):
                     extra[i].update(scored=True, **sc)
+            elif sel:
+                # every target by its own tag: those that transpose are stored at another size than those that do not, so
+                # they are stacked, turned upright and scored as (at most) two groups
+                loaded = {i: load_image(extra[i]["target"], orientation=True) for i in sel}
+                for bit in (0, 1):
+                    part = [i for i in sel if EXIF_TO_D4[loaded[i][1]][0] == bit]
+                    if not part:
+                        continue
+                    idx = torch.tensor(part, device=hazy.device)
+                    tgt = _stack([loaded[i][0] for i in part]).to(hazy.device)
+                    whole = len(part) == len(chunk)
+                    scores = score_batch(hazy if whole else hazy.index_select(0, idx),
+                                         out if whole else out.index_select(0, idx), tgt, [loaded[i][1] for i in part])
+                    for i, sc in zip(part, scores):
+                        extra[i].update(scored=True, **sc)
             if panel is None:
                 out = out.cpu()
             else:                                      # one copy back: the dehazed image is the panel's right pane
@@ -294,5 +385,7 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
             save_image(os.path.join(out_dir, name + ".png"), out[i])
             if panel is not None:
                 save_image(os.path.join(out_dir, name + "_panel.png"), panel[i])
-            results.append({"file": p, "height": sizes[p][0], "width": sizes[p][1], **rec, **extra[i]})
+            h, w = sizes[p] if tags is None else upright_size(*sizes[p], tags[p])
+            results.append({"file": p, "height": h, "width": w, **rec, **({} if tags is None else {"orientation": tags[p]}),
+                            **extra[i]})
     return sorted(results, key=lambda r: r["file"])

@@ -814,6 +814,25 @@ def _ciede2000_switch(config):
     return {"use_ciede2000": True} if (config.get("evaluation") or {}).get("ciede2000") else {}
 
 
+def _self_ensemble_mode(config):
+    """`evaluation.self_ensemble: 'flip' | 'd8'` averages every evaluated output over 4 or 8 symmetries of its input (DESIGN 4.27);
+    absent, None: the evaluators make exactly the calls they made before."""
+    mode = (config.get("evaluation") or {}).get("self_ensemble")
+    if mode is not None and mode not in ("flip", "d8"):
+        raise ValueError(f"evaluation.self_ensemble must be 'flip' or 'd8', got {mode!r}")
+    return mode
+
+
+def _record_self_ensemble(path, mode):
+    """the top-level `self_ensemble` key of a result file written by ImageQualityMetrics.save_results"""
+    import json
+    with open(path) as f:
+        saved = json.load(f)
+    saved["self_ensemble"] = {"mode": mode, "passes": {"flip": 4, "d8": 8}[mode]}
+    with open(path, "w") as f:
+        json.dump(saved, f, indent=2)
+
+
 @_rank0_only
 def evaluate_joint_model(config, test_loader=None, steps: int = 2, use_lpips: bool = True):
     """evaluation/evaluate.py:94-177 (image-quality part): load the joint checkpoint if present, route every test
@@ -822,20 +841,30 @@ def evaluate_joint_model(config, test_loader=None, steps: int = 2, use_lpips: bo
     from .metrics import CATEGORY_BY_LABEL, ImageQualityMetrics
     # (every rank scoring its own shard and writing the same JSON concurrently was a race, ADVICE r2: rank 0 evaluates and
     # writes, the others wait for it in _rank0_only)
+    ensemble = _self_ensemble_mode(config)
     system, _ = _joint_system_for_evaluation(config)
     dev = system["device"]
     metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips, **_ciede2000_switch(config))
     test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, dev, warn="evaluate_joint_model")
+
+    def routed(h):                                     # every variant of the ensemble gets logits of its own
+        return system["router"](h, system["classifier"](h)[0])
     with torch.no_grad():
         for batch in test_loader:
             hazy, clear = batch["hazy"].to(dev), batch["clear"].to(dev)
-            logits, _ = system["classifier"](hazy)
-            dehazed, _ = system["router"](hazy, logits)
+            if ensemble is None:
+                logits, _ = system["classifier"](hazy)
+                dehazed, _ = system["router"](hazy, logits)
+            else:
+                from .d4 import self_ensemble
+                dehazed, _ = self_ensemble(routed, hazy, ensemble)
             cats = [CATEGORY_BY_LABEL.get(int(i), "high_intensity") for i in batch["intensity"].tolist()]
             metrics.add_batch(dehazed, clear, cats)
     results = metrics.print_results()
     out_dir = config.get("evaluation", {}).get("results_dir", "results")
     metrics.save_results(os.path.join(out_dir, "joint_model_results.json"))
+    if ensemble is not None:
+        _record_self_ensemble(os.path.join(out_dir, "joint_model_results.json"), ensemble)
     return results
 
 
@@ -845,6 +874,7 @@ def evaluate_baseline_models(config, test_loader=None, steps: int = 2, use_lpips
     no router), PSNR / SSIM / LPIPS per category on the device, `<evaluation.results_dir>/baseline_results.json`.  The reference
     runs one image at a time; eval-mode branches are per-sample independent, so the images of a level go through as one batch."""
     from .metrics import CATEGORY_BY_LABEL, ImageQualityMetrics
+    ensemble = _self_ensemble_mode(config)
     system = build_joint_system(config, 1, with_ema=False)
     dev = system["device"]
     for level, m in system["models"].items():
@@ -860,11 +890,18 @@ def evaluate_baseline_models(config, test_loader=None, steps: int = 2, use_lpips
             labels = batch["intensity"].to(dev).clamp(max=2)       # evaluate.py:73-81: anything above 1 is "high"
             for lab, model in by_label.items():
                 idx = torch.nonzero(labels == lab).flatten()
-                if idx.numel():
+                if idx.numel() and ensemble is None:
                     metrics.add_batch(model(hazy[idx].contiguous()), clear[idx].contiguous(),
                                       [CATEGORY_BY_LABEL[lab]] * int(idx.numel()))
+                elif idx.numel():
+                    from .d4 import self_ensemble
+                    dehazed, _ = self_ensemble(lambda b, model=model: (model(b), None), hazy[idx].contiguous(), ensemble)
+                    metrics.add_batch(dehazed, clear[idx].contiguous(), [CATEGORY_BY_LABEL[lab]] * int(idx.numel()))
     results = metrics.print_results()
-    metrics.save_results(os.path.join(config.get("evaluation", {}).get("results_dir", "results"), "baseline_results.json"))
+    out_path = os.path.join(config.get("evaluation", {}).get("results_dir", "results"), "baseline_results.json")
+    metrics.save_results(out_path)
+    if ensemble is not None:
+        _record_self_ensemble(out_path, ensemble)
     return results
 
 
@@ -914,7 +951,8 @@ def run_comprehensive_evaluation(config, steps: int = 2, use_lpips: bool = True)
     return comprehensive
 
 
-def run_demo(config, input: str, output: str = "demo", panels: bool = False, target: Optional[str] = None):
+def run_demo(config, input: str, output: str = "demo", panels: bool = False, target: Optional[str] = None,
+             self_ensemble: Optional[str] = None, exif: bool = False):
     """main.py:152-217 of the reference loads every checkpoint and stops at a TODO (load sample hazy images, classify, dehaze
     through the router, visualise); this is that mode.  `input` is one image file or a directory whose *.png / *.jpg / *.jpeg /
     *.bmp files are taken; every image goes through the routed system at its own size (image_io.dehaze_files, `demo.batch_size`
@@ -923,7 +961,10 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
     `target`: the ground truth, a directory (matched to the inputs by base name, image_io.pair_targets) or one file.  Every
     written file is then scored against its target -- PSNR, SSIM and CIEDE2000, and the same three for the hazy input -- the
     scores are printed and recorded per file, and `<output>/demo_scores.json` holds their means per routed intensity
-    (image_io.summarize_scores).  No LPIPS here: without pretrained weights it would score with a random extractor."""
+    (image_io.summarize_scores).  No LPIPS here: without pretrained weights it would score with a random extractor.
+    `self_ensemble` ('flip' | 'd8'; or `demo.self_ensemble` of the config): the output is the average over 4 or 8 symmetries of
+    the input (d4.self_ensemble).  `exif` (or `demo.exif_orientation: true`): every file, and every target, is turned upright by
+    its EXIF orientation tag first.  An argument given here wins over the config; with neither, every call is the plain one."""
     import json
     from . import image_io as IO
     if _world_rank()[0] > 1:
@@ -938,13 +979,25 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
         raise SystemExit(f"--input {input}: no {' / '.join('*' + e for e in DEMO_EXTENSIONS)} files")
     if target is not None and not os.path.exists(target):
         raise SystemExit(f"--target {target}: no such file or directory")
-    pairs = None if target is None else IO.pair_targets(paths, target)      # before anything is built
-    system, _ = _joint_system_for_evaluation(config)
-    batch_size = int((config.get("demo") or {}).get("batch_size", 4))
-    if pairs is None:
-        results = IO.dehaze_files(system, paths, output, batch_size=batch_size, panels=panels)
+    demo = config.get("demo") or {}
+    self_ensemble = self_ensemble if self_ensemble is not None else demo.get("self_ensemble")
+    exif = bool(exif or demo.get("exif_orientation"))
+    if self_ensemble is not None and self_ensemble not in ("flip", "d8"):
+        raise SystemExit(f"self-ensemble mode {self_ensemble!r}: choose 'flip' (x4) or 'd8' (x8)")
+    if target is None:                                                       # before anything is built
+        pairs = None
     else:
-        results = IO.dehaze_files(system, paths, output, batch_size=batch_size, panels=panels, targets=pairs)
+        pairs = IO.pair_targets(paths, target, exif=True) if exif else IO.pair_targets(paths, target)
+    system, _ = _joint_system_for_evaluation(config)
+    batch_size = int(demo.get("batch_size", 4))
+    options = {}                                       # only what was asked for: absent options leave the call as it was
+    if pairs is not None:
+        options["targets"] = pairs
+    if self_ensemble is not None:
+        options["self_ensemble"] = self_ensemble
+    if exif:
+        options["exif"] = True
+    results = IO.dehaze_files(system, paths, output, batch_size=batch_size, panels=panels, **options)
     for r in results:
         print(f"{r['file']}: {r['height']}x{r['width']}  {r['routing']} routing -> {r['intensity']}  weights "
               + " ".join(f"{w:.3f}" for w in r["weights"]))

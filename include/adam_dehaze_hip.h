@@ -719,6 +719,18 @@ int adh_ciede2000_num_blocks(int64_t pixels);          /* pixels = H*W of one im
 int adh_ciede2000(void* stream, const float* pred_nchw, const float* target_nchw, int N, int H, int W, int lab_input,
                   double* partial, int nblk, float* map, float* mean);
 
+/* ---- the symmetries of the square (csrc/d4.hip): flips and 90-degree rotations of a dense fp32 [N,C,H,W] batch, which are also
+ * the eight EXIF orientations.  dst is dense [N,C,Hd,Wd] with (Hd,Wd) = transpose ? (W,H) : (H,W), and
+ *   v(n,c,y',x') = src[n,c,y,x],  u = bit1 ? Hd-1-y' : y',  w = bit0 ? Wd-1-x' : x',  (y,x) = transpose ? (w,u) : (u,w)
+ * i.e. transpose first, then mirror along x if bit 0 of the flip code is set and along y if bit 1 is.  The flip code is `flips`
+ * (0..3) for every image when flip_ops is NULL, else flip_ops[n] & 3 (device int32[N]); the transpose bit is per launch.
+ * Stored value = accumulate ? dst + v : v, then times `scale` (one rounding each, never fused) if scale != 1.0f; accumulate == 0
+ * with scale == 1 is a bit copy (NaN payloads and -0 survive).  Bit-equal to ((dst + ref(src)) * scale) in fp32 on the CPU.
+ * ADH_E_ARG (nothing is launched) for a null src / dst, N, C, H or W < 1, transpose outside {0,1}, flips outside 0..3, or a dst
+ * range that overlaps the src range (no in-place use). */
+int adh_d4_apply(void* stream, const float* src, int N, int C, int H, int W, int transpose, int flips, const int32_t* flip_ops,
+                 float* dst, int accumulate, float scale);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,12 @@ def parse_args():
     p.add_argument("--target", type=str, default=None,
                    help="--mode demo --input ...: the ground truth, a directory matched to the inputs by base name, or one "
                         "file; scores every dehazed file (PSNR, SSIM, CIEDE2000) and writes demo_scores.json")
+    p.add_argument("--self-ensemble", dest="self_ensemble", choices=["flip", "d8"], default=None,
+                   help="--mode demo --input ...: average the output over the 4 flips (flip) or all 8 flips and rotations (d8) "
+                        "of the input; overrides demo.self_ensemble of the config")
+    p.add_argument("--exif", action="store_true",
+                   help="--mode demo --input ...: turn every file (and every --target file) upright by its EXIF orientation "
+                        "tag first; same as demo.exif_orientation: true in the config")
     return p.parse_args()
 
 
@@ -61,6 +67,9 @@ def main():
         # refused before anything is built: there would be nothing to score
         raise SystemExit("--target needs --mode demo --input DIR_OR_FILE: it names the ground truth of the image files "
                          "given with --input.")
+    if (args.self_ensemble or args.exif) and not (args.mode == "demo" and args.input):
+        raise SystemExit("--self-ensemble and --exif need --mode demo --input DIR_OR_FILE: they are options of dehazing image "
+                         "files.")
     with open(args.config) as f:
         config = yaml.safe_load(f)
     if args.data_dir:   # main.py:66-69
@@ -148,10 +157,14 @@ def main():
         # here the paths of the config are used as they are)
         T.run_comprehensive_evaluation(config)   # baseline branches, routed system, detector on hazy vs dehazed frames
     elif args.mode == "demo" and args.input:
+        options = {}                                   # only the flags given: without any, the call is the plain one
         if args.target:
-            T.run_demo(config, args.input, args.output, args.panels, target=args.target)
-        else:
-            T.run_demo(config, args.input, args.output, args.panels)
+            options["target"] = args.target
+        if args.self_ensemble:
+            options["self_ensemble"] = args.self_ensemble
+        if args.exif:
+            options["exif"] = True
+        T.run_demo(config, args.input, args.output, args.panels, **options)
     elif args.mode == "demo":
         # without --input: one synthetic batch through the router
         from adam_dehaze_amd.image_io import routing_records

@@ -94,13 +94,15 @@ static inline void sincospif(float x, float* s, float* c) {
 #endif
 
 #ifdef ADH_HOST_EMU_STREAM
-// What csrc/bn_act.hip, csrc/depthwise.hip, csrc/densenet.hip and csrc/image_io.hip take beyond the ADH_HOST_EMU section; their drivers link
+// What csrc/bn_act.hip, csrc/depthwise.hip, csrc/densenet.hip, csrc/image_io.hip and csrc/d4.hip (tests/test_d4_hostemu_cpu.py; its
+// transposing kernel stages a static LDS tile between barriers) take beyond the ADH_HOST_EMU section; their drivers link
 // stream_rt.cpp, whose emu_launch walks grid.x, grid.y and grid.z.  The non-temporal builtins are plain loads and stores.  The
 // activation helpers are copies of csrc/common.h's: keep them the same.
 #include <atomic>
 #define __builtin_nontemporal_load(p) (*(p))
 #define __builtin_nontemporal_store(v, p) (*(p) = (v))
 static inline int adh_max_i(int a, int b) { return a > b ? a : b; }
+#define __builtin_amdgcn_readfirstlane(v) (v)   // csrc/d4.hip: a value its caller knows to be wave-uniform
 static inline float __fmul_rn(float a, float b) { return a * b; }   // csrc/image_io.hip: a product nothing is contracted into
 static inline bool adh_act_valid(int act) {
     return act == ADH_ACT_NONE || act == ADH_ACT_RELU || act == ADH_ACT_RELU6 || act == ADH_ACT_HARDSWISH ||
