@@ -13,59 +13,13 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
                                                            const float* __restrict__ beta, float eps, float momentum,
                                                            float* running_mean, float* running_var, float* scale,
                                                            float* shift, float* save_mean, float* save_invstd, int64_t* num_batches_tracked) {
-    // 32 channels x 32 row slices per block; each thread keeps 4 independent fp64 chains in flight
     __shared__ double red[2][32][33];
-    const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cx;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
-    if (c < C) {
-        int b = ry;
-        for (; b + 96 < nblk; b += 128) {   // eight independent loads in flight: the loop is latency-bound
-            s0 += (double)partials[((size_t)b * 2 + 0) * NcP + c];
-            q0 += (double)partials[((size_t)b * 2 + 1) * NcP + c];
-            s1 += (double)partials[((size_t)(b + 32) * 2 + 0) * NcP + c];
-            q1 += (double)partials[((size_t)(b + 32) * 2 + 1) * NcP + c];
-            s2 += (double)partials[((size_t)(b + 64) * 2 + 0) * NcP + c];
-            q2 += (double)partials[((size_t)(b + 64) * 2 + 1) * NcP + c];
-            s3 += (double)partials[((size_t)(b + 96) * 2 + 0) * NcP + c];
-            q3 += (double)partials[((size_t)(b + 96) * 2 + 1) * NcP + c];
-        }
-        for (; b < nblk; b += 32) {
-            s0 += (double)partials[((size_t)b * 2 + 0) * NcP + c];
-            q0 += (double)partials[((size_t)b * 2 + 1) * NcP + c];
-        }
-    }
-    s0 += s2;
-    s1 += s3;
-    q0 += q2;
-    q1 += q3;
-    red[0][ry][cx] = s0 + s1;
-    red[1][ry][cx] = q0 + q1;
-    __syncthreads();
-    if (ry == 0 && c < C) {
-        double S = 0.0, Q = 0.0;
-        for (int r = 0; r < 32; ++r) {
-            S += red[0][r][cx];
-            Q += red[1][r][cx];
-        }
-        const double mean = S / count;
-        double var = Q / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const double invstd = 1.0 / sqrt(var + (double)eps);
-        const float gm = gamma ? gamma[c] : 1.f;
-        const float bt = beta ? beta[c] : 0.f;
-        const float sc = (float)(gm * invstd);
-        scale[c] = sc;
-        shift[c] = (float)(bt - mean * gm * invstd);
-        if (save_mean) save_mean[c] = (float)mean;
-        if (save_invstd) save_invstd[c] = (float)invstd;
-        if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-        if (running_var) {
-            const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-            running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-        }
-        if (num_batches_tracked && c == 0) *num_batches_tracked += 1;     // BatchNorm2d's counter (one writer)
-    }
+    int c;
+    double S, Q, mean, var;
+    if (!bn_column_sums<4>(partials, nblk, NcP, C, red, c, S, Q)) return;
+    bn_mean_var(S, Q, count, mean, var);
+    bn_fold_channel(c, mean, var, count, gamma, beta, eps, momentum, running_mean, running_var, scale, shift, save_mean,
+                    save_invstd, num_batches_tracked);
 }
 
 extern "C" int adh_bn_finalize(void* stream, const float* partials, int nblk, int NcP, int C, double count,
@@ -88,31 +42,9 @@ extern "C" int adh_bn_finalize(void* stream, const float* partials, int nblk, in
 __global__ __launch_bounds__(1024) void bn_partial_sums_kernel(const float* __restrict__ partials, int nblk, int pitch, int C,
                                                                double count, double* __restrict__ sums) {
     __shared__ double red[2][32][33];
-    const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cx;
-    double s0 = 0.0, s1 = 0.0, q0 = 0.0, q1 = 0.0;
-    if (c < C) {
-        int b = ry;
-        for (; b + 32 < nblk; b += 64) {
-            s0 += (double)partials[((size_t)b * 2 + 0) * pitch + c];
-            q0 += (double)partials[((size_t)b * 2 + 1) * pitch + c];
-            s1 += (double)partials[((size_t)(b + 32) * 2 + 0) * pitch + c];
-            q1 += (double)partials[((size_t)(b + 32) * 2 + 1) * pitch + c];
-        }
-        for (; b < nblk; b += 32) {
-            s0 += (double)partials[((size_t)b * 2 + 0) * pitch + c];
-            q0 += (double)partials[((size_t)b * 2 + 1) * pitch + c];
-        }
-    }
-    red[0][ry][cx] = s0 + s1;
-    red[1][ry][cx] = q0 + q1;
-    __syncthreads();
-    if (ry == 0 && c < C) {
-        double S = 0.0, Q = 0.0;
-        for (int r = 0; r < 32; ++r) {
-            S += red[0][r][cx];
-            Q += red[1][r][cx];
-        }
+    int c;
+    double S, Q;
+    if (bn_column_sums<2>(partials, nblk, pitch, C, red, c, S, Q)) {
         sums[c] = S;
         sums[C + c] = Q;
     }
@@ -133,22 +65,10 @@ __global__ void bn_finalize_sums_kernel(const double* __restrict__ sums, int C, 
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const double count = sums[2 * C];
-    const double mean = sums[c] / count;
-    double var = sums[C + c] / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double invstd = 1.0 / sqrt(var + (double)eps);
-    const float gm = gamma ? gamma[c] : 1.f;
-    const float bt = beta ? beta[c] : 0.f;
-    scale[c] = (float)(gm * invstd);
-    shift[c] = (float)(bt - mean * gm * invstd);
-    if (save_mean) save_mean[c] = (float)mean;
-    if (save_invstd) save_invstd[c] = (float)invstd;
-    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-    if (running_var) {
-        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-    }
-    if (num_batches_tracked && c == 0) *num_batches_tracked += 1;
+    double mean, var;
+    bn_mean_var(sums[c], sums[C + c], count, mean, var);
+    bn_fold_channel(c, mean, var, count, gamma, beta, eps, momentum, running_mean, running_var, scale, shift, save_mean,
+                    save_invstd, num_batches_tracked);
 }
 
 extern "C" int adh_bn_finalize_sums(void* stream, const double* sums, int C, const float* gamma, const float* beta, float eps,
@@ -168,11 +88,8 @@ __global__ void bn_bwd_finalize_sums_kernel(const double* __restrict__ local_sum
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const double count = global_sums[2 * C];
-    if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)local_sums[C + c] : (float)local_sums[C + c];
-    if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)local_sums[c] : (float)local_sums[c];
-    coef[0 * C + c] = (gamma ? gamma[c] : 1.f) * invstd[c];
-    coef[1 * C + c] = (float)(global_sums[c] / count);
-    coef[2 * C + c] = (float)(global_sums[C + c] / count);
+    bn_bwd_coef_channel(c, C, local_sums[c], local_sums[C + c], global_sums[c], global_sums[C + c], count, gamma, invstd, dgamma,
+                        dbeta, accumulate, coef);
 }
 
 extern "C" int adh_bn_bwd_finalize_sums(void* stream, const double* local_sums, const double* global_sums, int C,
@@ -208,12 +125,11 @@ extern "C" int adh_bn_fold_eval(void* stream, int C, const float* gamma, const f
 // ---------------------------------------------------------------------------------------------
 // apply: out = act(y*scale + shift (+ residual))
 // ---------------------------------------------------------------------------------------------
-// Streaming layout shared by the element-wise kernels below: the launch has T = gridDim.x * 256 threads with T a
-// multiple of CQ (channel quads per pixel), so a thread keeps one channel quad for the whole sweep -- its per-channel
-// constants are loaded once and no index division happens inside the loop -- and walks pixels p0, p0 + T/CQ, ...
-// four at a time (4-12 independent 16-byte loads in flight per lane: these kernels are HBM-bound).  The tensors are
-// far larger than L2 + Infinity Cache and each element is touched once per pass, so all of their loads / stores carry the
-// non-temporal hint (measured on 8 x 512 x 1024 x 96: bn_apply 0.632 -> 0.603 ms, bn_bwd_apply 1.30 -> 1.16-1.22 ms).
+// The element-wise kernels below use the streaming layout of bn_stream.h (adh_stream_blocks / adh_stream_decode): a thread
+// keeps one channel quad and walks EW_UNROLL pixels per trip (8-24 independent 16-byte loads in flight per lane: these
+// kernels are HBM-bound).  The tensors are far larger than L2 + Infinity Cache and each element is touched once per pass, so
+// all of their loads / stores carry the non-temporal hint (measured on 8 x 512 x 1024 x 96: bn_apply 0.632 -> 0.603 ms,
+// bn_bwd_apply 1.30 -> 1.16-1.22 ms).
 #ifndef EW_UNROLL
 #define EW_UNROLL 8
 #endif
@@ -228,26 +144,15 @@ extern "C" int adh_bn_fold_eval(void* stream, int C, const float* gamma, const f
 #ifndef EW_MAXBLK_BWD
 #define EW_MAXBLK_BWD (256 * 32)
 #endif
-static int ew_blocks(int64_t P, int CQ, int EW_MAXBLK) {
-    int g = CQ, r = 256;   // gcd(CQ, 256)
-    while (r) { const int t = g % r; g = r; r = t; }
-    const int mult = CQ / g;                                  // blocks must be a multiple of this
-    int64_t want = (P * CQ + 256 * EW_UNROLL - 1) / (256 * EW_UNROLL);
-    if (want > EW_MAXBLK) want = EW_MAXBLK;
-    int64_t blocks = (want + mult - 1) / mult * mult;
-    if (blocks < mult) blocks = mult;
-    return (int)blocks;
-}
 
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ y, int y_cs,
                                                        const float* __restrict__ scale, const float* __restrict__ shift,
                                                        const float* __restrict__ residual, int res_cs, int act,
                                                        float* __restrict__ out, int out_cs, int64_t P, int CQ,
                                                        uint8_t* __restrict__ mask_bits) {
-    const int64_t t = blockIdx.x * (int64_t)256 + threadIdx.x;
-    const int64_t pstep = (int64_t)gridDim.x * 256 / CQ;
-    int64_t p = t / CQ;
-    const int c = (int)(t - p * CQ) * 4;
+    int64_t p, pstep;
+    int c;
+    adh_stream_decode(CQ, p, pstep, c);
     const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + c);
     const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + c);
     for (; p < P; p += EW_UNROLL * pstep) {
@@ -264,7 +169,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
             const int64_t q = p + u * pstep;
             f32x4 w;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) w[j] = fmaf(v[u][j], sc[j], sh[j]);   // (the backward mask below repeats exactly this)
+            for (int j = 0; j < 4; ++j) w[j] = fmaf(v[u][j], sc[j], sh[j]);   // (bn_masked_grad repeats exactly this)
             if (residual) w += r[u];
             if (mask_bits) {
                 // ReLU mask of this quad as a nibble; quads 2m, 2m+1 of a pixel sit in adjacent lanes (CQ is even) and share
@@ -293,8 +198,8 @@ extern "C" int adh_bn_apply(void* stream, const float* y, int y_cs, const float*
     if (!adh_act_host_valid(act)) return ADH_E_ARG;
     const int CQ = C / 4;
     if (mask_bits && ((CQ & 1) || act != ADH_ACT_RELU)) return ADH_E_ARG;   // nibble pairs: an even number of quads per pixel
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_blocks(P, CQ, EW_MAXBLK_APPLY)), dim3(256), 0, (hipStream_t)stream, y, y_cs, scale, shift,
-                       residual, res_cs, act, out, out_cs, P, CQ, mask_bits);
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(adh_stream_blocks(P, CQ, EW_UNROLL, EW_MAXBLK_APPLY)), dim3(256), 0,
+                       (hipStream_t)stream, y, y_cs, scale, shift, residual, res_cs, act, out, out_cs, P, CQ, mask_bits);
     return adh_check_launch();
 }
 
@@ -322,17 +227,11 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
                                                             int C, const float* __restrict__ mask_ss,
                                                             const uint8_t* __restrict__ mask_bits) {
     __shared__ f32x4 red[2][256];
-    // channels in groups of at most 1024 (256 quads, one per thread): one group for every layer of the dehazing branches; the
-    // resnet50 HDEN's 2048-channel BatchNorms (round 4) take two
-  for (int cbase = 0; cbase < C; cbase += 1024) {
-    const int CQ = (C - cbase < 1024 ? C - cbase : 1024) / 4;
-    const int R = 256 / CQ;  // pixel rows handled concurrently
-    const int cq = threadIdx.x % CQ;
-    const int prow = threadIdx.x / CQ;
-    const bool active = prow < R;
-    const int c = cbase + cq * 4;
+  for (int cbase = 0; cbase < C; cbase += 1024) {   // channel groups (bn_stream.h)
+    int CQ, R, prow, c;
+    bn_group_decode(C, cbase, CQ, R, prow, c);
     f32x4 sg = {0.f, 0.f, 0.f, 0.f}, sgx = {0.f, 0.f, 0.f, 0.f};
-    if (active) {
+    if (prow < R) {
         const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + c);
         const f32x4 is = *reinterpret_cast<const f32x4*>(invstd + c);
         // mask_ss = {scale[C], shift[C]} of the forward pass: the ReLU mask is recomputed from y (out is not read)
@@ -357,39 +256,14 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
 #pragma unroll
             for (int u = 0; u < BNB_UNROLL; ++u) {
                 if (p + u * R < p1) {
-                    f32x4 gg = g[u];
-                    if (mask_bits) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) gg[j] = ((mb[u] >> j) & 1) ? gg[j] : 0.f;
-                    } else if (act == ADH_ACT_RELU) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const float ov = mask_ss ? fmaf(yy[u][j], msc[j], msh[j]) : o[u][j];
-                            gg[j] = ov > 0.f ? gg[j] : 0.f;
-                        }
-                    } else if (act != ADH_ACT_NONE) {   // the derivative at the pre-activation (mask_ss is required)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) gg[j] = adh_act_bwd(act, fmaf(yy[u][j], msc[j], msh[j]), gg[j]);
-                    }
+                    const f32x4 gg = bn_masked_grad(g[u], act, mask_bits != nullptr, mb[u], mask_ss != nullptr, yy[u], msc, msh, o[u]);
                     sg += gg;
                     sgx += gg * ((yy[u] - mu) * is);
                 }
             }
         }
     }
-    red[0][threadIdx.x] = sg;
-    red[1][threadIdx.x] = sgx;
-    __syncthreads();
-    if (threadIdx.x < CQ) {
-        f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
-        for (int r = 0; r < R; ++r) {
-            a += red[0][r * CQ + threadIdx.x];
-            b += red[1][r * CQ + threadIdx.x];
-        }
-        *reinterpret_cast<f32x4*>(partials + ((size_t)blockIdx.x * 2 + 0) * C + c) = a;
-        *reinterpret_cast<f32x4*>(partials + ((size_t)blockIdx.x * 2 + 1) * C + c) = b;
-    }
-    __syncthreads();   // (the next channel group reuses `red`)
+    bn_block_fold(red, sg, sgx, CQ, R, c, C, partials);
   }
 }
 
@@ -410,44 +284,12 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __re
                                                                float* dgamma, float* dbeta, int accumulate, float* coef,
                                                                int centered) {
     // centered: row 1 holds sum g m (y - mean) (the fused data-gradient epilogue of conv_wino43.hip): times invstd = sum g m xhat
-    // 32 channels x 32 row slices per block, four independent fp64 chains per thread (latency-bound loop)
     __shared__ double red[2][32][33];
-    const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cx;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
-    if (c < C) {
-        int b = ry;
-        for (; b + 96 < nblk; b += 128) {
-            s0 += (double)partials[((size_t)b * 2 + 0) * pitch + c];
-            q0 += (double)partials[((size_t)b * 2 + 1) * pitch + c];
-            s1 += (double)partials[((size_t)(b + 32) * 2 + 0) * pitch + c];
-            q1 += (double)partials[((size_t)(b + 32) * 2 + 1) * pitch + c];
-            s2 += (double)partials[((size_t)(b + 64) * 2 + 0) * pitch + c];
-            q2 += (double)partials[((size_t)(b + 64) * 2 + 1) * pitch + c];
-            s3 += (double)partials[((size_t)(b + 96) * 2 + 0) * pitch + c];
-            q3 += (double)partials[((size_t)(b + 96) * 2 + 1) * pitch + c];
-        }
-        for (; b < nblk; b += 32) {
-            s0 += (double)partials[((size_t)b * 2 + 0) * pitch + c];
-            q0 += (double)partials[((size_t)b * 2 + 1) * pitch + c];
-        }
-    }
-    red[0][ry][cx] = (s0 + s1) + (s2 + s3);
-    red[1][ry][cx] = (q0 + q1) + (q2 + q3);
-    __syncthreads();
-    if (ry == 0 && c < C) {
-        double S = 0.0, Q = 0.0;
-        for (int r = 0; r < 32; ++r) {
-            S += red[0][r][cx];
-            Q += red[1][r][cx];
-        }
-        if (centered) Q *= (double)invstd[c];
-        if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)Q : (float)Q;
-        if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)S : (float)S;
-        coef[0 * C + c] = (gamma ? gamma[c] : 1.f) * invstd[c];
-        coef[1 * C + c] = (float)(S / count);
-        coef[2 * C + c] = (float)(Q / count);
-    }
+    int c;
+    double S, Q;
+    if (!bn_column_sums<4>(partials, nblk, pitch, C, red, c, S, Q)) return;
+    if (centered) Q *= (double)invstd[c];
+    bn_bwd_coef_channel(c, C, S, Q, S, Q, count, gamma, invstd, dgamma, dbeta, accumulate, coef);
 }
 
 extern "C" int adh_bn_bwd_finalize(void* stream, const float* partials, int nblk, int C, double count,
@@ -479,10 +321,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            int gres_cs, int64_t P, int C, const float* __restrict__ mask_ss,
                                                            const uint8_t* __restrict__ mask_bits) {
     const int CQ = C / 4;
-    const int64_t t = blockIdx.x * (int64_t)256 + threadIdx.x;
-    const int64_t pstep = (int64_t)gridDim.x * 256 / CQ;
-    int64_t p = t / CQ;
-    const int c = (int)(t - p * CQ) * 4;
+    int64_t p, pstep;
+    int c;
+    adh_stream_decode(CQ, p, pstep, c);
     const f32x4 k0 = *reinterpret_cast<const f32x4*>(coef + c);
     f32x4 mg = {0.f, 0.f, 0.f, 0.f}, kx = mg, mu = mg, msc = mg, msh = mg;
     if (mask_ss) {
@@ -510,6 +351,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
         for (int u = 0; u < EW_UNROLL; ++u) {
             const int64_t q = p + u * pstep;
             if (q < P) {
+                // bn_masked_grad (bn_stream.h) written out -- keep the two the same: through the helper hipcc allocates this
+                // kernel's registers differently (194 -> 196 VGPRs) and it measured slower than the spread of its repeats
                 f32x4 gg = g[u];
                 if (mask_bits) {
 #pragma unroll
@@ -545,7 +388,8 @@ extern "C" int adh_bn_bwd_apply(void* stream, const float* g_out, int g_cs, cons
     if (!adh_act_host_valid(act) || (act > ADH_ACT_RELU && !mask_ss)) return ADH_E_ARG;
     if (act == ADH_ACT_RELU && !out && !mask_ss && !mask_bits) return ADH_E_ARG;
     if (mask_bits && (((C / 4) & 1) || act != ADH_ACT_RELU)) return ADH_E_ARG;
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_blocks(P, C / 4, EW_MAXBLK_BWD)), dim3(256), 0, (hipStream_t)stream, g_out, g_cs, out, out_cs, act,
-                       y, y_cs, mean, invstd, coef, training, g_y, gy_cs, g_res, gres_cs, P, C, mask_ss, mask_bits);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(adh_stream_blocks(P, C / 4, EW_UNROLL, EW_MAXBLK_BWD)), dim3(256), 0,
+                       (hipStream_t)stream, g_out, g_cs, out, out_cs, act, y, y_cs, mean, invstd, coef, training, g_y, gy_cs, g_res,
+                       gres_cs, P, C, mask_ss, mask_bits);
     return adh_check_launch();
 }

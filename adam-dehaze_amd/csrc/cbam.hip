@@ -287,16 +287,14 @@ __global__ __launch_bounds__(256) void cbam_sa_kernel(const float* __restrict__ 
     }
 }
 
-// pass 3b: out = x * ca[c] * sa[p] -- streaming, a thread keeps one channel quad (cbam_scale layout = bn_act.hip's):
-// the launch has T threads, T a multiple of CQ; thread t walks pixels t / CQ, + T / CQ, ... eight at a time
+// pass 3b: out = x * ca[c] * sa[p] -- the streaming layout of bn_stream.h, eight pixels per trip
 __global__ __launch_bounds__(256) void cbam_scale_kernel(const float* __restrict__ x, int x_cs, const float* __restrict__ ca,
                                                          const float* __restrict__ sa, int64_t HW, int CQ,
                                                          float* __restrict__ out, int out_cs) {
     const int n = blockIdx.y;
-    const int64_t t = blockIdx.x * (int64_t)256 + threadIdx.x;
-    const int64_t pstep = (int64_t)gridDim.x * 256 / CQ;
-    int64_t p = t / CQ;
-    const int c = (int)(t - p * CQ) * 4;
+    int64_t p, pstep;
+    int c;
+    adh_stream_decode(CQ, p, pstep, c);
     const f32x4 cav = *reinterpret_cast<const f32x4*>(ca + (size_t)n * CQ * 4 + c);
     const float* xn = x + (size_t)n * HW * x_cs;
     float* on = out + (size_t)n * HW * out_cs;
@@ -318,17 +316,6 @@ __global__ __launch_bounds__(256) void cbam_scale_kernel(const float* __restrict
     }
 }
 
-static int cbam_scale_blocks(int64_t HW, int CQ) {
-    int g = CQ, r = 256;   // gcd(CQ, 256)
-    while (r) { const int t = g % r; g = r; r = t; }
-    const int mult = CQ / g;
-    int64_t want = (HW * CQ + 256 * 8 - 1) / (256 * 8);
-    if (want > CBAM_SCALE_MAXBLK) want = CBAM_SCALE_MAXBLK;
-    int64_t blocks = (want + mult - 1) / mult * mult;
-    if (blocks < mult) blocks = mult;
-    return (int)blocks;
-}
-
 extern "C" int adh_cbam_apply(void* stream, const float* x, int x_cs, const float* ca, const float* smap,
                               const float* wsp, int N, int H, int W, int C, float* sa, float* out, int out_cs) {
     if (!x || !ca || !smap || !wsp || !sa || !out || N < 1 || H < 1 || W < 1 || C < 4 || (C & 3) || (x_cs & 3) || (out_cs & 3) ||
@@ -337,8 +324,8 @@ extern "C" int adh_cbam_apply(void* stream, const float* x, int x_cs, const floa
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(cbam_sa_kernel, dim3(adh_ceil_div(W, SA_TW), adh_ceil_div(H, SA_TH), N), dim3(256), 0, s, smap, wsp, H, W,
                        sa);
-    hipLaunchKernelGGL(cbam_scale_kernel, dim3(cbam_scale_blocks((int64_t)H * W, C / 4), N), dim3(256), 0, s, x, x_cs, ca, sa,
-                       (int64_t)H * W, C / 4, out, out_cs);
+    hipLaunchKernelGGL(cbam_scale_kernel, dim3(adh_stream_blocks((int64_t)H * W, C / 4, 8, CBAM_SCALE_MAXBLK), N), dim3(256), 0, s,
+                       x, x_cs, ca, sa, (int64_t)H * W, C / 4, out, out_cs);
     return adh_check_launch();
 }
 
@@ -645,15 +632,14 @@ __global__ __launch_bounds__(256) void cbam_bwd_e_kernel(const float* __restrict
                                                          const float* __restrict__ gpool,
                                                          const int32_t* __restrict__ amax_idx, int HW, int C,
                                                          float* __restrict__ gx, int gx_cs) {
-    // thread = one channel quad for the whole launch (grid = a multiple of CQ / gcd(CQ, 256) blocks, cbam_scale_blocks): its
-    // per-channel constants are loaded once, and four pixels' loads are in flight per trip
+    // the streaming layout of bn_stream.h: a thread's per-channel constants are loaded once, and four pixels' loads are in
+    // flight per trip
     const int n = blockIdx.y;
     const int CQ = C / 4;
     const float invC = 1.0f / (float)C, invHW = 1.0f / (float)HW;
-    const int64_t t = blockIdx.x * (int64_t)256 + threadIdx.x;
-    const int64_t pstep = (int64_t)gridDim.x * 256 / CQ;
-    int64_t p = t / CQ;
-    const int c = (int)(t - p * CQ) * 4;
+    int64_t p, pstep;
+    int c;
+    adh_stream_decode(CQ, p, pstep, c);
     const float* gn = g + (size_t)n * HW * g_cs;
     float* gxn = gx + (size_t)n * HW * gx_cs;
     const f32x4 cav = *reinterpret_cast<const f32x4*>(ca + (size_t)n * C + c);
@@ -697,7 +683,9 @@ extern "C" int adh_cbam_bwd_e(void* stream, const float* g, int g_cs, const floa
     (void)x;
     (void)x_cs;
     if (!g || !ca || !sa || !gsmap || !cidx || !gpool || !amax_idx || !gx || C < 4 || (C & 3)) return ADH_E_ARG;
-    const int blocks = cbam_scale_blocks(HW, C / 4);
+    // 8 although the kernel walks 4 pixels per trip: this is cbam_scale_kernel's grid, the one CBAM_SCALE_MAXBLK's sweep measured
+    // for both kernels (its "one trip per thread" is cbam_scale's trip of 8; this kernel takes two below the cap)
+    const int blocks = adh_stream_blocks(HW, C / 4, 8, CBAM_SCALE_MAXBLK);
     hipLaunchKernelGGL(cbam_bwd_e_kernel, dim3(blocks, N), dim3(256), 0, (hipStream_t)stream, g, g_cs, ca, sa, gsmap, cidx,
                        gpool, amax_idx, HW, C, gx, gx_cs);
     return adh_check_launch();

@@ -58,35 +58,7 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + __expf(-v)); }
-// The activations of the BatchNorm / depthwise epilogues: value at the pre-activation z, and g times the derivative at z with
-// torch autograd's kink conventions (ReLU6: 0 at z = 0 and 6; Hardswish: 0 for z <= -3, 1 for z >= 3; Hardsigmoid: 1/6 only
-// for -3 < z < 3).  The backward passes always work from z, never from the output (Hardswish is not invertible).
-__device__ __forceinline__ bool adh_act_valid(int act) {
-    return act == ADH_ACT_NONE || act == ADH_ACT_RELU || act == ADH_ACT_RELU6 || act == ADH_ACT_HARDSWISH ||
-           act == ADH_ACT_HARDSIGMOID;
-}
-__device__ __forceinline__ float adh_act_fwd(int act, float z) {
-    switch (act) {
-        case ADH_ACT_RELU: return fmaxf(z, 0.f);
-        case ADH_ACT_RELU6: return fminf(fmaxf(z, 0.f), 6.f);
-        case ADH_ACT_HARDSWISH: return z * fminf(fmaxf(z + 3.f, 0.f), 6.f) / 6.f;
-        case ADH_ACT_HARDSIGMOID: return fminf(fmaxf(z + 3.f, 0.f), 6.f) / 6.f;
-        default: return z;
-    }
-}
-__device__ __forceinline__ float adh_act_bwd(int act, float z, float g) {
-    switch (act) {
-        case ADH_ACT_RELU: return z > 0.f ? g : 0.f;
-        case ADH_ACT_RELU6: return (z > 0.f && z < 6.f) ? g : 0.f;
-        case ADH_ACT_HARDSWISH: return z <= -3.f ? 0.f : (z < 3.f ? g * (z / 3.f + 0.5f) : g);
-        case ADH_ACT_HARDSIGMOID: return (z > -3.f && z < 3.f) ? g / 6.f : 0.f;
-        default: return g;
-    }
-}
-static inline bool adh_act_host_valid(int act) {
-    return act == ADH_ACT_NONE || act == ADH_ACT_RELU || act == ADH_ACT_RELU6 || act == ADH_ACT_HARDSWISH ||
-           act == ADH_ACT_HARDSIGMOID;
-}
+// (the activations of the BatchNorm / depthwise epilogues, adh_act_*: bn_stream.h)
 
 // a - b on float4 as two v_pk_fma_f32 (b * (-1) + a, exact: one rounding) instead of the four v_sub_f32 hipcc emits for a
 // vector subtraction; `m1` is -1.0f held in an SGPR the compiler cannot see through (adh_opaque(-1.f)), otherwise it folds
@@ -160,3 +132,7 @@ int adh_wgrad32_class_taps(const adh_conv_desc* d, adh_wg32_taps* tp);
 // is not one of its shapes; conv_igemm.hip then takes the launch)
 int adh_rows_fwd_num_blocks(const adh_conv_desc* d);
 int adh_rows_fwd_launch(void* stream, const adh_conv_desc* d);
+
+// the pieces the streaming kernels share (bn_act.hip, densenet.hip, cbam.hip, depthwise.hip) and the activations adh_act_*; the
+// host-emulation build's stand-in for this file includes the same header
+#include "bn_stream.h"

@@ -23,12 +23,9 @@ extern "C" int adh_bn_slice_stats_num_blocks(int64_t P, int C) {
 __global__ __launch_bounds__(256) void bn_slice_stats_kernel(const float* __restrict__ x, int x_cs, int64_t P, int C,
                                                              float* __restrict__ partials) {
     __shared__ f32x4 red[2][256];
-    for (int cbase = 0; cbase < C; cbase += 1024) {     // channel groups of <= 1024 (256 quads, one per thread)
-        const int CQ = (C - cbase < 1024 ? C - cbase : 1024) / 4;
-        const int R = 256 / CQ;                          // pixel rows handled concurrently
-        const int cq = threadIdx.x % CQ;
-        const int prow = threadIdx.x / CQ;
-        const int c = cbase + cq * 4;
+    for (int cbase = 0; cbase < C; cbase += 1024) {     // channel groups (bn_stream.h)
+        int CQ, R, prow, c;
+        bn_group_decode(C, cbase, CQ, R, prow, c);
         f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = s;
         if (prow < R) {
             const int64_t p0 = (int64_t)blockIdx.x * SS_PPB;
@@ -48,19 +45,7 @@ __global__ __launch_bounds__(256) void bn_slice_stats_kernel(const float* __rest
                     }
             }
         }
-        red[0][threadIdx.x] = s;
-        red[1][threadIdx.x] = q;
-        __syncthreads();
-        if (threadIdx.x < CQ) {
-            f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a;
-            for (int r = 0; r < R; ++r) {
-                a += red[0][r * CQ + threadIdx.x];
-                b += red[1][r * CQ + threadIdx.x];
-            }
-            *reinterpret_cast<f32x4*>(partials + ((size_t)blockIdx.x * 2 + 0) * C + c) = a;
-            *reinterpret_cast<f32x4*>(partials + ((size_t)blockIdx.x * 2 + 1) * C + c) = b;
-        }
-        __syncthreads();   // the next channel group reuses `red`
+        bn_block_fold(red, s, q, CQ, R, c, C, partials);
     }
 }
 
@@ -78,36 +63,12 @@ __global__ __launch_bounds__(1024) void bn_slice_moments_kernel(const float* __r
                                                                 double count, double* __restrict__ mean,
                                                                 double* __restrict__ var) {
     __shared__ double red[2][32][33];
-    const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cx;
-    double s0 = 0.0, s1 = 0.0, q0 = 0.0, q1 = 0.0;
-    if (c < C) {
-        int b = ry;
-        for (; b + 32 < nblk; b += 64) {
-            s0 += (double)partials[((size_t)b * 2 + 0) * pitch + c];
-            q0 += (double)partials[((size_t)b * 2 + 1) * pitch + c];
-            s1 += (double)partials[((size_t)(b + 32) * 2 + 0) * pitch + c];
-            q1 += (double)partials[((size_t)(b + 32) * 2 + 1) * pitch + c];
-        }
-        for (; b < nblk; b += 32) {
-            s0 += (double)partials[((size_t)b * 2 + 0) * pitch + c];
-            q0 += (double)partials[((size_t)b * 2 + 1) * pitch + c];
-        }
-    }
-    red[0][ry][cx] = s0 + s1;
-    red[1][ry][cx] = q0 + q1;
-    __syncthreads();
-    if (ry == 0 && c < C) {
-        double S = 0.0, Q = 0.0;
-        for (int r = 0; r < 32; ++r) {
-            S += red[0][r][cx];
-            Q += red[1][r][cx];
-        }
-        const double m = S / count;
-        const double v = Q / count - m * m;
-        mean[c] = m;
-        var[c] = v < 0.0 ? 0.0 : v;
-    }
+    int c;
+    double S, Q, m, v;
+    if (!bn_column_sums<2>(partials, nblk, pitch, C, red, c, S, Q)) return;
+    bn_mean_var(S, Q, count, m, v);
+    mean[c] = m;
+    var[c] = v;
 }
 
 extern "C" int adh_bn_slice_moments(void* stream, const float* partials, int nblk, int pitch, int C, double count, double* mean,
@@ -120,7 +81,7 @@ extern "C" int adh_bn_slice_moments(void* stream, const float* partials, int nbl
 
 // ---------------------------------------------------------------------------------------------
 // one BatchNorm2d of the block from the shared moments: scale / shift / mean / invstd and nn.BatchNorm2d's buffer update
-// (momentum, unbiased running variance, num_batches_tracked += 1) -- adh_bn_finalize's arithmetic after its reduce
+// (momentum, unbiased running variance, num_batches_tracked += 1) -- bn_fold_channel, as adh_bn_finalize after its reduce
 // ---------------------------------------------------------------------------------------------
 __global__ void bn_fold_moments_kernel(int C, const double* __restrict__ mean, const double* __restrict__ var, double count,
                                        const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
@@ -128,20 +89,8 @@ __global__ void bn_fold_moments_kernel(int C, const double* __restrict__ mean, c
                                        float* save_mean, float* save_invstd, int64_t* num_batches_tracked) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const double m = mean[c], v = var[c];
-    const double invstd = 1.0 / sqrt(v + (double)eps);
-    const float gm = gamma ? gamma[c] : 1.f;
-    const float bt = beta ? beta[c] : 0.f;
-    scale[c] = (float)(gm * invstd);
-    shift[c] = (float)(bt - m * gm * invstd);
-    if (save_mean) save_mean[c] = (float)m;
-    if (save_invstd) save_invstd[c] = (float)invstd;
-    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-    if (running_var) {
-        const double unbiased = count > 1.0 ? v * count / (count - 1.0) : v;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-    }
-    if (num_batches_tracked && c == 0) *num_batches_tracked += 1;
+    bn_fold_channel(c, mean[c], var[c], count, gamma, beta, eps, momentum, running_mean, running_var, scale, shift, save_mean,
+                    save_invstd, num_batches_tracked);
 }
 
 extern "C" int adh_bn_fold_moments(void* stream, int C, const double* mean, const double* var, double count, const float* gamma,
@@ -205,11 +154,9 @@ __global__ __launch_bounds__(256) void bn_preact_bwd_accum_kernel(const float* _
                                                                   const float* __restrict__ coef, int training,
                                                                   float* __restrict__ dbuf, int dbuf_cs, int64_t P, int C,
                                                                   int accumulate) {
-    const int CQ = C / 4;
-    const int64_t t = blockIdx.x * (int64_t)256 + threadIdx.x;
-    const int64_t pstep = (int64_t)gridDim.x * 256 / CQ;
-    int64_t p = t / CQ;
-    const int c = (int)(t - p * CQ) * 4;
+    int64_t p, pstep;
+    int c;
+    adh_stream_decode(C / 4, p, pstep, c);
     const f32x4 k0 = *reinterpret_cast<const f32x4*>(coef + c);
     const f32x4 msc = *reinterpret_cast<const f32x4*>(ss + c);
     const f32x4 msh = *reinterpret_cast<const f32x4*>(ss + C + c);
@@ -232,8 +179,8 @@ __global__ __launch_bounds__(256) void bn_preact_bwd_accum_kernel(const float* _
         for (int u = 0; u < PB_UNROLL; ++u) {
             const int64_t q = p + u * pstep;
             if (q < P) {
-                f32x4 gg = g[u];
-#pragma unroll
+                f32x4 gg = g[u];   // bn_masked_grad's (bn_stream.h) ReLU-from-(scale, shift) form, written out: through the helper
+#pragma unroll             // hipcc allocates this kernel's registers differently (156 -> 158 VGPRs) and it measured slower
                 for (int j = 0; j < 4; ++j) gg[j] = fmaf(xx[u][j], msc[j], msh[j]) > 0.f ? gg[j] : 0.f;
                 f32x4 r = training ? k0 * (gg - mg - (xx[u] - mu) * kx) : k0 * gg;
                 if (accumulate) r += d[u];
@@ -250,15 +197,7 @@ extern "C" int adh_bn_preact_bwd_accum(void* stream, const float* dA, int dA_cs,
         ((dA_cs | x_cs | dbuf_cs) & 3))
         return ADH_E_ARG;
     if (training && (!mean || !invstd)) return ADH_E_ARG;
-    const int CQ = C / 4;
-    int g = CQ, r = 256;   // blocks: a multiple of CQ / gcd(CQ, 256), so that a thread keeps one channel quad
-    while (r) { const int t = g % r; g = r; r = t; }
-    const int mult = CQ / g;
-    int64_t want = (P * CQ + 256 * PB_UNROLL - 1) / (256 * PB_UNROLL);
-    if (want > PB_MAXBLK) want = PB_MAXBLK;
-    int64_t blocks = (want + mult - 1) / mult * mult;
-    if (blocks < mult) blocks = mult;
-    hipLaunchKernelGGL(bn_preact_bwd_accum_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dA, dA_cs, x, x_cs,
-                       ss, mean, invstd, coef, training, dbuf, dbuf_cs, P, C, accumulate);
+    hipLaunchKernelGGL(bn_preact_bwd_accum_kernel, dim3(adh_stream_blocks(P, C / 4, PB_UNROLL, PB_MAXBLK)), dim3(256), 0,
+                       (hipStream_t)stream, dA, dA_cs, x, x_cs, ss, mean, invstd, coef, training, dbuf, dbuf_cs, P, C, accumulate);
     return adh_check_launch();
 }

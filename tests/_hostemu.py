@@ -28,6 +28,7 @@ def build(tmp, hip, driver, defines=(), exe="emu"):
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     assert cxx, "no host C++ compiler found"
     shutil.copy(os.path.join(ROOT, "adam-dehaze_amd", "csrc", hip + ".hip"), tmp / (hip + ".cpp"))
+    shutil.copy(os.path.join(ROOT, "adam-dehaze_amd", "csrc", "bn_stream.h"), tmp / "bn_stream.h")   # compiled as it ships
     for fn in ("common.h", "stream_rt.h", "stream_rt.cpp", driver):      # the copy's #include "common.h" finds the stand-in
         shutil.copy(os.path.join(ROOT, "tools", "host_emu", fn), tmp / fn)
     out = tmp / exe

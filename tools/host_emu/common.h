@@ -97,36 +97,14 @@ static inline void sincospif(float x, float* s, float* c) {
 // What csrc/bn_act.hip, csrc/depthwise.hip, csrc/densenet.hip, csrc/image_io.hip and csrc/d4.hip (tests/test_d4_hostemu_cpu.py; its
 // transposing kernel stages a static LDS tile between barriers) take beyond the ADH_HOST_EMU section; their drivers link
 // stream_rt.cpp, whose emu_launch walks grid.x, grid.y and grid.z.  The non-temporal builtins are plain loads and stores.  The
-// activation helpers are copies of csrc/common.h's: keep them the same.
+// activation helpers and the shared BatchNorm pieces are csrc/bn_stream.h itself, included at the end of this section as
+// csrc/common.h includes it at its end (the path is found from include/, which every build of this file has on its include path).
 #include <atomic>
 #define __builtin_nontemporal_load(p) (*(p))
 #define __builtin_nontemporal_store(v, p) (*(p) = (v))
 static inline int adh_max_i(int a, int b) { return a > b ? a : b; }
 #define __builtin_amdgcn_readfirstlane(v) (v)   // csrc/d4.hip: a value its caller knows to be wave-uniform
 static inline float __fmul_rn(float a, float b) { return a * b; }   // csrc/image_io.hip: a product nothing is contracted into
-static inline bool adh_act_valid(int act) {
-    return act == ADH_ACT_NONE || act == ADH_ACT_RELU || act == ADH_ACT_RELU6 || act == ADH_ACT_HARDSWISH ||
-           act == ADH_ACT_HARDSIGMOID;
-}
-static inline float adh_act_fwd(int act, float z) {
-    switch (act) {
-        case ADH_ACT_RELU: return fmaxf(z, 0.f);
-        case ADH_ACT_RELU6: return fminf(fmaxf(z, 0.f), 6.f);
-        case ADH_ACT_HARDSWISH: return z * fminf(fmaxf(z + 3.f, 0.f), 6.f) / 6.f;
-        case ADH_ACT_HARDSIGMOID: return fminf(fmaxf(z + 3.f, 0.f), 6.f) / 6.f;
-        default: return z;
-    }
-}
-static inline float adh_act_bwd(int act, float z, float g) {
-    switch (act) {
-        case ADH_ACT_RELU: return z > 0.f ? g : 0.f;
-        case ADH_ACT_RELU6: return (z > 0.f && z < 6.f) ? g : 0.f;
-        case ADH_ACT_HARDSWISH: return z <= -3.f ? 0.f : (z < 3.f ? g * (z / 3.f + 0.5f) : g);
-        case ADH_ACT_HARDSIGMOID: return (z > -3.f && z < 3.f) ? g / 6.f : 0.f;
-        default: return g;
-    }
-}
-static inline bool adh_act_host_valid(int act) { return adh_act_valid(act); }
 // __shfl_xor(v, mask, 64): lanes t and t ^ mask exchange through one mailbox per lane and wait for nobody else, so a pair may
 // shuffle inside a loop the rest of its workgroup has already left (bn_apply_kernel).  A lane's n-th shuffle posts into slot
 // n & 1 and publishes n + 1; its partner cannot post n + 2 before it has read n, so two slots are enough.  A lane whose
@@ -147,4 +125,5 @@ static inline int __shfl_xor(int v, int mask, int width) {
     while (theirs.seq.load(std::memory_order_acquire) < n + 1) std::this_thread::yield();
     return theirs.val[n & 1];
 }
+#include "../adam-dehaze_amd/csrc/bn_stream.h"
 #endif
