@@ -160,7 +160,7 @@ extern "C" int adh_cbam_pool(void* stream, const float* x, int x_cs, int N, int 
 __global__ __launch_bounds__(256) void cbam_mlp_kernel(const float* __restrict__ pooled, const float* __restrict__ w1,
                                                        const float* __restrict__ w2, int C, int Ch,
                                                        float* __restrict__ ca, float* __restrict__ hidden) {
-    extern __shared__ float sm[];  // [2][C] pooled, [2][Ch] hidden
+    ADH_DYN_LDS(float, sm);  // [2][C] pooled, [2][Ch] hidden
     float* pv = sm;
     float* hv = sm + 2 * C;
     const int n = blockIdx.x;
@@ -552,7 +552,7 @@ __global__ __launch_bounds__(256) void cbam_bwd_d1_kernel(const float* __restric
 __global__ __launch_bounds__(256) void cbam_bwd_d2_kernel(const float* __restrict__ gpre_all, const float* __restrict__ hidden,
                                                           const float* __restrict__ w1, const float* __restrict__ w2, int C,
                                                           int Ch, float* __restrict__ ghid_all, float* __restrict__ gpool) {
-    extern __shared__ float sm[];
+    ADH_DYN_LDS(float, sm);
     float* gpre = sm;            // [C]
     float* ghid = sm + C;        // [2][Ch]
     const int n = blockIdx.x;

@@ -47,16 +47,7 @@ struct ConvGeom {
     int xp;                 // wgrad: floats per staged input pixel (32, or Cin alloc (8) in packed small-Cin mode)
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
+#include "wave.h"   // wave_sum, wave_max (shared with the host-emulation build)
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + __expf(-v)); }
 // (the activations of the BatchNorm / depthwise epilogues, adh_act_*: bn_stream.h)
 

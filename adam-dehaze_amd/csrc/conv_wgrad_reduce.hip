@@ -58,7 +58,6 @@ extern "C" int adh_wgrad_reduce(void* stream, const float* slab, int nsplit, int
     return adh_check_launch();
 }
 
-#ifndef ADH_HOST_EMU   // wave_sum is a cross-lane shuffle: this kernel runs on the GPU only
 // dst(layout L) (+)= sum over slabs[s][tap][k][n]: one wave per output element (few outputs, hundreds of slabs: the
 // thread-per-output kernel above would run one long dependent chain per thread)
 __global__ __launch_bounds__(256) void wgrad_reduce_wave_kernel(const float* __restrict__ slab, int nslabs, int KP, int NcP,
@@ -85,7 +84,6 @@ extern "C" int adh_wgrad_reduce_small(void* stream, const float* slab, int nslab
                        slab, nslabs, KP, NcP, *L, dst, accumulate);
     return adh_check_launch();
 }
-#endif
 
 // Packed small-Cin slabs: slab[s][tap=(ky*KWg+kxg)][i=(kxl*8+ci)][NcP] -> dst OIHW [Cout][Cin][KH][KW]
 __global__ void wgrad_reduce_packed_kernel(const float* __restrict__ slab, int nsplit, int NcP, int Cin, int KH, int KW,

@@ -121,7 +121,7 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const float* __restrict__ 
 }
 
 __global__ __launch_bounds__(256) void nms_scan_kernel(const unsigned long long* __restrict__ mask, int M, int words, int* __restrict__ keep) {
-    extern __shared__ unsigned long long removed[];
+    ADH_DYN_LDS(unsigned long long, removed);
     for (int w = threadIdx.x; w < words; w += 256) removed[w] = 0ull;
     __syncthreads();
     for (int i = 0; i < M; ++i) {
@@ -177,8 +177,9 @@ __global__ __launch_bounds__(256) void roi_align_fpn_kernel(const adh_fpn_levels
     const int n = (int)roi[0];
     const float x1 = roi[1], y1 = roi[2], x2 = roi[3], y2 = roi[4];
     const float s = sqrtf((x2 - x1) * (y2 - y1));
-    int lvl = (int)floorf(4.f + log2f(s / 224.f) + 1e-6f);
-    lvl = adh_min_i(adh_max_i(lvl, 2), 5) - 2;
+    // clamped in float, before the conversion: a RoI of zero area gives log2f(0) = -inf and one of negative area NaN, which no
+    // int holds (the conversion is undefined in C++; fmaxf drops the NaN: level 0, like -inf)
+    int lvl = (int)fminf(fmaxf(floorf(4.f + log2f(s / 224.f) + 1e-6f), 2.f), 5.f) - 2;
     lvl = adh_min_i(lvl, L.nlevels - 1);
     const float sc = L.scale[lvl];
     const int H = L.H[lvl], W = L.W[lvl], cs = L.cs[lvl];

@@ -74,7 +74,9 @@ extern "C" int adh_lpips_s2d_bwd(void* stream, const float* g, int N, int H, int
 // per-tap distance: 8 lanes per pixel, shuffles for the channel reductions
 // ---------------------------------------------------------------------------------------------
 #define LP_EPS 1e-10f
-#define LP_PPB 1024
+#ifndef LP_PPB
+#define LP_PPB 1024      // pixels per block of lpips_layer_kernel
+#endif
 
 extern "C" int adh_lpips_layer_num_blocks(int HW) { return adh_ceil_div(HW, LP_PPB); }
 

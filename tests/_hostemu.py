@@ -1,4 +1,5 @@
-"""Shared by tests/test_{bn_act,depthwise,densenet}_hostemu_cpu.py: builds a copy of one csrc/*.hip file with the host C++
+"""Shared by the tests/test_*_hostemu_cpu.py that run on tools/host_emu/stream_rt.cpp (bn_act, depthwise, densenet, image_io, d4,
+ciede2000, cbam, lpips, detect, and the shuffle's self-test): builds a copy of one csrc/*.hip file with the host C++
 compiler against tools/host_emu (common.h's ADH_HOST_EMU_STREAM section, stream_rt.cpp, the file's driver) under
 AddressSanitizer and UndefinedBehaviorSanitizer, and runs scripts (tools/host_emu/stream_rt.h) through the resulting stand-alone
 program.  Nothing is loaded into Python.
@@ -23,19 +24,26 @@ WPOISON = 0x7FC0BEEF        # slack and unwritten elements of a tensor that is w
 TIMEOUT = 120
 
 
-def build(tmp, hip, driver, defines=(), exe="emu"):
-    """compile csrc/<hip>.hip + tools/host_emu/<driver> + stream_rt.cpp in the directory `tmp`; returns the program's path"""
+FLOAT_CAST = "address,undefined,float-cast-overflow"     # -fsanitize=undefined leaves a float -> int conversion out of range to g++
+
+
+def build(tmp, hip, driver, defines=(), exe="emu", sanitize="address,undefined"):
+    """compile csrc/<hip>.hip + tools/host_emu/<driver> + stream_rt.cpp in the directory `tmp`; returns the program's path.
+    hip = None: the driver brings its own kernel (tools/host_emu/shuffle_main.cpp)."""
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     assert cxx, "no host C++ compiler found"
-    shutil.copy(os.path.join(ROOT, "adam-dehaze_amd", "csrc", hip + ".hip"), tmp / (hip + ".cpp"))
-    shutil.copy(os.path.join(ROOT, "adam-dehaze_amd", "csrc", "bn_stream.h"), tmp / "bn_stream.h")   # compiled as it ships
+    srcs = [driver, "stream_rt.cpp"]
+    if hip is not None:
+        shutil.copy(os.path.join(ROOT, "adam-dehaze_amd", "csrc", hip + ".hip"), tmp / (hip + ".cpp"))
+        srcs.insert(0, hip + ".cpp")
+    for fn in ("bn_stream.h", "wave.h"):                                  # compiled as they ship
+        shutil.copy(os.path.join(ROOT, "adam-dehaze_amd", "csrc", fn), tmp / fn)
     for fn in ("common.h", "stream_rt.h", "stream_rt.cpp", driver):      # the copy's #include "common.h" finds the stand-in
         shutil.copy(os.path.join(ROOT, "tools", "host_emu", fn), tmp / fn)
     out = tmp / exe
     subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-DADH_HOST_EMU", "-DADH_HOST_EMU_STREAM", *["-D" + d for d in defines],
-                    "-I", os.path.join(ROOT, "include"), "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-Wno-unknown-pragmas", "-pthread", str(tmp / (hip + ".cpp")), str(tmp / driver), str(tmp / "stream_rt.cpp"),
-                    "-o", str(out)], check=True, cwd=tmp)
+                    "-I", os.path.join(ROOT, "include"), "-fsanitize=" + sanitize, "-fno-sanitize-recover=all",
+                    "-Wno-unknown-pragmas", "-pthread", *[str(tmp / f) for f in srcs], "-o", str(out)], check=True, cwd=tmp)
     return out
 
 

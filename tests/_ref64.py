@@ -2,7 +2,9 @@
 operations' definitions (numpy / torchvision / lpips / torch.optim semantics), not from the kernels.  Inputs are the fp32
 tensors a kernel receives; everything is promoted to float64 first, so a result is the exact operation on those inputs
 up to float64 rounding.  tests/test_ref64_cpu.py checks each function against oracle.ref_cpu on small inputs; the GPU
-tests compare the kernels with these.  All functions run on whatever device their inputs live on."""
+tests compare the kernels with these, and so do the host-emulation tests of the same sources (tests/test_lpips_hostemu_cpu.py,
+tests/test_detect_hostemu_cpu.py); the error bounds of the LPIPS distance kernels, in EPS = 2^-24 relative to the sum of |terms|
+added, are at the end of the file for both to share.  All functions run on whatever device their inputs live on."""
 import math
 
 import numpy as np
@@ -315,3 +317,124 @@ def lpips_layer_grad(fa, fb, w, g_val):
     dot = (delta * a).sum(-1, keepdim=True)
     k2 = torch.where(r > 0, dot / (r.clamp_min(1e-300) * s * s), torch.zeros_like(r))
     return delta / s - a * k2
+
+
+# ---- the bounds tests/test_gpu_lpips.py and tests/test_lpips_hostemu_cpu.py hold the distance kernels to; the comments name the
+# fp32 operations behind each count.  (Every product and sum is counted apart, so a host build, which does not contract
+# a * b + c, is held to the same figures.)
+EPS = 2.0 ** -24
+
+
+def lpips_features(N, HW, C_, randn, rand):
+    """post-ReLU-like features: |randn| with ~30 % zeros; by pixel index (p + n) % 7: 1 -> fa all zero, 2 -> fb all zero,
+    3 -> both all zero, 4 -> fa == fb, 5 -> one channel of fa dominant by 1e4.  randn / rand(k, *shape): the k-th draw.
+    -> (fa, fb, w, the pixel classes [N, HW])"""
+    def base(k):
+        return randn(k, N, HW, C_).abs() * (rand(k + 1, N, HW, C_) > 0.3)
+    fa, fb = base(0), base(2)
+    fam = (torch.arange(HW, device=fa.device)[None, :] + torch.arange(N, device=fa.device)[:, None]) % 7
+    fa[(fam == 1) | (fam == 3)] = 0.0
+    fb[(fam == 2) | (fam == 3)] = 0.0
+    fb[fam == 4] = fa[fam == 4]
+    dom = fa[..., C_ // 2]
+    dom[fam == 5] = 1e4
+    w = rand(4, C_)
+    return fa.contiguous(), fb.contiguous(), w, fam
+
+
+def lpips_lane_terms(C_):
+    """roundings of a C-channel sum as the kernels do it: four products summed pairwise per quad (3), C / 32 quads added
+    serially per lane, a 3-level tree over the 8 lanes of the pixel group."""
+    return -(-C_ // 32) + 6
+
+
+def lpips_norm_terms(C_):
+    """relative error of 1 / (sqrt(sum a^2) + 1e-10) in EPS: half the sum's, sqrtf, the fp32 constant and sum, the reciprocal."""
+    return lpips_lane_terms(C_) / 2 + 3
+
+
+def lpips_layer_blocks(fa, fb, w, ppb):
+    """-> (per-pixel distance [N, HW], per-block sums [N, nblk], the bound of the per-block sums) for blocks of ppb pixels"""
+    N, HW, C_ = fa.shape
+    nblk = -(-HW // ppb)
+    a, b, w64 = fa.double(), fb.double(), w.double()
+    na = a / (a.pow(2).sum(-1, keepdim=True).sqrt() + 1e-10)
+    nb = b / (b.pow(2).sum(-1, keepdim=True).sqrt() + 1e-10)
+    dpix = lpips_pixel(fa, fb, w)                                                       # [N, HW]
+    # per pixel: na and nb carry (norm + 1) EPS each, their difference one more; w df^2 doubles df's error and adds two
+    # products; the channel sum of the terms: lpips_lane_terms
+    kin = lpips_norm_terms(C_)
+    e_df = EPS * ((kin + 1) * (na.abs() + nb.abs()) + (na - nb).abs())
+    # (w e_df^2 is the second-order term: it is all there is where na == nb)
+    e_pix = (w64 * (2 * (na - nb).abs() * e_df + e_df ** 2)).sum(-1) + (lpips_lane_terms(C_) + 2) * EPS * dpix
+    # per block: 32 pixels added serially per thread, a 6-level wave tree, two more sums
+    pad = nblk * ppb - HW
+    blk = lambda t: F.pad(t, (0, pad)).view(N, nblk, ppb).sum(-1)
+    return dpix, blk(dpix), blk(e_pix) + 40 * EPS * blk(dpix)
+
+
+def lpips_layer_grad_bound(fa, fb, w, g_val, ref):
+    """the bound of lpips_layer_grad's result `ref` as csrc/lpips.hip computes it"""
+    N, HW, C_ = fa.shape
+    a, b, w64 = fa.double(), fb.double(), w.double()
+    r = a.pow(2).sum(-1, keepdim=True).sqrt()
+    s = r + 1e-10
+    na, nb = a / s, b / (b.pow(2).sum(-1, keepdim=True).sqrt() + 1e-10)
+    kin, kl = lpips_norm_terms(C_), lpips_lane_terms(C_)
+    gk = (g_val.double() / HW).view(-1, 1, 1)
+    # delta = w (na - nb) (2 gk): the difference as in the forward, gk = g / HW (1), three products
+    e_df = EPS * ((kin + 1) * (na.abs() + nb.abs()) + (na - nb).abs())
+    dl = 2 * w64 * (na - nb) * gk
+    e_dl = 2 * (w64 * gk).abs() * e_df + 4 * EPS * dl.abs()
+    # dot = sum delta a: the terms' own errors, one product each and the channel sum
+    dota = (dl * a).abs().sum(-1, keepdim=True)
+    e_dot = (a.abs() * e_dl).sum(-1, keepdim=True) + (kl + 1) * EPS * dota
+    # k2 = dot / (r s s): sqrtf's and the sum's error three times over, two products, one division
+    den = (r * s * s).clamp_min(1e-300)
+    pos = r > 0
+    e_k2 = torch.where(pos, (e_dot + (3 * kin + 3) * EPS * dota) / den, torch.zeros_like(r))
+    k2 = torch.where(pos, (dl * a).sum(-1, keepdim=True) / den, torch.zeros_like(r))
+    # out = delta / s - a k2: 1 / s carries kin, two products, one difference
+    return e_dl / s + (kin + 1) * EPS * (dl / s).abs() + a.abs() * e_k2 + 2 * EPS * (a * k2).abs() + EPS * ref.abs()
+
+
+# ---- the bounds tests/test_gpu_detect_kernels.py and tests/test_detect_hostemu_cpu.py hold the detector kernels to
+# expf of the box decodes (rpn_decode_kernel, box_postprocess_kernel), in EPS relative to its result: measured 1, bound 4
+# (the GPU tests print "expf units needed": at most 0.57 beyond the plain roundings in the RPN decode, nothing beyond them in
+# the box head, scores or boxes)
+EXP_UNITS = 4
+
+
+def rpn_decode_bounds(mag, pwh):
+    """(the plain roundings, the whole bound) of adh_rpn_decode's boxes from decode_clip's magnitudes.
+    Anchor width / centre are exact (small integers and halves).  pcx = d w + cx: two roundings (one with FMA) of
+    |d w| + |pcx|; pw = expf(dw) w: expf and a product; the clamp constant log(1000 / 16) is fp32: half an ulp of 4.1 is
+    4 EPS on the exponent, so 4 EPS of pw; pcx -+ pw / 2: one more rounding, of the result"""
+    plain = EPS * 2 * mag
+    return plain, plain + (EXP_UNITS + 6) * EPS * 0.5 * pwh
+
+
+def roi_align_bound(rois, mag, scale, vmax):
+    """rois [R, 5] of one level, mag from roi_align, vmax = max |feature| of the level.
+    Per sample: hy = 1 - ly, the weight product, four products with the values and three sums (6 EPS of the sum of
+    |weight * value|); four samples added (3) and the exact scale by 0.25; 12 with margin for the order.
+    Sample coordinate: x2 s - x1 s, / 7, ph * bin, (i + .5) * bin / 2 and two sums: 6 roundings of at most
+    |start| + extent; a coordinate error d moves a bilinear sample by at most d * 2 max|value| per axis."""
+    rd = rois.double()
+    ext = (rd[:, 1:3].abs().amax(1) + (rd[:, 3:5] - rd[:, 1:3]).abs().amax(1)) * scale + 1.0
+    return 12 * EPS * mag + (6 * EPS * ext * 4 * vmax).view(-1, 1, 1, 1)
+
+
+def box_postprocess_bounds(logits, rs, mag, pwh):
+    """logits [R, NC]; rs, mag, pwh from box_postprocess -> (plain score roundings, score bound, plain box roundings, box bound).
+    score = expf(l - m) / sum: l - m rounds once (EPS |l - m| on the exponent), expf, the NC-term sum of expf values
+    (each its own expf error, ceil(NC / 64) serial additions per lane and a 6-level tree), one division; its own exponent
+    roundings weigh in by the softmax-weighted mean of |l - m| <= ln NC.
+    box: d / 10 and d / 5 round once each (the latter moves expf by EPS |dw| <= 4.2 EPS), then as in the RPN decode
+    (product 1, fp32 clamp constant 4): 10 EPS of pw / 2 besides expf"""
+    NC = logits.shape[1]
+    lg = logits.double()
+    dist = (lg.amax(1, keepdim=True) - lg)[:, 1:]
+    plain_s = (dist + -(-NC // 64) + 8 + math.log(NC)) * EPS * rs + 1e-37
+    plain_b = EPS * 3 * mag
+    return plain_s, plain_s + 2 * EXP_UNITS * EPS * rs, plain_b, plain_b + (EXP_UNITS + 10) * EPS * 0.5 * pwh

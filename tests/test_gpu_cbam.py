@@ -7,20 +7,20 @@ caps.
 Every output buffer is prefilled with NaN (index buffers with -7): a kernel must write every element it owns, and
 everything outside the channel slice it owns must still be NaN afterwards.  Every entry point runs twice and must
 reproduce itself bit for bit.  Tolerances are in units of EPS = 2^-24, the fp32 unit roundoff, relative to the sum of
-|terms| the kernel adds, and each comment says which fp32 operations bound it."""
+|terms| the kernel adds; the float64 restatements and their bounds are tests/_cbam_ref64.py's, which the host-emulation run of
+the same source (tests/test_cbam_hostemu_cpu.py) shares."""
 import pytest
 import torch
-import torch.nn.functional as F
 
 from adam_dehaze_amd import _hip as H
 from adam_dehaze_amd.engine import Act, Engine
+from tests import _cbam_ref64 as R
+from tests._cbam_ref64 import APPLY_HW, EPS, POOL_PPB
 from tests.test_gpu_fullsize import _cbam_ref64
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-EPS = 2.0 ** -24
 NAN = float("nan")
-POOL_PPB = 512          # pixels per block of the pooling partials (cbam.hip)
 
 
 def _nan(*shape):
@@ -62,19 +62,7 @@ def _twice(fn):
     return a
 
 
-def _first_argmax(x, dim):
-    """index of the FIRST maximum along dim (torch.argmax does not promise which of equal maxima it returns)."""
-    n = x.shape[dim]
-    shape = [1] * x.dim()
-    shape[dim] = n
-    ar = torch.arange(n, device=x.device).view(shape)
-    return torch.where(x == x.amax(dim, keepdim=True), ar, n).amin(dim)
-
-
-def _assert_bound(got, ref64, bound, what):
-    assert not torch.isnan(got).any(), f"{what}: NaN (an element was not written)"
-    d = (got.double() - ref64).abs() - bound
-    assert float(d.max()) <= 0, f"{what}: exceeds its bound by {float(d.max()):.3e}"
+_assert_bound = R.assert_bound
 
 
 # ------------------------------------------------------------------------------------------------ channel pooling
@@ -112,9 +100,10 @@ def test_cbam_pool_ties_first_index(C, HW):
             xb[:, p, 3] = 2.0
     x = xb[..., :C].double()
     pooled, amax = _run_pool(xb, x_cs, N, HW, C)
-    assert torch.equal(pooled[:, 0].double(), (x.sum(1) / HW).float().double()), "mean"
-    assert torch.equal(pooled[:, 1].double(), x.amax(1)), "max"
-    assert torch.equal(amax.long(), _first_argmax(x, 1)), "arg-max must be the first index in scan order"
+    mean, mx, first = R.pool64(x)
+    assert torch.equal(pooled[:, 0].double(), mean), "mean"
+    assert torch.equal(pooled[:, 1].double(), mx), "max"
+    assert torch.equal(amax.long(), first), "arg-max must be the first index in scan order"
     if HW > 10 * POOL_PPB:
         assert (amax[:, 3] == POOL_PPB + 100).all()
 
@@ -134,18 +123,10 @@ def test_cbam_mlp(C):
         return ca, hidden
 
     ca, hidden = _twice(run)
-    p64, W1, W2 = pooled.double(), w1.double(), w2.double()
-    pre = p64 @ W1.t()                                        # [N, 2, Ch]
-    pre_abs = p64.abs() @ W1.abs().t()
-    # hidden: C / 64 fp32 products per lane, then a 64-lane tree: C / 64 + 8 roundings of the sum of |terms|
-    e_h = (C / 64 + 8) * EPS * pre_abs
-    _assert_bound(hidden, torch.relu(pre), e_h, "hidden")
+    h, e_h, ca_ref, e_ca = R.mlp64(pooled, w1, w2)
+    _assert_bound(hidden, h, e_h, "hidden")
     assert (hidden[:, :, 0] == 0).all()
-    h = torch.relu(pre)
-    logit = (h[:, 0] + h[:, 1]) @ W2.t()
-    # ca: two Ch-term fp32 sums and their sum, the hidden errors through |W2|; sigmoid' <= 1/4, expf and the division
-    e_logit = (Ch + 4) * EPS * ((h[:, 0] + h[:, 1]) @ W2.abs().t()) + (e_h[:, 0] + e_h[:, 1]) @ W2.abs().t()
-    _assert_bound(ca, torch.sigmoid(logit), 0.25 * e_logit + 8 * EPS, "ca")
+    _assert_bound(ca, ca_ref, e_ca, "ca")
 
 
 # ------------------------------------------------------------------------------------------------ spatial statistics
@@ -168,25 +149,13 @@ def test_cbam_spatial_stats_ties_first_index(C, HW):
         return smap, cidx
 
     smap, cidx = _twice(run)
-    v = xb[..., :C].double() * ca.double()[:, None, :]
-    mean = v.sum(2) / C
-    # the sum is exact (multiples of 1/8 below 2^12); times fp32(1 / C): two roundings
-    _assert_bound(smap[..., 0], mean, 3 * EPS * mean.abs(), "channel mean")
-    assert torch.equal(smap[..., 1].double(), v.amax(2)), "channel max"
-    assert torch.equal(cidx.long(), _first_argmax(v, 2)), "channel arg-max must be the first index"
+    mean, e_mean, mx, first = R.spatial_stats64(xb[..., :C], ca)
+    _assert_bound(smap[..., 0], mean, e_mean, "channel mean")
+    assert torch.equal(smap[..., 1].double(), mx), "channel max"
+    assert torch.equal(cidx.long(), first), "channel arg-max must be the first index"
 
 
 # ------------------------------------------------------------------------------------------------ spatial attention + apply
-APPLY_HW = [(1, 1), (1, 40), (2, 7), (6, 33), (7, 8), (8, 6), (33, 40), (40, 2), (7, 7), (2, 1)]
-
-
-def _sa_ref(smap, wsp, N, Hh, Ww):
-    s = smap.view(N, Hh, Ww, 2).permute(0, 3, 1, 2).double()
-    pre = F.conv2d(s, wsp.double().view(1, 2, 7, 7), padding=3)[:, 0]
-    terms = F.conv2d(s.abs(), wsp.double().abs().view(1, 2, 7, 7), padding=3)[:, 0]
-    return torch.sigmoid(pre), terms
-
-
 def _check_apply(N, Hh, Ww, C, x_cs, out_cs, seed):
     HW = Hh * Ww
     xb = _randn(N, Hh, Ww, x_cs, seed=seed)
@@ -201,12 +170,10 @@ def _check_apply(N, Hh, Ww, C, x_cs, out_cs, seed):
         return sa, ob
 
     sa, ob = _twice(run)
-    sa_ref, terms = _sa_ref(smap, wsp, N, Hh, Ww)
-    # 98 products summed in one fp32 chain (ky, kx, channel order); sigmoid' <= 1/4; expf and the division
-    _assert_bound(sa.view(N, Hh, Ww), sa_ref, 0.25 * 100 * EPS * terms + 8 * EPS, "sa")
+    sa_ref, e_sa = R.sa64(smap, wsp, N, Hh, Ww)
+    _assert_bound(sa.view(N, Hh, Ww), sa_ref, e_sa, "sa")
     # out = (x * ca) * sa, two roundings in that order: equal to the same two fp32 products
-    want = xb[..., :C] * ca.view(N, 1, 1, C) * sa.view(N, Hh, Ww, 1)
-    assert torch.equal(ob[..., :C], want), "out = x * ca * sa"
+    assert torch.equal(ob[..., :C], R.scale_f32(xb[..., :C], ca, sa, N, Hh, Ww)), "out = x * ca * sa"
     assert torch.isnan(ob[..., C:]).all(), "written outside its channel slice"
 
 
@@ -241,8 +208,8 @@ def test_cbam_apply_past_the_grid_cap():
             want = x[:, y0:y0 + 64] * ca.view(N, 1, 1, C) * sa.view(N, Hh, Ww, 1)[:, y0:y0 + 64]
             assert torch.equal(out[:, y0:y0 + 64], want), f"run {run}, rows {y0}.."
             del want
-    sa_ref, terms = _sa_ref(smap, wsp, N, Hh, Ww)
-    _assert_bound(sa.view(N, Hh, Ww), sa_ref, 0.25 * 100 * EPS * terms + 8 * EPS, "sa")
+    sa_ref, e_sa = R.sa64(smap, wsp, N, Hh, Ww)
+    _assert_bound(sa.view(N, Hh, Ww), sa_ref, e_sa, "sa")
     del x, out, sa, smap
     torch.cuda.empty_cache()
 
@@ -304,11 +271,8 @@ def test_cbam_bwd_a(shape):
         return (out,)
 
     (gsa,) = _twice(run)
-    t = f.gv.double() * f.x.double() * f.ca.double()[:, None, :]
-    s64, a = f.sa.double(), t.sum(2)
-    # two products per term, C / 32 per lane, the quad and the 8-lane tree, then two products: relative to sum |terms|
-    e = ((C / 32 + 10) * EPS * t.abs().sum(2)) * s64 * (1 - s64) + 3 * EPS * (a * s64 * (1 - s64)).abs()
-    _assert_bound(gsa, a * s64 * (1 - s64), e, "gsa_pre")
+    ref, e = R.bwd_a64(f.gv, f.x, f.ca, f.sa)
+    _assert_bound(gsa, ref, e, "gsa_pre")
 
 
 BWD_B_SHAPES = [(3, 37, 53), (2, 1, 5), (3, 4, 2), (1, 7, 7), (2, 40, 33), (1, 1, 1)]
@@ -335,15 +299,9 @@ def test_cbam_bwd_b_transposed_conv_and_weight_gradient(shape):
         return gsmap, dw, dwa
 
     gsmap, dw, dwa = _twice(run)
-    s = smap.view(N, Hh, Ww, 2).permute(0, 3, 1, 2).double().requires_grad_(True)
-    w = wsp.double().view(1, 2, 7, 7).requires_grad_(True)
-    F.conv2d(s, w, padding=3).backward(gsa.double().view(N, 1, Hh, Ww))
-    # gsmap: up to 49 products in one fp32 chain; relative to the sum of |terms|
-    ta = F.conv_transpose2d(gsa.double().abs().view(N, 1, Hh, Ww), w.detach().abs(), padding=3)
-    _assert_bound(gsmap.view(N, Hh, Ww, 2), s.grad.permute(0, 2, 3, 1), 52 * EPS * ta.permute(0, 2, 3, 1), "gsmap")
-    # d-wsp: the product, a 64-lane tree, four waves, fp64 over the blocks: 10 roundings of the sum of |terms|
-    tw = torch.nn.grad.conv2d_weight(s.detach().abs(), (1, 2, 7, 7), gsa.double().abs().view(N, 1, Hh, Ww), padding=3)
-    _assert_bound(dw, w.grad.flatten(), 12 * EPS * tw.flatten(), "d-wsp")
+    gs_ref, e_gs, dw_ref, e_dw = R.bwd_b64(gsa, smap, wsp, N, Hh, Ww)
+    _assert_bound(gsmap.view(N, Hh, Ww, 2), gs_ref, e_gs, "gsmap")
+    _assert_bound(dw, dw_ref, e_dw, "d-wsp")
     assert torch.equal(dwa, dw0 + dw), "accumulate=1 adds the fp32 result"
 
 
@@ -360,13 +318,8 @@ def test_cbam_bwd_c(shape):
         return (part,)
 
     (part,) = _twice(run)
-    onehot = F.one_hot(f.cidx.long(), C).double()
-    gm, gx = gsmap[..., 0:1].double(), gsmap[..., 1:2].double()
-    gx1 = f.gv.double() * f.sa.double()[..., None] + gm / C + gx * onehot
-    t = gx1 * f.x.double()
-    ta = (f.gv.double() * f.sa.double()[..., None]).abs() + gm.abs() / C + gx.abs() * onehot
-    # gx1 takes 3 roundings, the product 1; per thread <= 512 / R pixels, then R rows: <= 513 + 4 deep
-    _assert_bound(part.double().sum(1), t.sum(1), 520 * EPS * (ta * f.x.double().abs()).sum(1), "gca")
+    ref, e = R.bwd_c64(f.gv, f.x, f.sa, gsmap, f.cidx)
+    _assert_bound(part.double().sum(1), ref, e, "gca")
 
 
 @pytest.mark.parametrize("N", [1, 5])
@@ -393,23 +346,7 @@ def test_cbam_bwd_d_mlp_gradients(N, C):
     _, dw1a, dw2a = run(1)
     assert torch.equal(dw1a, dw10 + dw1) and torch.equal(dw2a, dw20 + dw2), "accumulate=1"
 
-    def ref(sign):
-        """sign = identity: the gradients; abs: the same sums over |terms| (the error scale)"""
-        p = sign(f.pooled.double()).requires_grad_(True)
-        W1 = sign(f.w1.double()).requires_grad_(True)
-        W2 = sign(f.w2.double()).requires_grad_(True)
-        a = f.ca.double()
-        gpre = sign(gcap.double().sum(1) * a * (1 - a))
-        mask = (f.hidden > 0).double()
-        h = (p @ W1.t()) * mask
-        ((h[:, 0] + h[:, 1]) @ W2.t() * gpre).sum().backward()
-        return p.grad, W1.grad, W2.grad
-
-    gp, g1, g2 = ref(lambda t: t)
-    tp, t1, t2 = ref(torch.abs)
-    # gpre: fp64 over the partials, then two products; the hidden gradient: C / 64 products per lane and a 64-lane tree;
-    # gpool: Ch products; the weight gradients: N products per element
-    k = (C / 64 + 2 * Ch + 2 * N + 16) * EPS
+    (gp, g1, g2), (tp, t1, t2), k = R.bwd_d64(gcap, f.ca, f.pooled, f.hidden, f.w1, f.w2)
     _assert_bound(gpool, gp, k * tp, "gpool")
     _assert_bound(dw1, g1, k * t1, "d-W1")
     _assert_bound(dw2, g2, k * t2, "d-W2")
@@ -432,18 +369,8 @@ def test_cbam_bwd_e_gradient_lands_on_the_first_index(shape):
         return (gx,)
 
     (gx,) = _twice(run)
-    onehot_c = F.one_hot(f.cidx.long(), C).double()                                        # [N, HW, C]
-    onehot_p = F.one_hot(f.amax.long(), HW).double().permute(0, 2, 1)                       # [N, HW, C]
-    gm, gxs = gsmap[..., 0:1].double(), gsmap[..., 1:2].double()
-    a = f.ca.double()[:, None, :]
-    gx1 = f.gv.double() * f.sa.double()[..., None] + gm / C + gxs * onehot_c
-    gavg, gmax = gpool[:, 0].double()[:, None, :], gpool[:, 1].double()[:, None, :]
-    want = gx1 * a + gavg / HW + gmax * onehot_p
-    terms = ((f.gv.double() * f.sa.double()[..., None]).abs() + gm.abs() / C + gxs.abs() * onehot_c) * a + \
-        gavg.abs() / HW + gmax.abs() * onehot_p
-    # gx1 three roundings, the product by ca and the two sums: 8 EPS of the terms (a misplaced max gradient is a whole
-    # term of up to 8 sqrt(HW) off)
-    _assert_bound(gx[..., :C], want, 8 * EPS * terms, "gx")
+    want, e = R.bwd_e64(f.gv, f.ca, f.sa, gsmap, f.cidx, gpool, f.amax)
+    _assert_bound(gx[..., :C], want, e, "gx")
     assert torch.isnan(gx[..., C:]).all(), "written outside its channel slice"
 
 

@@ -10,7 +10,6 @@ exactly, on inputs whose decision is exact in fp32 (integer boxes) or stands a c
 (tests/_cases.py, asserted without a GPU in tests/test_ref64_cpu.py).  Value tolerances are in EPS = 2^-24 relative to the
 sum of |terms| added, each with the fp32 operations it counts."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
@@ -22,10 +21,7 @@ from tests import _ref64 as R64
 from tests._util import DEV, EPS, _assert_bound, _idx, _nan, _pad_untouched, _padded, _same_bits, _twice
 
 pytestmark = pytest.mark.gpu
-# expf of the box decodes (rpn_decode_kernel, box_postprocess_kernel), in EPS relative to its result: measured 1, bound 4
-# (the tests print "expf units needed": at most 0.57 beyond the plain roundings in the RPN decode, nothing beyond them in
-# the box head, scores or boxes)
-EXP_UNITS = 4
+# (the bounds, and EXP_UNITS for expf, are tests/_ref64.py's: the host-emulation run of csrc/detect.hip shares them)
 
 
 def _gen(seed):
@@ -126,11 +122,8 @@ def test_rpn_decode(N, Hh, Ww, A, cpad, rpad, sh, sw):
     assert _same_bits(logits, cls[..., :A].reshape(N, tot)), "logits are copied"
     anchors = R64.rpn_anchors(Hh, Ww, base, sh, sw)                      # [tot, 4]
     ref, mag, pwh = R64.decode_clip(d.view(N, tot, 4), anchors[None], (1.0, 1.0, 1.0, 1.0), img_h, img_w)
-    # anchor width / centre are exact (small integers and halves).  pcx = d w + cx: two roundings (one with FMA) of
-    # |d w| + |pcx|; pw = expf(dw) w: expf and a product; the clamp constant log(1000 / 16) is fp32: half an ulp of 4.1 is
-    # 4 EPS on the exponent, so 4 EPS of pw; pcx -+ pw / 2: one more rounding, of the result
-    plain = EPS * 2 * mag
-    _assert_bound(boxes, ref, plain + (EXP_UNITS + 6) * EPS * 0.5 * pwh, "rpn boxes")
+    plain, bound = R64.rpn_decode_bounds(mag, pwh)
+    _assert_bound(boxes, ref, bound, "rpn boxes")
     need = (((boxes.double() - ref).abs() - plain) / (EPS * 0.5 * pwh)).max()
     print(f"[measure] rpn_decode: expf units needed beyond the plain roundings: {float(need):.2f}")
     zero = (pos % 8 == 1).repeat_interleave(A)
@@ -308,15 +301,8 @@ def test_roi_align_fpn(nlevels, C_, pad):
             continue
         r = rois[idx]
         v, mag = R64.roi_align(feats[l][..., :C_], r, sc)
-        # per sample: hy = 1 - ly, the weight product, four products with the values and three sums (6 EPS of the sum of
-        # |weight * value|); four samples added (3) and the exact scale by 0.25; 12 with margin for the order.
-        # Sample coordinate: x2 s - x1 s, / 7, ph * bin, (i + .5) * bin / 2 and two sums: 6 roundings of at most
-        # |start| + extent; a coordinate error d moves a bilinear sample by at most d * 2 max|value| per axis.
-        rd = r.double()
-        ext = (rd[:, 1:3].abs().amax(1) + (rd[:, 3:5] - rd[:, 1:3]).abs().amax(1)) * sc + 1.0
-        vmax = feats[l][..., :C_].abs().max().double()
         ref[idx] = v
-        bound[idx] = 12 * EPS * mag + (6 * EPS * ext * 4 * vmax).view(-1, 1, 1, 1)
+        bound[idx] = R64.roi_align_bound(r, mag, sc, feats[l][..., :C_].abs().max().double())
     _assert_bound(out, ref.flatten(1), bound.flatten(1), f"roi_align nlevels={nlevels} C={C_}")
     assert (out[5:7] == 0).all(), "RoIs fully outside the feature map pool to exactly 0"
     assert float(out[7:9].abs().max()) > 0
@@ -383,17 +369,9 @@ def test_box_postprocess(NC, R):
         return boxes.view(R, NC - 1, 4), scores.view(R, NC - 1), valid.view(R, NC - 1)
     boxes, scores, valid = _twice(run)
     rb, rs, rv, mag, pwh = R64.box_postprocess(logits[:, :NC], deltas[:, :4 * NC].view(R, NC, 4), props, hw, img, thresh, K.BOXPOST_MIN_SIZE)
-    # score = expf(l - m) / sum: l - m rounds once (EPS |l - m| on the exponent), expf, the NC-term sum of expf values
-    # (each its own expf error, ceil(NC / 64) serial additions per lane and a 6-level tree), one division
-    lg = logits[:, :NC].double()
-    dist = (lg.amax(1, keepdim=True) - lg)[:, 1:]
-    # (its own exponent roundings weigh in by the softmax-weighted mean of |l - m| <= ln NC)
-    plain_s = (dist + -(-NC // 64) + 8 + math.log(NC)) * EPS * rs + 1e-37
-    _assert_bound(scores, rs, plain_s + 2 * EXP_UNITS * EPS * rs, f"scores NC={NC}")
-    # box: d / 10 and d / 5 round once each (the latter moves expf by EPS |dw| <= 4.2 EPS), then as in the RPN decode
-    # (product 1, fp32 clamp constant 4): 10 EPS of pw / 2 besides expf
-    plain_b = EPS * 3 * mag
-    _assert_bound(boxes, rb, plain_b + (EXP_UNITS + 10) * EPS * 0.5 * pwh, f"boxes NC={NC}")
+    plain_s, e_s, plain_b, e_b = R64.box_postprocess_bounds(logits[:, :NC], rs, mag, pwh)
+    _assert_bound(scores, rs, e_s, f"scores NC={NC}")
+    _assert_bound(boxes, rb, e_b, f"boxes NC={NC}")
     need_s = (((scores.double() - rs).abs() - plain_s) / (2 * EPS * rs)).max()
     need_b = (((boxes.double() - rb).abs() - plain_b - 10 * EPS * 0.5 * pwh) / (EPS * 0.5 * pwh)).max()
     print(f"[measure] box_postprocess NC={NC}: expf units needed, scores {float(need_s):.2f}, boxes {float(need_b):.2f}")

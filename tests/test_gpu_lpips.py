@@ -137,28 +137,8 @@ LAYER_CASES = [(c, hw, n) for c in LAYER_C for hw in LAYER_HW_SMALL for n in (1,
 def _features(N, HW, C_, seed):
     """post-ReLU-like features: |randn| with ~30 % zeros; by pixel index (p + n) % 7: 1 -> fa all zero, 2 -> fb all zero,
     3 -> both all zero, 4 -> fa == fb, 5 -> one channel of fa dominant by 1e4."""
-    def base(s):
-        return _randn(N, HW, C_, seed=s).abs() * (_rand(N, HW, C_, seed=s + 1) > 0.3)
-    fa, fb = base(seed), base(seed + 2)
-    fam = (torch.arange(HW, device=DEV)[None, :] + torch.arange(N, device=DEV)[:, None]) % 7
-    fa[(fam == 1) | (fam == 3)] = 0.0
-    fb[(fam == 2) | (fam == 3)] = 0.0
-    fb[fam == 4] = fa[fam == 4]
-    dom = fa[..., C_ // 2]
-    dom[fam == 5] = 1e4
-    w = _rand(C_, seed=seed + 4)
-    return fa.contiguous(), fb.contiguous(), w, fam
-
-
-def _lane_terms(C_):
-    """roundings of a C-channel sum as the kernels do it: four products summed pairwise per quad (3), C / 32 quads added
-    serially per lane, a 3-level tree over the 8 lanes of the pixel group."""
-    return -(-C_ // 32) + 6
-
-
-def _norm_terms(C_):
-    """relative error of 1 / (sqrt(sum a^2) + 1e-10) in EPS: half the sum's, sqrtf, the fp32 constant and sum, the reciprocal."""
-    return _lane_terms(C_) / 2 + 3
+    return R64.lpips_features(N, HW, C_, lambda k, *shape: _randn(*shape, seed=seed + k),
+                              lambda k, *shape: _rand(*shape, seed=seed + k))
 
 
 @pytest.mark.parametrize("C_,HW,N", LAYER_CASES)
@@ -174,20 +154,8 @@ def test_lpips_layer_forward_and_rows_sum(C_, HW, N):
         assert _pad_untouched(wp, N * nblk)
         return (part.view(N, nblk),)
     part, = _twice(run)
-    a, b, w64 = fa.double(), fb.double(), w.double()
-    na = a / (a.pow(2).sum(-1, keepdim=True).sqrt() + 1e-10)
-    nb = b / (b.pow(2).sum(-1, keepdim=True).sqrt() + 1e-10)
-    dpix = R64.lpips_pixel(fa, fb, w)                                                   # [N, HW]
-    # per pixel: na and nb carry (norm + 1) EPS each, their difference one more; w df^2 doubles df's error and adds two
-    # products; the channel sum of the terms: _lane_terms
-    kin = _norm_terms(C_)
-    e_df = EPS * ((kin + 1) * (na.abs() + nb.abs()) + (na - nb).abs())
-    # (w e_df^2 is the second-order term: it is all there is where na == nb)
-    e_pix = (w64 * (2 * (na - nb).abs() * e_df + e_df ** 2)).sum(-1) + (_lane_terms(C_) + 2) * EPS * dpix
-    # per block: 32 pixels added serially per thread, a 6-level wave tree, two more sums
-    pad = nblk * LP_PPB - HW
-    blk = lambda t: torch.nn.functional.pad(t, (0, pad)).view(N, nblk, LP_PPB).sum(-1)
-    _assert_bound(part, blk(dpix), blk(e_pix) + 40 * EPS * blk(dpix), f"layer partials C={C_} HW={HW}")
+    dpix, blk_ref, blk_bound = R64.lpips_layer_blocks(fa, fb, w, LP_PPB)
+    _assert_bound(part, blk_ref, blk_bound, f"layer partials C={C_} HW={HW}")
     # rows_sum: float64 sum of the fp32 partials times the fp32 scale, rounded once; accumulate adds one fp32 sum
     scale = float(np.float32(1.0 / HW))
     prev = _randn(N, seed=9)
@@ -206,7 +174,7 @@ def test_lpips_layer_forward_and_rows_sum(C_, HW, N):
     _assert_bound(o0, v, EPS * v.abs() * (1 + 1e-6), "rows_sum")
     _assert_bound(o1, prev.double() + v, EPS * (v.abs() + (prev.double() + v).abs()) * (1 + 1e-6), "rows_sum accumulate")
     # and end to end against the float64 mean
-    _assert_bound(o0, dpix.mean(1), (blk(e_pix) + 40 * EPS * blk(dpix)).sum(1) / HW + 2 * EPS * dpix.mean(1), "layer mean")
+    _assert_bound(o0, dpix.mean(1), blk_bound.sum(1) / HW + 2 * EPS * dpix.mean(1), "layer mean")
 
 
 @pytest.mark.parametrize("C_,HW,N", LAYER_CASES)
@@ -225,26 +193,7 @@ def test_lpips_layer_backward(C_, HW, N):
         return (gfa.view(N, HW, C_),)
     gfa, = _twice(run)
     ref = R64.lpips_layer_grad(fa, fb, w, g_val)
-    a, b, w64 = fa.double(), fb.double(), w.double()
-    r = a.pow(2).sum(-1, keepdim=True).sqrt()
-    s = r + 1e-10
-    na, nb = a / s, b / (b.pow(2).sum(-1, keepdim=True).sqrt() + 1e-10)
-    kin, kl = _norm_terms(C_), _lane_terms(C_)
-    gk = (g_val.double() / HW).view(-1, 1, 1)
-    # delta = w (na - nb) (2 gk): the difference as in the forward, gk = g / HW (1), three products
-    e_df = EPS * ((kin + 1) * (na.abs() + nb.abs()) + (na - nb).abs())
-    dl = 2 * w64 * (na - nb) * gk
-    e_dl = 2 * (w64 * gk).abs() * e_df + 4 * EPS * dl.abs()
-    # dot = sum delta a: the terms' own errors, one product each and the channel sum
-    dota = (dl * a).abs().sum(-1, keepdim=True)
-    e_dot = (a.abs() * e_dl).sum(-1, keepdim=True) + (kl + 1) * EPS * dota
-    # k2 = dot / (r s s): sqrtf's and the sum's error three times over, two products, one division
-    den = (r * s * s).clamp_min(1e-300)
-    pos = r > 0
-    e_k2 = torch.where(pos, (e_dot + (3 * kin + 3) * EPS * dota) / den, torch.zeros_like(r))
-    k2 = torch.where(pos, (dl * a).sum(-1, keepdim=True) / den, torch.zeros_like(r))
-    # out = delta / s - a k2: 1 / s carries kin, two products, one difference
-    bound = e_dl / s + (kin + 1) * EPS * (dl / s).abs() + a.abs() * e_k2 + 2 * EPS * (a * k2).abs() + EPS * ref.abs()
+    bound = R64.lpips_layer_grad_bound(fa, fb, w, g_val, ref)
     _assert_bound(gfa, ref, bound, f"layer backward C={C_} HW={HW}")
     same = (fam == 4)
     assert (gfa[same] == 0).all(), "fa == fb: the gradient is exactly 0"

@@ -2,9 +2,10 @@
 tools/host_emu (its ADH_HOST_EMU section) with AddressSanitizer and UndefinedBehaviorSanitizer, run as a stand-alone program
 on heap buffers of exactly their sizes and held to the float64 reference and the bound of tests/_wgrad_reduce_ref.py -- the
 ones tests/test_gpu_wgrad_reduce.py holds the library to.  It runs the index decode, the split sums, the inverse transforms
-and the layout scatter (negative tap strides included) of the very source the GPU runs under the sanitizers.  The
-one-wave-per-element kernel (adh_wgrad_reduce_small) needs cross-lane shuffles and is covered on the GPU only; the class taps
-of the wino32 form, which conv_wgrad32.hip derives from a descriptor, are given by the case."""
+and the layout scatter (negative tap strides included) of the very source the GPU runs under the sanitizers.  The class taps
+of the wino32 form, which conv_wgrad32.hip derives from a descriptor, are given by the case.  The one-wave-per-element kernel
+(adh_wgrad_reduce_small: csrc/wave.h's wave_sum on the emulator's __shfl_xor) runs in a second program of the same source, on
+the streaming runtime (tools/host_emu/stream_rt.cpp, wgrad_reduce_small_main.cpp; tests/_hostemu.py)."""
 import os
 import shutil
 import subprocess
@@ -12,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import _hostemu as E
 from tests import _wgrad_reduce_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -67,6 +69,52 @@ def _run_case(emu, cs, nsplit, accumulate, seed):
 def test_direct_reduce_reversed_taps(emu, K, Nc, accumulate):
     for KH, nsplit in ((1, 1), (2, 5), (3, 1), (4, 5)):
         _run_case(emu, R.case("adh_wgrad_reduce", K, Nc, KH, reverse=True), nsplit, accumulate, seed=10 + KH)
+
+
+@pytest.fixture(scope="module")
+def small_emu(tmp_path_factory):
+    d = tmp_path_factory.mktemp("wgrad_reduce_small_emu")
+    exe = E.build(d, "conv_wgrad_reduce", "wgrad_reduce_small_main.cpp")
+    return lambda: E.Script(exe, d)
+
+
+def _small_call(s, slab, dst0, nslabs, L, accumulate, null_slab=False):
+    dst = s.out(dst0.size, init=dst0)
+    s.call(0, [nslabs, slab.shape[-2], slab.shape[-1], accumulate] + list(L), [None if null_slab else s.vec(slab), dst])
+    return dst
+
+
+@pytest.mark.parametrize("accumulate", [0, 1])
+@pytest.mark.parametrize("nslabs", [1, 63, 64, 65, 200])
+def test_wave_reduce(small_emu, nslabs, accumulate):
+    """adh_wgrad_reduce_small, one wave per element: fewer slabs than lanes, one short of a wave, exactly one, one more, three
+    trips and a partial fourth.  3 x 3 taps with K = 3, Nc = 16 (432 elements: 108 workgroups of four waves, reversed taps) and
+    7 x 7 taps with K = 3, Nc = 5 (735 elements: the last workgroup has one idle wave).  The bound is the tap-domain one of the
+    sibling kernels, (nslabs + c) EPS of the sum of |terms|, with c = 6 for the six additions of the 64-lane tree.  The slabs
+    are padded to KP = 4 rows and NcP = 20 / 8 columns (random in the padding too), not to the 32 x 32 of the other cases: 200
+    of those would be 40 MB a case.  Each case runs twice and must give the same bits."""
+    s = small_emu()
+    todo = []
+    for cs, seed, ncp in ((R.case("adh_wgrad_reduce_small", 3, 16, 3, reverse=True), 60 + nslabs, 20),
+                          (R.case("adh_wgrad_reduce_small", 3, 5, 7), 61 + nslabs, 8)):
+        slab, dst0 = R.rng_slab(seed, nslabs, 1, cs.M.shape[1], 4, ncp), R.rng_dst(seed, cs.ndst, accumulate)
+        todo.append((cs, slab, dst0, [_small_call(s, slab, dst0, nslabs, cs.L, accumulate) for _ in range(2)]))
+    rcs = s.run()
+    assert rcs == [0] * 4, rcs
+    for cs, slab, dst0, (d1, d2) in todo:
+        assert (s.after[d1] == s.after[d2]).all(), "two identical calls differ"
+        ref, bound, written = R.reference(slab, cs.M, cs.c + 6, cs.L, cs.taps, dst0, accumulate)
+        R.check(s.get(d1).numpy(), dst0, ref, bound, written, f"small taps={cs.L.KHt} nslabs={nslabs} acc={accumulate}")
+
+
+def test_wave_reduce_rejections_leave_dst_unwritten(small_emu):
+    s = small_emu()
+    cs = R.case("adh_wgrad_reduce_small", 3, 16, 3)
+    slab, nan = cs.slab(50, 1), R.rng_dst(0, cs.ndst, 0)
+    bad = [_small_call(s, slab, nan, 1, cs.L, 0, null_slab=True), _small_call(s, slab, nan, 0, cs.L, 0)]
+    assert s.run() == [ADH_E_ARG] * 2
+    for dst in bad:
+        assert s.unchanged(dst)
 
 
 @pytest.mark.parametrize("accumulate", [0, 1])

@@ -3,16 +3,18 @@
 // GPU thread, a pthread barrier for __syncthreads(), the workgroups of a launch one after the other.  The point is to run the
 // kernel's own index arithmetic under the host sanitizers (-fsanitize=address,undefined) and against float64 without a GPU;
 // it says nothing about speed.  Used by tests/test_ssim_loss_hostemu_cpu.py on a copy of csrc/ssim_loss.hip and, with
-// -DADH_HOST_EMU (the section at the end), by tests/test_wgrad_reduce_hostemu_cpu.py on a copy of csrc/conv_wgrad_reduce.hip and
-// by tests/test_ema_hostemu_cpu.py on a copy of csrc/ema.hip; with -DADH_HOST_EMU_DYN_LDS on top (the last section), by
-// tests/test_fft_loss_hostemu_cpu.py on a copy of csrc/fft_loss.hip; with -DADH_HOST_EMU_STREAM on top of ADH_HOST_EMU (the section
-// after it), by tests/test_{bn_act,depthwise,densenet,image_io}_hostemu_cpu.py on copies of the four streaming kernel files and by
-// tests/test_ciede2000_hostemu_cpu.py on a copy of csrc/ciede2000.hip (which reduces through LDS and barriers: no shuffle).
+// -DADH_HOST_EMU (the section at the end), by tests/test_ema_hostemu_cpu.py on a copy of csrc/ema.hip; with
+// -DADH_HOST_EMU_DYN_LDS on top, by tests/test_fft_loss_hostemu_cpu.py on a copy of csrc/fft_loss.hip; with
+// -DADH_HOST_EMU_STREAM on top of ADH_HOST_EMU (the last section; the cross-lane shuffle and the wave reductions are ADH_HOST_EMU's), by
+// tests/test_{bn_act,depthwise,densenet,image_io,d4,ciede2000}_hostemu_cpu.py, by tests/test_{cbam,lpips,detect}_hostemu_cpu.py and
+// tests/test_wgrad_reduce_hostemu_cpu.py on copies of their kernel files, and by tests/test_hostemu_shuffle_cpu.py on the
+// shuffle itself.
 #pragma once
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <pthread.h>
 #include <thread>
@@ -41,8 +43,9 @@ void emu_launch(dim3 grid, dim3 block, std::function<void()> fn);
 #ifdef ADH_HOST_EMU
 // What csrc/conv_wgrad_reduce.hip takes from csrc/common.h beyond the above: the public structs, the grid-stride loop's
 // blockDim, float4 arithmetic, and the helpers and internal declarations it shares with the other source files (copies of
-// csrc/common.h's: keep them the same).  Its one-wave-per-element kernel needs cross-lane shuffles and is compiled out.
+// csrc/common.h's: keep them the same), and for its one-wave-per-element kernel the cross-lane shuffle and csrc/wave.h.
 #include "adam_dehaze_hip.h"   // include/, on the include path
+#include <atomic>
 #define __host__
 #define __device__
 #define __forceinline__ inline
@@ -64,13 +67,53 @@ struct adh_wg32_taps {
 };
 int adh_wgrad32_class_taps(const adh_conv_desc* d, adh_wg32_taps* tp);
 #define ADH_ADAM_CHUNK 16384   // csrc/ema.hip: floats per workgroup (csrc/common.h's)
+// __shfl_xor(v, mask, 64): lanes t and u = t ^ mask exchange 32 bits through the channel the pair owns, emu_chan[t][mask] and
+// emu_chan[u][mask], and wait for nobody else, so a pair may shuffle inside a loop the rest of its workgroup has already left
+// (bn_apply_kernel), and the waves of a workgroup may shuffle different numbers of times (cbam_mlp_kernel).  A channel counts
+// the shuffles its lane has made with THIS partner, so the n-th shuffle of t with u meets the n-th shuffle of u with t whatever
+// either lane has exchanged with third lanes in between -- a butterfly changes partners every step.  For its n-th shuffle
+// with u, t writes slot n & 1 of its channel, publishes n + 1, waits until u's channel has published n + 1 and reads u's slot
+// n & 1.  Two slots are enough: t overwrites slot n & 1 in its shuffle n + 2 with u, after it finished n + 1, that is after u
+// published n + 2, which u does only after it has read t's slot of shuffle n (release / acquire on `seq` orders the plain
+// accesses).  The counters run on over the workgroups of a launch; stream_rt.cpp clears them before the next one, and under a
+// launcher that does not (wgrad_reduce_main.cpp) they run on over the launches too, which pairs as well.  A lane whose partner
+// has left the kernel waits for ever: the tests run every driver under a timeout.  mask is 1..63 and the partner must be a
+// lane of the workgroup; the value travels bit for bit (a NaN payload, -0.0f).
+struct emu_channel {
+    std::atomic<unsigned> seq;
+    uint32_t val[2];
+};
+inline emu_channel emu_chan[1024][64];       // (an inline variable: no driver has to define it)
+static inline uint32_t emu_shfl_bits(uint32_t v, int mask) {
+    if (mask == 0) return v;
+    const unsigned u = threadIdx.x ^ (unsigned)mask;
+    if (mask < 0 || mask > 63 || u >= blockDim.x) {
+        fprintf(stderr, "__shfl_xor: lane %u, mask %d: no such partner in a workgroup of %u\n", threadIdx.x, mask, blockDim.x);
+        abort();
+    }
+    emu_channel& mine = emu_chan[threadIdx.x][mask];
+    emu_channel& theirs = emu_chan[u][mask];
+    const unsigned n = mine.seq.load(std::memory_order_relaxed);
+    mine.val[n & 1] = v;
+    mine.seq.store(n + 1, std::memory_order_release);
+    while (theirs.seq.load(std::memory_order_acquire) < n + 1) std::this_thread::yield();
+    return theirs.val[n & 1];
+}
+static inline int __shfl_xor(int v, int mask, int) { return (int)emu_shfl_bits((uint32_t)v, mask); }
+static inline unsigned __shfl_xor(unsigned v, int mask, int) { return emu_shfl_bits(v, mask); }
+static inline float __shfl_xor(float v, int mask, int) {
+    uint32_t b;
+    memcpy(&b, &v, 4);
+    b = emu_shfl_bits(b, mask);
+    memcpy(&v, &b, 4);
+    return v;
+}
+#include "../adam-dehaze_amd/csrc/wave.h"
 #endif
 
-#ifdef ADH_HOST_EMU_DYN_LDS
-// What csrc/fft_loss.hip takes beyond the ADH_HOST_EMU section (tests/test_fft_loss_hostemu_cpu.py defines both): dynamic LDS,
-// which every launch gets as a heap block of exactly the bytes it asked for, so that an LDS index out of range is the
-// sanitizer's to report as well; the attribute call that lifts the 64 KiB limit on the device; bit reversal; and sincospif,
-// here the float64 functions rounded once.
+#if defined(ADH_HOST_EMU_DYN_LDS) || defined(ADH_HOST_EMU_STREAM)
+// Dynamic LDS (csrc/fft_loss.hip; in the stream section cbam_mlp_kernel, cbam_bwd_d2_kernel and nms_scan_kernel): every launch
+// gets a heap block of exactly the bytes it asked for, so that an LDS index out of range is the sanitizer's to report as well.
 extern void* emu_dyn_lds;
 #define ADH_DYN_LDS(T, name) T* name = (T*)emu_dyn_lds
 #undef hipLaunchKernelGGL
@@ -80,6 +123,12 @@ extern void* emu_dyn_lds;
         emu_launch(grid, block, [&]() { k(__VA_ARGS__); });        \
         free(emu_dyn_lds);                                         \
     } while (0)
+#endif
+
+#ifdef ADH_HOST_EMU_DYN_LDS
+// What csrc/fft_loss.hip takes beyond the ADH_HOST_EMU section and dynamic LDS (tests/test_fft_loss_hostemu_cpu.py defines
+// both): the attribute call that lifts the 64 KiB limit on the device; bit reversal; and sincospif, here the float64 functions
+// rounded once.
 #define hipFuncAttributeMaxDynamicSharedMemorySize 0
 static inline int hipFuncSetAttribute(const void*, int, int) { return 0; }
 static inline unsigned __brev(unsigned v) {
@@ -99,31 +148,11 @@ static inline void sincospif(float x, float* s, float* c) {
 // stream_rt.cpp, whose emu_launch walks grid.x, grid.y and grid.z.  The non-temporal builtins are plain loads and stores.  The
 // activation helpers and the shared BatchNorm pieces are csrc/bn_stream.h itself, included at the end of this section as
 // csrc/common.h includes it at its end (the path is found from include/, which every build of this file has on its include path).
-#include <atomic>
 #define __builtin_nontemporal_load(p) (*(p))
 #define __builtin_nontemporal_store(v, p) (*(p) = (v))
 static inline int adh_max_i(int a, int b) { return a > b ? a : b; }
 #define __builtin_amdgcn_readfirstlane(v) (v)   // csrc/d4.hip: a value its caller knows to be wave-uniform
 static inline float __fmul_rn(float a, float b) { return a * b; }   // csrc/image_io.hip: a product nothing is contracted into
-// __shfl_xor(v, mask, 64): lanes t and t ^ mask exchange through one mailbox per lane and wait for nobody else, so a pair may
-// shuffle inside a loop the rest of its workgroup has already left (bn_apply_kernel).  A lane's n-th shuffle posts into slot
-// n & 1 and publishes n + 1; its partner cannot post n + 2 before it has read n, so two slots are enough.  A lane whose
-// partner has left the kernel waits for ever: the tests run every driver under a timeout.
-struct emu_mailbox {
-    std::atomic<unsigned> seq;
-    int val[2];
-};
-extern emu_mailbox emu_mail[1024];           // stream_rt.cpp clears them before every launch
-extern thread_local unsigned emu_shfl_count;
-static inline int __shfl_xor(int v, int mask, int width) {
-    (void)width;
-    const unsigned n = emu_shfl_count++;
-    emu_mailbox& mine = emu_mail[threadIdx.x];
-    emu_mailbox& theirs = emu_mail[threadIdx.x ^ (unsigned)mask];
-    mine.val[n & 1] = v;
-    mine.seq.store(n + 1, std::memory_order_release);
-    while (theirs.seq.load(std::memory_order_acquire) < n + 1) std::this_thread::yield();
-    return theirs.val[n & 1];
-}
+static inline int hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { memset(p, v, n); return 0; }   // csrc/detect.hip
 #include "../adam-dehaze_amd/csrc/bn_stream.h"
 #endif

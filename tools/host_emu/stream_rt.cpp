@@ -1,15 +1,15 @@
 // Runtime shared by the streaming drivers (built with -DADH_HOST_EMU -DADH_HOST_EMU_STREAM): the emulator's globals, an
-// emu_launch that walks all three grid dimensions, the shuffle mailboxes, and the script reader of stream_rt.h.
+// emu_launch that walks all three grid dimensions, the shuffle channels, the dynamic-LDS pointer, and the script reader of
+// stream_rt.h.
 #include "common.h"
 #include "stream_rt.h"
 #include <condition_variable>
 #include <cstring>
 #include <mutex>
 thread_local dim3 threadIdx;
-thread_local unsigned emu_shfl_count;
 dim3 blockIdx, gridDim, blockDim;
 pthread_barrier_t emu_barrier;
-emu_mailbox emu_mail[1024];
+void* emu_dyn_lds;
 
 // The lanes are a pool of OS threads kept over the launches of a script (a script makes hundreds of launches, and starting 256
 // threads under the sanitizers costs more than most of these kernels): a launch publishes its job under a new generation
@@ -33,7 +33,6 @@ static void lane_main(unsigned t) {
             if (t >= pool_lanes) continue;
         }
         threadIdx = dim3(t);
-        emu_shfl_count = 0;
         const dim3 grid = gridDim;
         for (unsigned z = 0; z < grid.z; ++z)
             for (unsigned y = 0; y < grid.y; ++y)
@@ -52,7 +51,8 @@ void emu_launch(dim3 grid, dim3 block, std::function<void()> fn) {
     if (block.x < 1 || block.x > 1024 || block.y != 1 || block.z != 1) exit(6);
     gridDim = grid;
     blockDim = block;
-    for (unsigned t = 0; t < block.x; ++t) emu_mail[t].seq.store(0);
+    for (unsigned t = 0; t < block.x; ++t)
+        for (auto& ch : emu_chan[t]) ch.seq.store(0, std::memory_order_relaxed);
     pthread_barrier_init(&emu_barrier, nullptr, block.x);
     std::unique_lock<std::mutex> lk(pool_mu);
     while (pool.size() < block.x) {
@@ -68,7 +68,7 @@ void emu_launch(dim3 grid, dim3 block, std::function<void()> fn) {
     pthread_barrier_destroy(&emu_barrier);
 }
 
-static void pool_shutdown() {
+void emu_shutdown() {
     {
         std::lock_guard<std::mutex> lk(pool_mu);
         pool_quit = true;
@@ -118,7 +118,7 @@ int emu_run_script(int argc, char** argv, int64_t (*dispatch)(const emu_call&)) 
         rc.push_back(dispatch(c));
     }
     fclose(f);
-    pool_shutdown();
+    emu_shutdown();
     f = fopen(argv[2], "wb");
     if (!f || fwrite(rc.data(), 8, rc.size(), f) != rc.size()) return 4;
     for (int64_t k = 0; k < nbuf; ++k) {

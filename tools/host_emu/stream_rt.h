@@ -24,3 +24,6 @@ struct emu_call {
 
 // reads the script, runs `dispatch` on every call in order and writes out.bin; the value of main()
 int emu_run_script(int argc, char** argv, int64_t (*dispatch)(const emu_call&));
+
+// joins the lane threads emu_launch keeps between launches; a driver with a main() of its own calls it before it returns
+void emu_shutdown();
