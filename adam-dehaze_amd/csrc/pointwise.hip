@@ -3,9 +3,36 @@
 // in a fixed order).  Reference lines are cited per kernel (paths under /root/reference).
 #include "common.h"
 
+// Grid caps of the grid-stride loops (workgroups of 256 lanes) and the elements a workgroup of the loss reductions takes.  They
+// are names so that a host build (tools/host_emu) can set them small and run every loop and every multi-block partial row at a
+// few hundred elements; the library is built with these defaults.
+#ifndef RED_ELEMS_PER_BLOCK
 #define RED_ELEMS_PER_BLOCK (256 * 16)
+#endif
+#ifndef PW_MAXBLK_RED
+#define PW_MAXBLK_RED 2048       // adh_reduce_num_blocks
+#endif
+#ifndef PW_MAXBLK_EW
+#define PW_MAXBLK_EW 8192        // one element or pixel per lane and trip: layout, head_blend, loss gradients, add, mul, axpby
+#endif
+#ifndef PW_MAXBLK_SPATIAL
+#define PW_MAXBLK_SPATIAL 4096   // per image (grid.y = N): pools and resize; head_blend_bwd's partial rows; adam_step
+#endif
+#ifndef PW_MAXBLK_IMAGE
+#define PW_MAXBLK_IMAGE 2048     // per image: soft_blend, global_avgpool_bwd
+#endif
+#ifndef PW_MAXBLK_GATHER
+#define PW_MAXBLK_GATHER 1024    // per selected image: gather / scatter
+#endif
 
 extern "C" int adh_version(void) { return 100; }
+
+// Argument checks shared by the entry points (include/adam_dehaze_hip.h states the contract): a base the kernel moves 16 bytes at
+// a time from must be 16-byte aligned, a pixel stride it does so at a multiple of 4 floats and at least C; grid.y and grid.z
+// carry batch sizes, so those stay below 65536.  Every entry point returns ADH_E_ARG before it launches anything.
+static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+static inline bool cs4_ok(int cs, int C) { return cs >= C && (cs & 3) == 0; }
+static inline bool batch_ok(int N) { return N >= 1 && N <= 65535; }
 
 // ------------------------------------------------------------------------------------------------
 // layout
@@ -24,9 +51,9 @@ __global__ void image_to_nhwc8_kernel(const float* __restrict__ img, int64_t HW,
 }
 
 extern "C" int adh_image_to_nhwc8(void* stream, const float* img, int N, int H, int W, float* out) {
-    if (!img || !out || N < 1 || H < 1 || W < 1) return ADH_E_ARG;
+    if (!img || !out || N < 1 || H < 1 || W < 1 || !al16(out)) return ADH_E_ARG;
     const int64_t HW = (int64_t)H * W, total = HW * N;
-    hipLaunchKernelGGL(image_to_nhwc8_kernel, dim3(adh_min_i(adh_ceil_div(total, 256), 8192)), dim3(256), 0,
+    hipLaunchKernelGGL(image_to_nhwc8_kernel, dim3(adh_min_i(adh_ceil_div(total, 256), PW_MAXBLK_EW)), dim3(256), 0,
                        (hipStream_t)stream, img, HW, total, out);
     return adh_check_launch();
 }
@@ -47,9 +74,9 @@ __global__ void image_normalize_kernel(const float* __restrict__ img, int64_t HW
 
 extern "C" int adh_image_normalize_to_nhwc8(void* stream, const float* img, int N, int H, int W, float m0, float m1, float m2,
                                             float is0, float is1, float is2, float* out) {
-    if (!img || !out || N < 1 || H < 1 || W < 1) return ADH_E_ARG;
+    if (!img || !out || N < 1 || H < 1 || W < 1 || !al16(out)) return ADH_E_ARG;
     const int64_t HW = (int64_t)H * W, total = HW * N;
-    hipLaunchKernelGGL(image_normalize_kernel, dim3(adh_min_i(adh_ceil_div(total, 256), 8192)), dim3(256), 0,
+    hipLaunchKernelGGL(image_normalize_kernel, dim3(adh_min_i(adh_ceil_div(total, 256), PW_MAXBLK_EW)), dim3(256), 0,
                        (hipStream_t)stream, img, HW, total, m0, m1, m2, is0, is1, is2, out);
     return adh_check_launch();
 }
@@ -69,9 +96,9 @@ __global__ void image_normalize_bwd_kernel(const float* __restrict__ g, int g_cs
 
 extern "C" int adh_image_normalize_bwd(void* stream, const float* g, int g_cs, int N, int H, int W, float is0, float is1,
                                        float is2, float* g_img) {
-    if (!g || !g_img || N < 1 || g_cs < 3) return ADH_E_ARG;
+    if (!g || !g_img || N < 1 || H < 1 || W < 1 || g_cs < 3) return ADH_E_ARG;
     const int64_t HW = (int64_t)H * W, total = HW * N;
-    hipLaunchKernelGGL(image_normalize_bwd_kernel, dim3(adh_min_i(adh_ceil_div(total, 256), 8192)), dim3(256), 0,
+    hipLaunchKernelGGL(image_normalize_bwd_kernel, dim3(adh_min_i(adh_ceil_div(total, 256), PW_MAXBLK_EW)), dim3(256), 0,
                        (hipStream_t)stream, g, g_cs, HW, total, is0, is1, is2, g_img);
     return adh_check_launch();
 }
@@ -116,7 +143,7 @@ __global__ void nhwc_to_nchw_kernel(const float* __restrict__ src, int src_cs, i
 }
 
 extern "C" int adh_nchw_to_nhwc(void* stream, const float* src, int N, int C, int H, int W, float* dst, int dst_cs) {
-    if (!src || !dst || N < 1 || C < 1 || dst_cs < C) return ADH_E_ARG;
+    if (!src || !dst || !batch_ok(N) || C < 1 || H < 1 || W < 1 || dst_cs < C || adh_ceil_div(C, 32) > 65535) return ADH_E_ARG;
     const int64_t HW = (int64_t)H * W;
     hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(adh_ceil_div(HW, 32), adh_ceil_div(C, 32), N), dim3(256), 0,
                        (hipStream_t)stream, src, C, HW, dst, dst_cs);
@@ -124,7 +151,7 @@ extern "C" int adh_nchw_to_nhwc(void* stream, const float* src, int N, int C, in
 }
 
 extern "C" int adh_nhwc_to_nchw(void* stream, const float* src, int src_cs, int N, int C, int H, int W, float* dst) {
-    if (!src || !dst || N < 1 || C < 1 || src_cs < C) return ADH_E_ARG;
+    if (!src || !dst || !batch_ok(N) || C < 1 || H < 1 || W < 1 || src_cs < C || adh_ceil_div(C, 32) > 65535) return ADH_E_ARG;
     const int64_t HW = (int64_t)H * W;
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(adh_ceil_div(HW, 32), adh_ceil_div(C, 32), N), dim3(256), 0,
                        (hipStream_t)stream, src, src_cs, C, HW, dst);
@@ -166,17 +193,17 @@ __global__ __launch_bounds__(256) void head_blend_kernel(int mode, const float* 
 
 extern "C" int adh_head_blend(void* stream, int mode, const float* x_nchw, const float* r, int r_cs, const float* gd,
                               int gd_cs, const float* alpha, int N, int H, int W, float* out_nchw) {
-    if (!x_nchw || !r || !out_nchw || mode < 0 || mode > 4 || r_cs < 3) return ADH_E_ARG;
+    if (!x_nchw || !r || !out_nchw || mode < 0 || mode > 4 || r_cs < 3 || N < 1 || H < 1 || W < 1) return ADH_E_ARG;
     if ((mode == 2 || mode == 4) && (!gd || gd_cs < 1)) return ADH_E_ARG;
     if (mode == 0 && !alpha) return ADH_E_ARG;
     const int64_t HW = (int64_t)H * W, total = HW * N;
-    hipLaunchKernelGGL(head_blend_kernel, dim3(adh_min_i(adh_ceil_div(total, 256), 8192)), dim3(256), 0,
+    hipLaunchKernelGGL(head_blend_kernel, dim3(adh_min_i(adh_ceil_div(total, 256), PW_MAXBLK_EW)), dim3(256), 0,
                        (hipStream_t)stream, mode, x_nchw, r, r_cs, gd, gd_cs, alpha, HW, total, out_nchw);
     return adh_check_launch();
 }
 
 extern "C" int adh_head_blend_bwd_num_blocks(int N, int H, int W) {
-    return adh_min_i(adh_ceil_div((int64_t)N * H * W, 256), 4096);
+    return adh_min_i(adh_ceil_div((int64_t)N * H * W, 256), PW_MAXBLK_SPATIAL);
 }
 
 __global__ __launch_bounds__(256) void head_blend_bwd_kernel(int mode, const float* __restrict__ g,
@@ -241,7 +268,7 @@ __global__ __launch_bounds__(256) void head_blend_bwd_kernel(int mode, const flo
 extern "C" int adh_head_blend_bwd(void* stream, int mode, const float* g_out_nchw, const float* x_nchw, const float* r,
                                   int r_cs, const float* gd, int gd_cs, const float* alpha, int N, int H, int W, float* g_r,
                                   float* g_gd, float* galpha_partial, int nblk) {
-    if (!g_out_nchw || !x_nchw || !r || !g_r || mode < 0 || mode > 4 || r_cs < 3) return ADH_E_ARG;
+    if (!g_out_nchw || !x_nchw || !r || !g_r || mode < 0 || mode > 4 || r_cs < 3 || N < 1 || H < 1 || W < 1) return ADH_E_ARG;
     if ((mode == 2 || mode == 4) && (!gd || !g_gd || gd_cs < 1)) return ADH_E_ARG;
     if (mode == 0 && (!alpha || !galpha_partial)) return ADH_E_ARG;
     if (nblk != adh_head_blend_bwd_num_blocks(N, H, W)) return ADH_E_ARG;
@@ -324,14 +351,15 @@ __global__ __launch_bounds__(256) void soft_blend_scalar_kernel(const float* __r
 
 extern "C" int adh_soft_blend(void* stream, const float* weights, const float* o0, const float* o1, const float* o2, int N,
                               int64_t per, float* out) {
-    if (!weights || !o0 || !o1 || !o2 || !out || N < 1 || per < 1) return ADH_E_ARG;
+    if (!weights || !o0 || !o1 || !o2 || !out || !batch_ok(N) || per < 1) return ADH_E_ARG;
+    if (!(per & 3) && !(al16(o0) && al16(o1) && al16(o2) && al16(out))) return ADH_E_ARG;
     if (per & 3) {
-        hipLaunchKernelGGL(soft_blend_scalar_kernel, dim3(adh_min_i(adh_ceil_div(per, 256), 2048), N), dim3(256), 0,
+        hipLaunchKernelGGL(soft_blend_scalar_kernel, dim3(adh_min_i(adh_ceil_div(per, 256), PW_MAXBLK_IMAGE), N), dim3(256), 0,
                            (hipStream_t)stream, weights, o0, o1, o2, per, out);
         return adh_check_launch();
     }
     const int64_t per4 = per / 4;
-    hipLaunchKernelGGL(soft_blend_kernel, dim3(adh_min_i(adh_ceil_div(per4, 256), 2048), N), dim3(256), 0,
+    hipLaunchKernelGGL(soft_blend_kernel, dim3(adh_min_i(adh_ceil_div(per4, 256), PW_MAXBLK_IMAGE), N), dim3(256), 0,
                        (hipStream_t)stream, weights, o0, o1, o2, per4, out);
     return adh_check_launch();
 }
@@ -377,7 +405,9 @@ __global__ __launch_bounds__(256) void soft_blend_bwd_kernel(const float* __rest
 extern "C" int adh_soft_blend_bwd(void* stream, const float* weights, const float* g, const float* o0, const float* o1,
                                   const float* o2, int N, int64_t per, float* g0, float* g1, float* g2, float* gw_partial,
                                   int nblk) {
-    if (!weights || !g || !o0 || !o1 || !o2 || !gw_partial || N < 1 || per < 4 || (per & 3) || nblk < 1) return ADH_E_ARG;
+    if (!weights || !g || !o0 || !o1 || !o2 || !gw_partial || !batch_ok(N) || per < 4 || (per & 3) || nblk < 1) return ADH_E_ARG;
+    // (a null g0 / g1 / g2 counts as aligned)
+    if (!(al16(g) && al16(o0) && al16(o1) && al16(o2) && al16(g0) && al16(g1) && al16(g2))) return ADH_E_ARG;
     hipLaunchKernelGGL(soft_blend_bwd_kernel, dim3(nblk, N), dim3(256), 0, (hipStream_t)stream, weights, g, o0, o1, o2,
                        per / 4, g0, g1, g2, gw_partial);
     return adh_check_launch();
@@ -438,23 +468,25 @@ __global__ __launch_bounds__(256) void gather_images_scalar_kernel(const float* 
 
 static int gather_images_scalar(void* stream, const float* src, const int32_t* sel, int count, int64_t per, float* dst,
                                 int scatter) {
-    hipLaunchKernelGGL(gather_images_scalar_kernel, dim3(adh_min_i(adh_ceil_div(per, 256), 1024), count), dim3(256), 0,
-                       (hipStream_t)stream, src, sel, per, dst, scatter);
+    hipLaunchKernelGGL(gather_images_scalar_kernel, dim3(adh_min_i(adh_ceil_div(per, 256), PW_MAXBLK_GATHER), count), dim3(256),
+                       0, (hipStream_t)stream, src, sel, per, dst, scatter);
     return adh_check_launch();
 }
 
 extern "C" int adh_gather_images(void* stream, const float* src, const int32_t* sel, int count, int64_t per, float* dst) {
-    if (!src || !sel || !dst || count < 1 || per < 1) return ADH_E_ARG;
+    if (!src || !sel || !dst || !batch_ok(count) || per < 1) return ADH_E_ARG;
+    if (!(per & 3) && !(al16(src) && al16(dst))) return ADH_E_ARG;
     if (per & 3) return gather_images_scalar(stream, src, sel, count, per, dst, 0);
-    hipLaunchKernelGGL(gather_images_kernel, dim3(adh_min_i(adh_ceil_div(per / 4, 256), 1024), count), dim3(256), 0,
+    hipLaunchKernelGGL(gather_images_kernel, dim3(adh_min_i(adh_ceil_div(per / 4, 256), PW_MAXBLK_GATHER), count), dim3(256), 0,
                        (hipStream_t)stream, src, sel, per / 4, dst, 0);
     return adh_check_launch();
 }
 
 extern "C" int adh_scatter_images(void* stream, const float* src, const int32_t* sel, int count, int64_t per, float* dst) {
-    if (!src || !sel || !dst || count < 1 || per < 1) return ADH_E_ARG;
+    if (!src || !sel || !dst || !batch_ok(count) || per < 1) return ADH_E_ARG;
+    if (!(per & 3) && !(al16(src) && al16(dst))) return ADH_E_ARG;
     if (per & 3) return gather_images_scalar(stream, src, sel, count, per, dst, 1);
-    hipLaunchKernelGGL(gather_images_kernel, dim3(adh_min_i(adh_ceil_div(per / 4, 256), 1024), count), dim3(256), 0,
+    hipLaunchKernelGGL(gather_images_kernel, dim3(adh_min_i(adh_ceil_div(per / 4, 256), PW_MAXBLK_GATHER), count), dim3(256), 0,
                        (hipStream_t)stream, src, sel, per / 4, dst, 1);
     return adh_check_launch();
 }
@@ -462,7 +494,9 @@ extern "C" int adh_scatter_images(void* stream, const float* src, const int32_t*
 // ------------------------------------------------------------------------------------------------
 // losses (training/loss.py:138 L1Loss, :81 mse_loss, :200 CrossEntropyLoss)
 // ------------------------------------------------------------------------------------------------
-extern "C" int adh_reduce_num_blocks(int64_t n) { return adh_max_i(1, adh_min_i(adh_ceil_div(n, RED_ELEMS_PER_BLOCK), 2048)); }
+extern "C" int adh_reduce_num_blocks(int64_t n) {
+    return adh_max_i(1, adh_min_i(adh_ceil_div(n, RED_ELEMS_PER_BLOCK), PW_MAXBLK_RED));
+}
 
 template <int SQ>
 __global__ __launch_bounds__(256) void diff_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
@@ -489,14 +523,14 @@ __global__ __launch_bounds__(256) void diff_partial_kernel(const float* __restri
 }
 
 extern "C" int adh_l1_partial(void* stream, const float* a, const float* b, int64_t n, float* partial) {
-    if (!a || !b || !partial || n < 1) return ADH_E_ARG;
+    if (!a || !b || !partial || n < 1 || !al16(a) || !al16(b)) return ADH_E_ARG;
     hipLaunchKernelGGL(diff_partial_kernel<0>, dim3(adh_reduce_num_blocks(n)), dim3(256), 0, (hipStream_t)stream, a, b, n,
                        partial);
     return adh_check_launch();
 }
 
 extern "C" int adh_mse_partial(void* stream, const float* a, const float* b, int64_t n, float* partial) {
-    if (!a || !b || !partial || n < 1) return ADH_E_ARG;
+    if (!a || !b || !partial || n < 1 || !al16(a) || !al16(b)) return ADH_E_ARG;
     hipLaunchKernelGGL(diff_partial_kernel<1>, dim3(adh_reduce_num_blocks(n)), dim3(256), 0, (hipStream_t)stream, a, b, n,
                        partial);
     return adh_check_launch();
@@ -537,7 +571,7 @@ __global__ __launch_bounds__(256) void diff_bwd_kernel(const float* __restrict__
 extern "C" int adh_l1_bwd(void* stream, const float* a, const float* b, int64_t n, float gscale, const float* upstream,
                           float* g_a) {
     if (!a || !b || !g_a || n < 1) return ADH_E_ARG;
-    hipLaunchKernelGGL(diff_bwd_kernel<0>, dim3(adh_min_i(adh_ceil_div(n, 256), 8192)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(diff_bwd_kernel<0>, dim3(adh_min_i(adh_ceil_div(n, 256), PW_MAXBLK_EW)), dim3(256), 0, (hipStream_t)stream,
                        a, b, n, gscale, upstream, g_a);
     return adh_check_launch();
 }
@@ -545,7 +579,7 @@ extern "C" int adh_l1_bwd(void* stream, const float* a, const float* b, int64_t 
 extern "C" int adh_mse_bwd(void* stream, const float* a, const float* b, int64_t n, float gscale, const float* upstream,
                            float* g_a) {
     if (!a || !b || !g_a || n < 1) return ADH_E_ARG;
-    hipLaunchKernelGGL(diff_bwd_kernel<1>, dim3(adh_min_i(adh_ceil_div(n, 256), 8192)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(diff_bwd_kernel<1>, dim3(adh_min_i(adh_ceil_div(n, 256), PW_MAXBLK_EW)), dim3(256), 0, (hipStream_t)stream,
                        a, b, n, gscale, upstream, g_a);
     return adh_check_launch();
 }
@@ -616,8 +650,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 extern "C" int adh_adam_step(void* stream, float* p, const float* g, float* m, float* v, int64_t n, int step, float lr,
                              float beta1, float beta2, float eps, float weight_decay, int repeats) {
     if (!p || !g || !m || !v || n < 1 || repeats < 1 || step < 0) return ADH_E_ARG;
-    hipLaunchKernelGGL(adam_kernel, dim3(adh_min_i(adh_ceil_div(n, 256), 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m,
-                       v, n, step, lr, beta1, beta2, eps, weight_decay, repeats);
+    hipLaunchKernelGGL(adam_kernel, dim3(adh_min_i(adh_ceil_div(n, 256), PW_MAXBLK_SPATIAL)), dim3(256), 0, (hipStream_t)stream,
+                       p, g, m, v, n, step, lr, beta1, beta2, eps, weight_decay, repeats);
     return adh_check_launch();
 }
 
@@ -631,7 +665,7 @@ __global__ void add_inplace_kernel(float* __restrict__ dst, const float* __restr
 
 extern "C" int adh_add_inplace(void* stream, float* dst, const float* src, int64_t n) {
     if (!dst || !src || n < 1) return ADH_E_ARG;
-    hipLaunchKernelGGL(add_inplace_kernel, dim3(adh_min_i(adh_ceil_div(n, 256), 8192)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(add_inplace_kernel, dim3(adh_min_i(adh_ceil_div(n, 256), PW_MAXBLK_EW)), dim3(256), 0, (hipStream_t)stream,
                        dst, src, n);
     return adh_check_launch();
 }
@@ -652,8 +686,9 @@ __global__ __launch_bounds__(256) void axpby_strided_kernel(float* __restrict__ 
 
 extern "C" int adh_axpby_strided(void* stream, float* dst, int dst_cs, const float* src, int src_cs, int64_t P, int C,
                                  float a, float b) {
-    if (!dst || !src || P < 1 || C < 4 || (C & 3) || (dst_cs & 3) || (src_cs & 3)) return ADH_E_ARG;
-    hipLaunchKernelGGL(axpby_strided_kernel, dim3(adh_min_i(adh_ceil_div(P * (C / 4), 256), 8192)), dim3(256), 0,
+    if (!dst || !src || P < 1 || C < 4 || (C & 3) || !cs4_ok(dst_cs, C) || !cs4_ok(src_cs, C) || !al16(dst) || !al16(src))
+        return ADH_E_ARG;
+    hipLaunchKernelGGL(axpby_strided_kernel, dim3(adh_min_i(adh_ceil_div(P * (C / 4), 256), PW_MAXBLK_EW)), dim3(256), 0,
                        (hipStream_t)stream, dst, dst_cs, src, src_cs, P, C / 4, a, b);
     return adh_check_launch();
 }
@@ -701,10 +736,11 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const float* __restrict__ 
 extern "C" int adh_maxpool(void* stream, const float* x, int x_cs, int N, int H, int W, int C, int k, int stride, int pad,
                            float* out, int out_cs, int32_t* idx) {
     if (!x || !out || k < 1 || stride < 1 || pad < 0 || pad > k / 2 || C < 4 || (C & 3)) return ADH_E_ARG;
+    if (!batch_ok(N) || H < 1 || W < 1 || !cs4_ok(x_cs, C) || !cs4_ok(out_cs, C) || !al16(x) || !al16(out)) return ADH_E_ARG;
     const int OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
     if (OH < 1 || OW < 1) return ADH_E_ARG;
-    hipLaunchKernelGGL(maxpool_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)OH * OW * (C / 4), 256), 4096), N), dim3(256), 0,
-                       (hipStream_t)stream, x, x_cs, H, W, C / 4, k, stride, pad, OH, OW, out, out_cs, idx);
+    hipLaunchKernelGGL(maxpool_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)OH * OW * (C / 4), 256), PW_MAXBLK_SPATIAL), N),
+                       dim3(256), 0, (hipStream_t)stream, x, x_cs, H, W, C / 4, k, stride, pad, OH, OW, out, out_cs, idx);
     return adh_check_launch();
 }
 
@@ -738,9 +774,12 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restric
 
 extern "C" int adh_maxpool_bwd(void* stream, const float* g, int g_cs, const int32_t* idx, int N, int OH, int OW, int C,
                                int k, int stride, int pad, int H, int W, float* gx, int gx_cs) {
-    if (!g || !idx || !gx || k < 1 || stride < 1) return ADH_E_ARG;
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)H * W * C, 256), 4096), N), dim3(256), 0,
-                       (hipStream_t)stream, g, g_cs, idx, OH, OW, C, k, stride, pad, H, W, gx, gx_cs);
+    if (!g || !idx || !gx || k < 1 || stride < 1 || pad < 0 || pad > k / 2) return ADH_E_ARG;
+    if (C < 1 || H < 1 || W < 1 || !batch_ok(N)) return ADH_E_ARG;
+    if (g_cs < C || gx_cs < C || OH < 1 || OW < 1 || OH != (H + 2 * pad - k) / stride + 1 || OW != (W + 2 * pad - k) / stride + 1)
+        return ADH_E_ARG;
+    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)H * W * C, 256), PW_MAXBLK_SPATIAL), N),
+                       dim3(256), 0, (hipStream_t)stream, g, g_cs, idx, OH, OW, C, k, stride, pad, H, W, gx, gx_cs);
     return adh_check_launch();
 }
 
@@ -764,9 +803,10 @@ __global__ __launch_bounds__(256) void avgpool_kernel(const float* __restrict__ 
 
 extern "C" int adh_avgpool(void* stream, const float* x, int x_cs, int N, int H, int W, int C, int k, float* out, int out_cs) {
     if (!x || !out || k < 1 || C < 4 || (C & 3) || H < k || W < k) return ADH_E_ARG;
+    if (!batch_ok(N) || !cs4_ok(x_cs, C) || !cs4_ok(out_cs, C) || !al16(x) || !al16(out)) return ADH_E_ARG;
     const int OH = H / k, OW = W / k;
-    hipLaunchKernelGGL(avgpool_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)OH * OW * (C / 4), 256), 4096), N), dim3(256), 0,
-                       (hipStream_t)stream, x, x_cs, H, W, C / 4, k, OH, OW, out, out_cs);
+    hipLaunchKernelGGL(avgpool_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)OH * OW * (C / 4), 256), PW_MAXBLK_SPATIAL), N),
+                       dim3(256), 0, (hipStream_t)stream, x, x_cs, H, W, C / 4, k, OH, OW, out, out_cs);
     return adh_check_launch();
 }
 
@@ -783,9 +823,9 @@ __global__ __launch_bounds__(256) void global_avgpool_bwd_kernel(const float* __
 }
 
 extern "C" int adh_global_avgpool_bwd(void* stream, const float* g, int N, int HW, int C, float* gx, int gx_cs) {
-    if (!g || !gx || N < 1 || HW < 1 || C < 1) return ADH_E_ARG;
-    hipLaunchKernelGGL(global_avgpool_bwd_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)HW * C, 256), 2048), N), dim3(256), 0,
-                       (hipStream_t)stream, g, HW, C, gx, gx_cs);
+    if (!g || !gx || !batch_ok(N) || HW < 1 || C < 1 || gx_cs < C) return ADH_E_ARG;
+    hipLaunchKernelGGL(global_avgpool_bwd_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)HW * C, 256), PW_MAXBLK_IMAGE), N),
+                       dim3(256), 0, (hipStream_t)stream, g, HW, C, gx, gx_cs);
     return adh_check_launch();
 }
 
@@ -796,7 +836,8 @@ __global__ void mul_kernel(float* __restrict__ dst, const float* __restrict__ a,
 
 extern "C" int adh_mul(void* stream, float* dst, const float* a, const float* b, int64_t n) {
     if (!dst || !a || !b || n < 1) return ADH_E_ARG;
-    hipLaunchKernelGGL(mul_kernel, dim3(adh_min_i(adh_ceil_div(n, 256), 8192)), dim3(256), 0, (hipStream_t)stream, dst, a, b, n);
+    hipLaunchKernelGGL(mul_kernel, dim3(adh_min_i(adh_ceil_div(n, 256), PW_MAXBLK_EW)), dim3(256), 0,
+                       (hipStream_t)stream, dst, a, b, n);
     return adh_check_launch();
 }
 
@@ -845,8 +886,9 @@ __global__ __launch_bounds__(256) void bilinear_kernel(const float* __restrict__
 extern "C" int adh_bilinear(void* stream, const float* x, int x_cs, int N, int H, int W, int C, int OH, int OW,
                             int align_corners, float* out, int out_cs) {
     if (!x || !out || C < 4 || (C & 3) || H < 1 || W < 1 || OH < 1 || OW < 1) return ADH_E_ARG;
-    hipLaunchKernelGGL(bilinear_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)OH * OW * (C / 4), 256), 4096), N), dim3(256), 0,
-                       (hipStream_t)stream, x, x_cs, H, W, C / 4, OH, OW, align_corners, out, out_cs);
+    if (!batch_ok(N) || !cs4_ok(x_cs, C) || !cs4_ok(out_cs, C) || !al16(x) || !al16(out)) return ADH_E_ARG;
+    hipLaunchKernelGGL(bilinear_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)OH * OW * (C / 4), 256), PW_MAXBLK_SPATIAL), N),
+                       dim3(256), 0, (hipStream_t)stream, x, x_cs, H, W, C / 4, OH, OW, align_corners, out, out_cs);
     return adh_check_launch();
 }
 
@@ -913,8 +955,8 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* __restri
 
 extern "C" int adh_bilinear_bwd(void* stream, const float* g, int g_cs, int N, int H, int W, int C, int OH, int OW,
                                 int align_corners, float* gx, int gx_cs) {
-    if (!g || !gx || C < 1 || H < 1 || W < 1 || OH < 1 || OW < 1) return ADH_E_ARG;
-    hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)H * W * C, 256), 4096), N), dim3(256), 0,
-                       (hipStream_t)stream, g, g_cs, H, W, C, OH, OW, align_corners, gx, gx_cs);
+    if (!g || !gx || C < 1 || H < 1 || W < 1 || OH < 1 || OW < 1 || !batch_ok(N) || g_cs < C || gx_cs < C) return ADH_E_ARG;
+    hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(adh_min_i(adh_ceil_div((int64_t)H * W * C, 256), PW_MAXBLK_SPATIAL), N),
+                       dim3(256), 0, (hipStream_t)stream, g, g_cs, H, W, C, OH, OW, align_corners, gx, gx_cs);
     return adh_check_launch();
 }

@@ -9,6 +9,25 @@
 // ------------------------------------------------------------------------------------------------
 #define ADAM_CHUNK ADH_ADAM_CHUNK   // floats per workgroup (common.h: ema.hip walks the same chunks)
 
+// Grid caps of the grid-stride loops and the elements per workgroup of the two-stage sums: names, so that a host build
+// (tools/host_emu) can set them small and run every loop and every multi-block partial row at a few hundred elements; the
+// library is built with these defaults.
+#ifndef TIO_MAXBLK_PIXELS
+#define TIO_MAXBLK_PIXELS 2048       // fog and the augmentation's gather pass: workgroups of 256 pixels per image
+#endif
+#ifndef PSNR_ELEMS_PER_BLOCK
+#define PSNR_ELEMS_PER_BLOCK (256 * 32)
+#endif
+#ifndef PSNR_MAXBLK
+#define PSNR_MAXBLK 1024
+#endif
+#ifndef AUG_ELEMS_PER_BLOCK
+#define AUG_ELEMS_PER_BLOCK (256 * 16)
+#endif
+#ifndef AUG_MAXBLK
+#define AUG_MAXBLK 256
+#endif
+
 // one update of `repeats` listed copies of a tensor; dup_mode 0: the single-tensor loop of torch.optim.Adam (CPU default,
 // every torch < 2.0): `repeats` consecutive full updates; dup_mode 1: torch >= 2.0's foreach form on CUDA, where the
 // duplicate entries of a parameter list alias each other inside the _foreach_ calls (weight decay from the original p,
@@ -231,8 +250,8 @@ extern "C" int adh_apply_fog(void* stream, const float* clear_nchw, const float*
                              int W, float* hazy_nchw) {
     if (!clear_nchw || !beta || !airlight || !hazy_nchw || N < 1 || H < 1 || W < 1 || N > 65535) return ADH_E_ARG;
     const int64_t HW = (int64_t)H * W;
-    hipLaunchKernelGGL(fog_kernel, dim3(adh_min_i(adh_ceil_div(HW, 256), 2048), N), dim3(256), 0, (hipStream_t)stream,
-                       clear_nchw, beta, airlight, H, W, hazy_nchw);
+    hipLaunchKernelGGL(fog_kernel, dim3(adh_min_i(adh_ceil_div(HW, 256), TIO_MAXBLK_PIXELS), N), dim3(256), 0,
+                       (hipStream_t)stream, clear_nchw, beta, airlight, H, W, hazy_nchw);
     return adh_check_launch();
 }
 
@@ -240,10 +259,8 @@ extern "C" int adh_apply_fog(void* stream, const float* clear_nchw, const float*
 // PSNR per image (evaluation/metrics.py:27, training/train_joint.py:217: skimage peak_signal_noise_ratio(target, pred,
 // data_range=1.0) = 10 log10(1 / mean((t-p)^2)), the mean taken in float64 over all 3*H*W elements)
 // ------------------------------------------------------------------------------------------------
-#define PSNR_ELEMS_PER_BLOCK (256 * 32)
-
 extern "C" int adh_psnr_num_blocks(int64_t per_image) {
-    return adh_max_i(1, adh_min_i(adh_ceil_div(per_image, PSNR_ELEMS_PER_BLOCK), 1024));
+    return adh_max_i(1, adh_min_i(adh_ceil_div(per_image, PSNR_ELEMS_PER_BLOCK), PSNR_MAXBLK));
 }
 
 __global__ __launch_bounds__(256) void sqerr_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
@@ -455,7 +472,9 @@ __global__ __launch_bounds__(256) void aug_apply_kernel(const float* __restrict_
     }
 }
 
-extern "C" int adh_augment_num_blocks(int64_t HW) { return adh_max_i(1, adh_min_i(adh_ceil_div(HW, 256 * 16), 256)); }
+extern "C" int adh_augment_num_blocks(int64_t HW) {
+    return adh_max_i(1, adh_min_i(adh_ceil_div(HW, AUG_ELEMS_PER_BLOCK), AUG_MAXBLK));
+}
 
 extern "C" int adh_paired_augment(void* stream, const float* x_nchw, const float* params, int N, int H, int W, double* partial,
                                   int nblk, float* out_nchw) {
@@ -463,7 +482,7 @@ extern "C" int adh_paired_augment(void* stream, const float* x_nchw, const float
     const int64_t HW = (int64_t)H * W;
     if (nblk != adh_augment_num_blocks(HW) || x_nchw == out_nchw) return ADH_E_ARG;
     hipLaunchKernelGGL(aug_gray_partial_kernel, dim3(nblk, N), dim3(256), 0, (hipStream_t)stream, x_nchw, params, HW, partial);
-    hipLaunchKernelGGL(aug_apply_kernel, dim3(adh_min_i(adh_ceil_div(HW, 256), 2048), N), dim3(256), 0, (hipStream_t)stream, x_nchw,
-                       params, partial, nblk, H, W, out_nchw);
+    hipLaunchKernelGGL(aug_apply_kernel, dim3(adh_min_i(adh_ceil_div(HW, 256), TIO_MAXBLK_PIXELS), N), dim3(256), 0,
+                       (hipStream_t)stream, x_nchw, params, partial, nblk, H, W, out_nchw);
     return adh_check_launch();
 }

@@ -32,6 +32,11 @@ def _warn_random_extractor(what: str, how: str):
                       f"initialised until real weights are loaded ({how}).", stacklevel=3)
 
 
+def _aligned16(t):
+    """the loss reductions read 16 bytes per lane: a contiguous view that starts off a 16-byte boundary is copied"""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 class _L1Fn(torch.autograd.Function):
     """mean(|a - b|)  (nn.L1Loss, loss.py:119,138)."""
 
@@ -39,7 +44,7 @@ class _L1Fn(torch.autograd.Function):
     def forward(ctx, a, b):
         H.require_cuda(a, "prediction")
         H.require_cuda(b, "target")
-        a, b = a.contiguous(), b.contiguous()
+        a, b = _aligned16(a.contiguous()), _aligned16(b.contiguous())
         n = a.numel()
         nblk = H.value("adh_reduce_num_blocks", n)
         partial = torch.empty(nblk, device=a.device, dtype=torch.float32)
@@ -68,7 +73,7 @@ class _MSEFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, b):
-        a, b = a.contiguous(), b.contiguous()
+        a, b = _aligned16(a.contiguous()), _aligned16(b.contiguous())
         n = a.numel()
         nblk = H.value("adh_reduce_num_blocks", n)
         partial = torch.empty(nblk, device=a.device, dtype=torch.float32)

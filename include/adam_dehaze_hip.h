@@ -361,6 +361,28 @@ int adh_cbam_bwd_e(void* stream, const float* g, int g_cs, const float* x, int x
                    const float* sa, const float* gsmap, const int32_t* cidx, const float* gpool,
                    const int32_t* amax_idx, int N, int HW, int C, float* gx, int gx_cs);
 
+/* ---- Buffer contract of csrc/pointwise.hip (every entry point from here to adh_bilinear_bwd) -------------------------------
+ * A violation returns ADH_E_ARG before anything is launched; nothing is written.
+ *   sizes     Every N, H, W, C, HW, OH, OW, P, n, per, count and nblk is >= 1.  A batch size that becomes a grid dimension
+ *             (N of the transposes, pools, resizes, soft blends and adh_global_avgpool_bwd; count of gather / scatter) is
+ *             <= 65535.
+ *   NHWC      A tensor with a channel stride `cs` is [pixels][cs] floats of which the entry point owns channels 0..C-1 of every
+ *             pixel and touches nothing else; it may end at the last owned channel of the last pixel.  cs >= C always (r_cs >= 3,
+ *             g_cs >= 3 of adh_image_normalize_bwd, gd_cs >= 1).  The exception is adh_head_blend_bwd: g_r and g_gd are dense
+ *             [pixels][r_cs] and [pixels][gd_cs] blocks the kernel writes whole (channels >= 3 and >= 1 zeroed).
+ *   16 bytes  Entry points that move four channels per lane need C % 4 == 0, cs % 4 == 0 and a 16-byte aligned base (so every
+ *             pixel's slice is aligned): x / out of adh_maxpool, adh_avgpool and adh_bilinear; dst / src of adh_axpby_strided.
+ *             16-byte aligned bases, dense: out of adh_image_to_nhwc8 and adh_image_normalize_to_nhwc8; a and b of
+ *             adh_l1_partial / adh_mse_partial (any n: the n % 4 tail is read float by float); g, o0..o2 and the non-null g0..g2
+ *             of adh_soft_blend_bwd (per % 4 == 0); o0..o2 / out of adh_soft_blend and src / dst of adh_gather_images /
+ *             adh_scatter_images when per % 4 == 0 (any alignment when it is not: single floats).
+ *   scalar    Everything else is read and written float by float and needs only its natural alignment and cs >= C:
+ *             adh_nchw_to_nhwc, adh_nhwc_to_nchw, adh_image_normalize_bwd, adh_head_blend(_bwd), adh_maxpool_bwd (g_cs, gx_cs;
+ *             idx is dense [N][OH][OW][C]; OH, OW must be the forward's (H + 2 pad - k) / stride + 1), adh_global_avgpool_bwd
+ *             (gx_cs), adh_bilinear_bwd (g_cs, gx_cs), the routing, loss-gradient, Adam and dense elementwise entry points.
+ *   partials  galpha_partial[nblk] with nblk = adh_head_blend_bwd_num_blocks; partial[adh_reduce_num_blocks(n)];
+ *             gw_partial[N][nblk][3] for any nblk >= 1 the caller chooses; sel[3][N] and counts[3] of adh_route_compact (only the
+ *             first counts[c] entries of row c are written). */
 /* ---- boundary layout + branch heads ------------------------------------------------------------ */
 /* NCHW [N,3,H,W] image -> NHWC with cstride 8 (channels 3..7 zero) */
 int adh_image_to_nhwc8(void* stream, const float* img, int N, int H, int W, float* out);

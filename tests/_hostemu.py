@@ -1,5 +1,5 @@
 """Shared by the tests/test_*_hostemu_cpu.py that run on tools/host_emu/stream_rt.cpp (bn_act, depthwise, densenet, image_io, d4,
-ciede2000, cbam, lpips, detect, and the shuffle's self-test): builds a copy of one csrc/*.hip file with the host C++
+ciede2000, cbam, lpips, detect, pointwise, train_io, and the shuffle's self-test): builds a copy of one csrc/*.hip file with the host C++
 compiler against tools/host_emu (common.h's ADH_HOST_EMU_STREAM section, stream_rt.cpp, the file's driver) under
 AddressSanitizer and UndefinedBehaviorSanitizer, and runs scripts (tools/host_emu/stream_rt.h) through the resulting stand-alone
 program.  Nothing is loaded into Python.
@@ -99,14 +99,15 @@ class Script:
         return k
 
     def out(self, n, dtype=np.float32, init=None):
-        """a dense output of n elements, every element poison (0x5A bytes for uint8) unless `init` is given"""
+        """a dense output of n elements, every element poison (every byte 0x5A for the integer types: 0x5A5A5A5A as int32)
+        unless `init` is given"""
         if init is not None:
             return self.raw(np.ascontiguousarray(torch.as_tensor(init).detach().numpy().astype(dtype)))
         if dtype == np.float32:
             return self.raw(np.full(n, WPOISON, np.uint32))
         if dtype == np.float64:
             return self.raw(np.full(n, 0x7FF8DEADBEEF0000, np.uint64))
-        return self.raw(np.full(n, 0x5A, dtype))
+        return self.raw(np.full(n * np.dtype(dtype).itemsize, 0x5A, np.uint8).view(dtype))
 
     # ------------------------------------------------------------------ calls
     def call(self, fn, ints=(), bufs=(), doubles=()):

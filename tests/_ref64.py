@@ -139,6 +139,52 @@ def adam(p, g, m, v, step, repeats, dup_mode, lr, beta1, beta2, eps, wd, gscale,
     return (p, m, v), (ep, em, ev)
 
 
+# ---- the bounds and cases tests/test_gpu_train_io.py and tests/test_train_io_hostemu_cpu.py hold csrc/train_io.hip to
+# float64 part of the fog kernel (x * (1 / (W - 1)) against linspace, sqrt, exp, six more operations, the exponent's
+# condition number beta * depth <= 3 * 1.2): 64 units of 2^-53 by that count.  It cannot be measured through the fp32
+# store, where it only shows as a flipped rounding: measured 0 (every element within half an fp32 ulp), bound 64.
+FOG_F64_UNITS = 64
+# float64 log10 and the float64 sums: not observable through the fp32 store of the results; the sums are of at most
+# per / (1024 * 256) serial terms per thread plus a 20-level tree: 128 units of 2^-53 cover them.  measured 2 (the vector
+# and the scalar path's float64 sums of the same data differ by at most 2 units; 2^-50 = 8 is asserted by the tests), bound 128.
+PSNR_F64_UNITS = 128
+# powf(beta, t) of the bias corrections, in EPS relative to beta^t: measured 1, bound 4 (test_adam_bias_correction_powf of the GPU
+# test prints it: 0.96 at worst over t = 1..128, 1000, 10000, 100001).  It matters because 1 - beta2^t amplifies it by
+# beta2^t / (1 - beta2^t), ~1000 at t = 1: the first update is good to ~57 EPS, not to 1.
+ADAM_POW_UNITS = 4
+ADAM_KW = dict(lr=1e-3, beta1=float(np.float32(0.9)), beta2=float(np.float32(0.999)), eps=float(np.float32(1e-8)))
+AUG_BC = [(0.9, 1.1), (1.1, 0.9), (1.05, 0.9), (1.0, 1.0)]
+
+
+def aug_params(b, c):
+    """all eight (flip_h, flip_v, brightness_first) combinations with one (b, c): params [8, 5]"""
+    return torch.tensor([[i & 1, (i >> 1) & 1, (i >> 2) & 1, b, c] for i in range(8)], dtype=torch.float32)
+
+
+def aug_bound(x, params, gabs):
+    """fp32 forward error of brightness = clamp(b x) and contrast = clamp(c x + (1 - c) mean) in either order: one
+    rounding for b x; for the contrast step the products c x and (1 - c) mean, the difference 1 - c and the sum (3 |c x| +
+    4 |(1 - c) mean| roundings, FMA or not); the mean itself: fp32 grayscale (three coefficient roundings, three
+    products, two sums: 6 EPS of mean |gray terms|), summed in float64.  The clamps are 1-Lipschitz."""
+    E = 2.0 ** -24
+    out = []
+    for n in range(x.shape[0]):
+        fh, fv, bfirst, b, c = [float(v) for v in params[n]]
+        img = x[n].double()
+        if fh:
+            img = img.flip(-1)
+        if fv:
+            img = img.flip(-2)
+        xin = (b * img).clamp(0, 1) if bfirst else img
+        e_in = E * (b * img).abs() if bfirst else torch.zeros_like(img)
+        mean = (0.2989 * xin[0] + 0.587 * xin[1] + 0.114 * xin[2]).mean()
+        e = E * (3 * (c * xin).abs() + 4 * abs((1 - c) * mean)) + abs(1 - c) * 6 * E * gabs[n] + abs(c) * e_in
+        if not bfirst:
+            e = abs(b) * e + E * abs(b) * (c * xin + (1 - c) * mean).clamp(0, 1)
+        out.append(e)
+    return torch.stack(out)
+
+
 # ------------------------------------------------------------------------------------------------ detect
 def nearest_src(out_size, in_size):
     """source index of F.interpolate(mode='nearest'): min(floor(i * (in / out)), in - 1), the scale and the product in fp32."""

@@ -6,13 +6,16 @@ padded / overlapping windows, channel-slice inputs and outputs, clamp bounds hit
 Every output and gradient buffer is prefilled with NaN: a kernel must write every element it owns, and everything outside
 the channel slice it owns must still be NaN afterwards.  Every deterministic kernel runs twice and must reproduce itself
 bit for bit.  Tolerances are relative to the float64 reference's largest magnitude unless a comment says otherwise, and
-each comment says what in the kernel's fp32 arithmetic bounds it (EPS = 2^-24, the fp32 unit roundoff)."""
+each comment says what in the kernel's fp32 arithmetic bounds it (EPS = 2^-24, the fp32 unit roundoff).  The restatements, case
+builders and bounds this file shares with tests/test_pointwise_hostemu_cpu.py (the same source under the host sanitizers) are in
+tests/_pointwise_ref64.py: they build CPU tensors, which are moved to the device here."""
 import pytest
 import torch
 import torch.nn.functional as F
 
 from adam_dehaze_amd import _hip as H
 from adam_dehaze_amd.engine import Act, Engine
+from tests import _pointwise_ref64 as P
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -60,18 +63,19 @@ def _nchw64(t_nhwc):
 
 
 # ------------------------------------------------------------------------------------------------ MaxPool
-MP_CFG = [(2, 2, 0), (4, 4, 0), (3, 2, 1), (3, 2, 0), (1, 2, 0)]
+MP_CFG = P.MP_CFG
 MP_SHAPES = [(2, 7, 9, 16), (3, 33, 47, 64), (1, 5, 130, 96)]
 
 
+def _rejected(name, *args):
+    with pytest.raises(RuntimeError):
+        H.call(name, *args)
+    torch.cuda.synchronize()
+
+
 def _check_maxpool(N, Hh, Ww, C, k, s, p, x_cs, g_cs, gx_cs, seed):
-    # values from {0, 1, 2}: nearly every window ties.  Gradients are multiples of 1/4 in [-2, 2]: every sum the backward
-    # forms is exact in fp32, so the gradient must equal float64 autograd exactly.
-    xb = torch.randint(0, 3, (N, Hh, Ww, x_cs), device=DEV, generator=_gen(seed)).float()
-    x = xb[..., :C]
-    OH, OW = (Hh + 2 * p - k) // s + 1, (Ww + 2 * p - k) // s + 1
-    gb = torch.randint(-8, 9, (N, OH, OW, g_cs), device=DEV, generator=_gen(seed + 1)).float() / 4
-    g = gb[..., :C]
+    xb, gb = (t.to(DEV) for t in P.maxpool_inputs(N, Hh, Ww, k, s, p, x_cs, g_cs, seed))      # ties everywhere, exact sums
+    OH, OW = gb.shape[1], gb.shape[2]
 
     def run():
         out, idx = _nan(N, OH, OW, C), torch.full((N, OH, OW, C), -7, device=DEV, dtype=torch.int32)
@@ -81,12 +85,10 @@ def _check_maxpool(N, Hh, Ww, C, k, s, p, x_cs, g_cs, gx_cs, seed):
         return out, idx, gx
 
     out, idx, gx = _twice(run)
-    x64 = _nchw64(x).requires_grad_(True)
-    y, ind = F.max_pool2d(x64, k, s, p, return_indices=True)
-    y.backward(_nchw64(g))
-    assert torch.equal(_nchw64(out), y.detach()), "pooled values"
+    y, ind, gref = P.maxpool_ref(xb[..., :C], gb[..., :C], k, s, p)
+    assert torch.equal(_nchw64(out), y), "pooled values"
     assert torch.equal(idx.permute(0, 3, 1, 2).long(), ind), "arg-max indices (ties must go to the first in scan order)"
-    assert torch.equal(_nchw64(gx[..., :C]), x64.grad), "input gradient"
+    assert torch.equal(_nchw64(gx[..., :C]), gref), "input gradient"
     assert torch.isnan(gx[..., C:]).all(), "gradient written outside its channel slice"
 
 
@@ -108,40 +110,14 @@ def test_maxpool_grid_stride_loop():
 
 
 # ------------------------------------------------------------------------------------------------ bilinear resize
-def _src_err(n_in, n_out, align):
-    """max |fp32 - float64| of the source coordinate along one axis: the only error of the resize weights."""
-    o = torch.arange(n_out, dtype=torch.float64)
-    if align:
-        s64 = o * ((n_in - 1) / (n_out - 1) if n_out > 1 else 0.0)
-        s32 = o.float() * torch.tensor((n_in - 1) / (n_out - 1) if n_out > 1 else 0.0, dtype=torch.float32)
-    else:
-        s64 = ((o + 0.5) * (n_in / n_out) - 0.5).clamp_min(0)
-        s32 = ((o.float() + 0.5) * torch.tensor(n_in / n_out, dtype=torch.float32) - 0.5).clamp_min(0)
-    return float((s32.double() - s64).abs().max())
-
-
-BL_CASES = [
-    # N, H, W, C, OH, OW, align_corners, x_cs, out_cs (out_cs > C: written at channel offset 4 of a wider buffer)
-    (2, 19, 23, 16, 38, 46, 1, 16, 16),          # x2 (CORUN-inspired, DualBranch)
-    (1, 13, 17, 8, 52, 68, 1, 16, 8),            # x4, input read from a channel slice
-    (2, 1, 9, 4, 3, 33, 1, 4, 4),                # one-row input
-    (2, 5, 9, 4, 1, 17, 1, 4, 4),                # OH = 1: the `out > 1 ? ... : 0` branch
-    (2, 7, 1, 4, 15, 1, 1, 4, 4),                # one-column input, OW = 1
-    (2, 8, 12, 12, 17, 25, 0, 12, 12),           # non-integer up-sampling
-    (1, 301, 401, 12, 200, 266, 0, 12, 12),      # non-integer down-sampling (detector transform); backward loops
-    (2, 9, 11, 16, 19, 23, 0, 16, 28),           # into a channel slice of a concat buffer (_UNetTrunk's out=)
-    (1, 1, 7, 4, 5, 13, 0, 4, 4),                # one-row input, align_corners=False
-    (1, 256, 512, 32, 512, 1024, 1, 32, 32),     # x2 at a CORUN-sized plane: both grid-stride loops run several times
-]
+BL_CASES = P.BL_CASES
 
 
 @pytest.mark.parametrize("case", BL_CASES, ids=lambda c: "%dx%dx%dx%d-%dx%d-a%d-xcs%d-ocs%d" % c)
 def test_bilinear_fwd_bwd_vs_float64(case):
     N, Hh, Ww, C, OH, OW, align, x_cs, out_cs = case
     off = 4 if out_cs > C else 0
-    xb = _rand(N, Hh, Ww, x_cs, seed=Hh * 7 + Ww)
-    x = xb[..., :C]
-    g = _rand(N, OH, OW, C, seed=OH + OW)    # positive: |reference| ~ the sum of |terms| the backward adds
+    xb, g = (t.to(DEV) for t in P.bilinear_inputs(N, Hh, Ww, C, OH, OW, x_cs))
 
     def run():
         ob = _nan(N, OH, OW, out_cs)
@@ -151,17 +127,16 @@ def test_bilinear_fwd_bwd_vs_float64(case):
         return ob, gx
 
     ob, gx = _twice(run)
-    x64 = _nchw64(x).requires_grad_(True)
-    y = F.interpolate(x64, size=(OH, OW), mode="bilinear", align_corners=bool(align))
-    y.backward(_nchw64(g))
+    y, gref = P.bilinear_ref(xb[..., :C], g, OH, OW, align)
     # both sides use ATen's source-coordinate formula; the kernel evaluates it in fp32 like ATen's fp32 path.  An error ds
     # in a coordinate moves an output by at most ds * (neighbour difference <= max|x| for x in [0, 1)) and a weight by ds.
-    ds = _src_err(Hh, OH, align) + _src_err(Ww, OW, align)
-    e_f = _rel(ob[..., off:off + C], y.detach().permute(0, 2, 3, 1))
-    assert e_f <= 4 * ds + 8 * EPS, f"forward: {e_f:.3e} (source-coordinate error {ds:.3e})"
     # backward: up to (2 * ratio + 1)^2 fp32 products summed per input element, in two levels (row sums, then rows)
-    e_b = _rel(gx, x64.grad.permute(0, 2, 3, 1))
-    assert e_b <= 8 * ds + 64 * EPS, f"backward: {e_b:.3e} (source-coordinate error {ds:.3e})"
+    b_f, b_b, ds = P.bilinear_bounds(Hh, Ww, OH, OW, align)
+    assert (b_f, b_b) == (4 * ds + 8 * EPS, 8 * ds + 64 * EPS)
+    e_f = _rel(ob[..., off:off + C], y)
+    assert e_f <= b_f, f"forward: {e_f:.3e} (source-coordinate error {ds:.3e})"
+    e_b = _rel(gx, gref)
+    assert e_b <= b_b, f"backward: {e_b:.3e} (source-coordinate error {ds:.3e})"
     if out_cs > C:
         assert torch.isnan(ob[..., :off]).all() and torch.isnan(ob[..., off + C:]).all(), "written outside its slice"
 
@@ -226,52 +201,16 @@ def test_global_avgpool_bwd_channel_slice():
 
 
 # ------------------------------------------------------------------------------------------------ branch-head blends
-def _blend_ref(mode, x, r, gd, a):
-    if mode == 0:
-        return (1 - a) * x + a * torch.sigmoid(r)
-    if mode == 1:
-        return torch.clamp(x + torch.tanh(r), 0, 1)
-    if mode == 2:
-        return torch.clamp(x + torch.tanh(r) * torch.sigmoid(gd), 0, 1)
-    if mode == 3:
-        return torch.clamp(x + (torch.sigmoid(r) - 0.5) * 2, 0, 1)
-    return torch.clamp(x + torch.tanh(r) * (1 - torch.sigmoid(gd)), 0, 1)
+_blend_ref = P.blend_ref
 
 
 def _blend_inputs(mode, N, Hh, Ww, r_cs, gd_cs, seed):
-    """x in [0, 1], pre-activations r (channels 0..2 of r_cs) and gd (channel 0 of gd_cs).  Every 5th pixel has r = 0 and
-    x on a clamp bound, where x + delta is exactly 0 or 1 in both fp32 and float64 (tanh(0) = 0, sigmoid(0) = 0.5): torch's
-    clamp passes the gradient there.  Elsewhere r is zeroed wherever float64 puts x + delta within 1e-4 of a bound, so that
-    fp32 rounding cannot flip the clamp mask."""
-    x = _rand(N, 3, Hh, Ww, seed=seed)
-    rb = _randn(N, Hh, Ww, r_cs, seed=seed + 1) * 1.5
-    gdb = _randn(N, Hh, Ww, gd_cs, seed=seed + 2) * 2
-    edge = (torch.arange(N * Hh * Ww, device=DEV) % 5 == 0).view(N, Hh, Ww)
-    x[:, 0][edge] = 0.0
-    x[:, 1][edge] = 1.0
-    x[:, 2][edge] = torch.where(torch.arange(int(edge.sum()), device=DEV) % 2 == 0, 0.0, 1.0)
-    rb[..., :3][edge] = 0.0
-    if mode != 0:
-        raw = _raw(mode, x.double(), rb[..., :3].permute(0, 3, 1, 2).double(), gdb[..., :1].permute(0, 3, 1, 2).double())
-        near = ((raw.abs() < 1e-4) | ((raw - 1).abs() < 1e-4)).permute(0, 2, 3, 1)
-        rb[..., :3][near] = 0.0
-    return x.contiguous(), rb, gdb
-
-
-def _raw(mode, x, r, gd):
-    """x + delta before the clamp."""
-    if mode == 1:
-        return x + torch.tanh(r)
-    if mode == 2:
-        return x + torch.tanh(r) * torch.sigmoid(gd)
-    if mode == 3:
-        return x + (torch.sigmoid(r) - 0.5) * 2
-    return x + torch.tanh(r) * (1 - torch.sigmoid(gd))
+    return tuple(t.to(DEV) for t in P.blend_inputs(mode, N, Hh, Ww, r_cs, gd_cs, seed))
 
 
 def _check_head_blend(mode, N, Hh, Ww, r_cs, gd_cs, seed):
     x, rb, gdb = _blend_inputs(mode, N, Hh, Ww, r_cs, gd_cs, seed)
-    alpha = torch.tensor([0.3125], device=DEV)
+    alpha = torch.tensor([P.BLEND_ALPHA], device=DEV)
     g = _randn(N, 3, Hh, Ww, seed=seed + 3)
     nb = H.value("adh_head_blend_bwd_num_blocks", N, Hh, Ww)
     gated = mode in (2, 4)
@@ -289,25 +228,22 @@ def _check_head_blend(mode, N, Hh, Ww, r_cs, gd_cs, seed):
         return out, g_r, g_gd, ga
 
     out, g_r, g_gd, ga = _twice(run)
-    r64 = rb[..., :3].permute(0, 3, 1, 2).double().requires_grad_(True)
-    gd64 = gdb[..., :1].permute(0, 3, 1, 2).double().requires_grad_(True)
-    a64 = alpha.double().requires_grad_(True)
-    y = _blend_ref(mode, x.double(), r64, gd64, a64)
-    y.backward(g.double())
+    y, gr_ref, ggd_ref, ga_ref, terms = P.blend_ref_grads(mode, x, rb, gdb, g)
+    b_f, b_g, b_a = P.blend_bounds()
+    assert (b_f, b_g, b_a) == (16 * EPS, 32 * EPS, 64 * EPS)
     # forward: expf / tanhf are faithful to a few ulp, then two or three fp32 operations on values of size <= 2
-    assert float((out.double() - y.detach()).abs().max()) <= 16 * EPS, "forward"
+    assert float((out.double() - y).abs().max()) <= b_f, "forward"
     # gradients: products of a few faithfully rounded factors (the gate gradient adds three of them)
-    assert _rel(g_r[..., :3], r64.grad.permute(0, 2, 3, 1)) <= 32 * EPS, "g_r"
+    assert _rel(g_r[..., :3], gr_ref) <= b_g, "g_r"
     assert torch.equal(g_r[..., 3:], torch.zeros_like(g_r[..., 3:])), "padding channels of g_r must be exactly 0"
     if gated:
-        assert _rel(g_gd[..., :1], gd64.grad.permute(0, 2, 3, 1)) <= 32 * EPS, "g_gd"
+        assert _rel(g_gd[..., :1], ggd_ref) <= b_g, "g_gd"
         assert torch.equal(g_gd[..., 1:], torch.zeros_like(g_gd[..., 1:])), "padding channels of g_gd must be exactly 0"
     else:
         assert torch.isnan(g_gd).all()
     if mode == 0:
         # fp32 sums per thread, wave and block, then fp64 over the block partials: relative to the sum of |terms|
-        terms = (g.double() * (torch.sigmoid(rb[..., :3].permute(0, 3, 1, 2).double()) - x.double())).abs().sum()
-        assert abs(float(ga) - float(a64.grad)) <= 64 * EPS * float(terms), "alpha gradient"
+        assert abs(float(ga) - ga_ref) <= b_a * terms, "alpha gradient"
 
 
 @pytest.mark.parametrize("mode", [0, 1, 2, 3, 4])
@@ -511,7 +447,7 @@ def test_gather_scatter_images_round_trip():
 
 
 # ------------------------------------------------------------------------------------------------ losses
-LOSS_N = [1, 3, 4097, 4096 * 2048 + 5, 8 * 3 * 512 * 1024]
+LOSS_N = P.LOSS_N
 
 
 @pytest.mark.parametrize("sq", [0, 1], ids=["l1", "mse"])
@@ -623,3 +559,146 @@ def test_add_inplace_and_mul_exact(n):
     # one correctly rounded operation each: equal to the float64 result rounded to fp32
     assert torch.equal(s, (a.double() + b.double()).float())
     assert torch.equal(m, (a.double() * b.double()).float())
+
+
+# ------------------------------------------------------------------------------------------------ generic transposes
+@pytest.mark.parametrize("HW", P.LAYOUT_HW)
+@pytest.mark.parametrize("C", P.LAYOUT_C)
+def test_nchw_nhwc_transposes_exact(C, HW):
+    """32 x 32 tiles through LDS: channel and pixel counts on both sides of a tile edge, dense (cs = C) and into / out of a
+    channel slice (cs = C + 5: the stores are scalar, so any stride is legal).  A bit-exact copy; the slack stays NaN."""
+    N = 2
+    src = P.randn(N, C, HW, 1, seed=C * 100 + HW).to(DEV)
+    for cs in (C, C + 5):
+        def run():
+            nhwc = _nan(N, HW, 1, cs)
+            H.call("adh_nchw_to_nhwc", src.data_ptr(), N, C, HW, 1, nhwc.data_ptr(), cs)
+            back = _nan(N, C, 1, HW)                               # the same plane as 1 x HW: only H * W enters
+            H.call("adh_nhwc_to_nchw", nhwc.data_ptr(), cs, N, C, 1, HW, back.data_ptr())
+            return nhwc, back
+
+        nhwc, back = _twice(run)
+        assert torch.equal(nhwc[..., :C].view(torch.int32), src.permute(0, 2, 3, 1).contiguous().view(torch.int32))
+        assert torch.isnan(nhwc[..., C:]).all(), "written outside its channel slice"
+        assert torch.equal(back.view(N, C, HW).view(torch.int32), src.view(N, C, HW).view(torch.int32))
+
+
+# ------------------------------------------------------------------------------------------------ single-tensor Adam
+@pytest.mark.parametrize("step", [0, 7])
+@pytest.mark.parametrize("repeats", [1, 2, 3])
+@pytest.mark.parametrize("n", P.ADAM_STEP_N)
+def test_adam_step_vs_float64(n, repeats, step):
+    """adh_adam_step (in the C ABI, unused by the package) against the float64 Adam of tests/_ref64.py with its powf allowance;
+    p, m and v sit in NaN guard bands, 257 and 1500 elements take more than one block."""
+    kw = dict(lr=1e-3, beta1=float(torch.tensor(0.9)), beta2=float(torch.tensor(0.999)), eps=float(torch.tensor(1e-8)),
+              wd=float(torch.tensor(1e-2)))
+    p0, g, m0, v0 = P.adam_step_case(n, seed=n + 10 * repeats + step)
+    gd = g.to(DEV)
+
+    def run():
+        bufs = []
+        for t in (p0, m0, v0):
+            whole = _nan(n + 32)
+            whole[16:16 + n] = t.to(DEV)
+            bufs.append(whole)
+        p, m, v = (b[16:16 + n] for b in bufs)
+        H.call("adh_adam_step", p.data_ptr(), gd.data_ptr(), m.data_ptr(), v.data_ptr(), n, step, kw["lr"], kw["beta1"],
+               kw["beta2"], kw["eps"], kw["wd"], repeats)
+        return tuple(bufs)
+
+    bufs = _twice(run)
+    (p, m, v), (ep, em, ev) = P.adam_step_ref(p0, g, m0, v0, step, repeats, **kw)
+    for what, whole, ref, e in (("p", bufs[0], p, ep), ("m", bufs[1], m, em), ("v", bufs[2], v, ev)):
+        got = whole[16:16 + n].cpu()
+        assert not torch.isnan(got).any(), what
+        over = float(((got.double() - ref).abs() - e).max())
+        assert over <= 0, f"{what} is {over:.3e} over its bound"
+        assert torch.isnan(whole[:16]).all() and torch.isnan(whole[16 + n:]).all(), f"{what}: written outside the tensor"
+
+
+# ------------------------------------------------------------------------------------------------ argument rejections
+def test_pool_and_resize_reject_bad_strides():
+    """the buffer contract of include/adam_dehaze_hip.h: four channels per lane need cs % 4 == 0 and cs >= C; N, H, W >= 1.
+    Every bad call raises and leaves its outputs NaN."""
+    N, Hh, Ww, C = 2, 6, 8, 8
+    x = _rand(N, Hh, Ww, 16, seed=1)
+    out, idx = _nan(N, Hh, Ww, 16), torch.full((N, Hh, Ww, C), -7, device=DEV, dtype=torch.int32)
+    for x_cs, out_cs, n, h, w in ((10, 8, N, Hh, Ww), (8, 10, N, Hh, Ww), (4, 8, N, Hh, Ww), (8, 4, N, Hh, Ww), (8, 8, 0, Hh, Ww),
+                                  (8, 8, N, 0, Ww), (8, 8, N, Hh, 0), (8, 8, 65536, Hh, Ww)):
+        _rejected("adh_maxpool", x.data_ptr(), x_cs, n, h, w, C, 2, 2, 0, out.data_ptr(), out_cs, idx.data_ptr())
+        if h and w:
+            _rejected("adh_avgpool", x.data_ptr(), x_cs, n, h, w, C, 2, out.data_ptr(), out_cs)
+        _rejected("adh_bilinear", x.data_ptr(), x_cs, n, h, w, C, 3, 5, 0, out.data_ptr(), out_cs)
+    # a base one float off 16-byte alignment
+    _rejected("adh_maxpool", x.data_ptr() + 4, 8, N, Hh, Ww, C, 2, 2, 0, out.data_ptr(), 8, idx.data_ptr())
+    _rejected("adh_avgpool", x.data_ptr(), 8, N, Hh, Ww, C, 2, out.data_ptr() + 4, 8)
+    _rejected("adh_bilinear", x.data_ptr() + 8, 8, N, Hh, Ww, C, 3, 5, 1, out.data_ptr(), 8)
+    assert torch.isnan(out).all() and (idx == -7).all()
+
+
+def test_backward_entry_points_reject_bad_arguments():
+    N, Hh, Ww, C = 2, 6, 8, 4
+    g = _rand(N, 3, 4, 8, seed=2)
+    idx = torch.zeros((N, 3, 4, C), device=DEV, dtype=torch.int32)
+    gx = _nan(N, Hh, Ww, 8)
+    ok = dict(g_cs=8, N=N, OH=3, OW=4, C=C, k=2, s=2, p=0, H=Hh, W=Ww, gx_cs=8)
+    for bad in (dict(g_cs=3), dict(gx_cs=3), dict(N=0), dict(OH=0), dict(OW=5), dict(OH=4), dict(C=0), dict(H=0), dict(W=0),
+                dict(p=-1), dict(p=2), dict(k=0), dict(s=0)):
+        a = {**ok, **bad}
+        _rejected("adh_maxpool_bwd", g.data_ptr(), a["g_cs"], idx.data_ptr(), a["N"], a["OH"], a["OW"], a["C"], a["k"], a["s"],
+                  a["p"], a["H"], a["W"], gx.data_ptr(), a["gx_cs"])
+    for g_cs, gx_cs, n in ((3, 8, N), (8, 3, N), (8, 8, 0)):
+        _rejected("adh_bilinear_bwd", g.data_ptr(), g_cs, n, Hh, Ww, C, 3, 4, 0, gx.data_ptr(), gx_cs)
+    gv = _rand(N, C, seed=3)
+    for n, hw, c, gx_cs in ((N, 48, C, 3), (0, 48, C, 8), (N, 0, C, 8), (N, 48, 0, 8)):
+        _rejected("adh_global_avgpool_bwd", gv.data_ptr(), n, hw, c, gx.data_ptr(), gx_cs)
+    gi = _nan(N, 3, Hh, Ww)
+    for g_cs, n, h, w in ((2, N, Hh, Ww), (8, 0, Hh, Ww), (8, N, 0, Ww), (8, N, Hh, 0)):
+        _rejected("adh_image_normalize_bwd", gx.data_ptr(), g_cs, n, h, w, 1.0, 1.0, 1.0, gi.data_ptr())
+    assert torch.isnan(gx).all() and torch.isnan(gi).all()
+
+
+def test_head_blend_and_layout_reject_bad_sizes():
+    N, Hh, Ww = 2, 5, 7
+    x, rb, gdb = _blend_inputs(2, N, Hh, Ww, 4, 4, seed=4)
+    alpha = torch.tensor([P.BLEND_ALPHA], device=DEV)
+    out, g_r, g_gd, gap = _nan(N, 3, Hh, Ww), _nan(N, Hh, Ww, 4), _nan(N, Hh, Ww, 4), _nan(4)
+    for n, h, w in ((0, Hh, Ww), (N, 0, Ww), (N, Hh, 0)):
+        for mode in (0, 2):
+            _rejected("adh_head_blend", mode, x.data_ptr(), rb.data_ptr(), 4, gdb.data_ptr(), 4, alpha.data_ptr(), n, h, w,
+                      out.data_ptr())
+            _rejected("adh_head_blend_bwd", mode, x.data_ptr(), x.data_ptr(), rb.data_ptr(), 4, gdb.data_ptr(), 4, alpha.data_ptr(),
+                      n, h, w, g_r.data_ptr(), g_gd.data_ptr(), gap.data_ptr(), H.value("adh_head_blend_bwd_num_blocks", n, h, w))
+        _rejected("adh_image_to_nhwc8", x.data_ptr(), n, h, w, g_r.data_ptr())
+        _rejected("adh_nchw_to_nhwc", x.data_ptr(), n, 3, h, w, g_r.data_ptr(), 4)
+        _rejected("adh_nhwc_to_nchw", rb.data_ptr(), 4, n, 3, h, w, out.data_ptr())
+    _rejected("adh_head_blend", 2, x.data_ptr(), rb.data_ptr(), 2, gdb.data_ptr(), 4, alpha.data_ptr(), N, Hh, Ww, out.data_ptr())
+    _rejected("adh_head_blend", 2, x.data_ptr(), rb.data_ptr(), 4, gdb.data_ptr(), 0, alpha.data_ptr(), N, Hh, Ww, out.data_ptr())
+    _rejected("adh_nchw_to_nhwc", x.data_ptr(), N, 3, Hh, Ww, g_r.data_ptr(), 2)
+    _rejected("adh_image_to_nhwc8", x.data_ptr(), N, Hh, Ww, g_r.data_ptr() + 4)                      # 16-byte stores
+    assert all(torch.isnan(t).all() for t in (out, g_r, g_gd, gap))
+
+
+def test_vector_paths_reject_unaligned_bases():
+    """what moves 16 bytes per lane needs 16-byte aligned bases; the single-float paths (per % 4 != 0) take any"""
+    N, per = 2, 16
+    buf = _rand(4 * N * per + 8, seed=5)
+    w = torch.softmax(_randn(N, 3, seed=6), dim=1).contiguous()
+    o = [buf[i * N * per:(i + 1) * N * per] for i in range(3)]
+    out, gwp, part = _nan(N * per + 4), _nan(N, 1, 3), _nan(4)
+    sel = torch.tensor([1, 0], device=DEV, dtype=torch.int32)
+    _rejected("adh_soft_blend", w.data_ptr(), o[0].data_ptr() + 4, o[1].data_ptr(), o[2].data_ptr(), N, per, out.data_ptr())
+    _rejected("adh_soft_blend", w.data_ptr(), o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), N, per, out.data_ptr() + 4)
+    _rejected("adh_soft_blend_bwd", w.data_ptr(), o[0].data_ptr(), o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), N, per,
+              out.data_ptr() + 4, None, None, gwp.data_ptr(), 1)
+    _rejected("adh_gather_images", o[0].data_ptr() + 4, sel.data_ptr(), N, per, out.data_ptr())
+    _rejected("adh_scatter_images", o[0].data_ptr(), sel.data_ptr(), N, per, out.data_ptr() + 4)
+    _rejected("adh_l1_partial", o[0].data_ptr() + 4, o[1].data_ptr(), per, part.data_ptr())
+    _rejected("adh_mse_partial", o[0].data_ptr(), o[1].data_ptr() + 4, per, part.data_ptr())
+    _rejected("adh_axpby_strided", out.data_ptr() + 4, 8, o[0].data_ptr(), 8, 2, 8, 0.0, 1.0)
+    _rejected("adh_axpby_strided", out.data_ptr(), 4, o[0].data_ptr(), 8, 2, 8, 0.0, 1.0)                # dst_cs < C
+    assert all(torch.isnan(t).all() for t in (out, gwp, part))
+    # the scalar path at the same unaligned base is legal
+    H.call("adh_soft_blend", w.data_ptr(), o[0].data_ptr() + 4, o[1].data_ptr(), o[2].data_ptr(), N, per - 1, out.data_ptr() + 4)
+    torch.cuda.synchronize()
+    assert not torch.isnan(out[1:1 + N * (per - 1)]).any() and torch.isnan(out[0])

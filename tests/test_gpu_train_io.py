@@ -41,11 +41,7 @@ def _rejected(name, *args):
 
 # ------------------------------------------------------------------------------------------------ fog
 FOG_SHAPES = [(1, 1, 1), (2, 1, 9), (2, 9, 1), (3, 37, 5), (2, 512, 1024), (1, 1024, 2048), (1, 725, 1447)]
-# float64 part of the fog kernel (x * (1 / (W - 1)) against linspace, sqrt, exp, six more operations, the exponent's
-# condition number beta * depth <= 3 * 1.2): 64 units of 2^-53 by that count.  It cannot be measured through the fp32
-# store, where it only shows as a flipped rounding: measured 0 (every element within half an fp32 ulp), bound 64.
-FOG_F64_UNITS = 64
-
+FOG_F64_UNITS = R64.FOG_F64_UNITS     # (the bounds shared with tests/test_train_io_hostemu_cpu.py are in tests/_ref64.py)
 
 @pytest.mark.parametrize("N,Hh,Ww", FOG_SHAPES)
 def test_apply_fog(N, Hh, Ww):
@@ -92,11 +88,7 @@ def test_apply_fog_rejects():
 
 # ------------------------------------------------------------------------------------------------ PSNR
 PSNR_PER = [1, 3, 4, 5, 147, 8191, 8192, 8193, 1024 * 8192 - 4, 1024 * 8192 + 4, 3 * 2048 * 2048]
-# float64 log10 and the float64 sums: not observable through the fp32 store of the results; the sums are of at most
-# per / (1024 * 256) serial terms per thread plus a 20-level tree: 128 units of 2^-53 cover them.  measured 2 (the vector
-# and the scalar path's float64 sums of the same data differ by at most 2 units; 2^-50 = 8 is asserted below), bound 128.
-PSNR_F64_UNITS = 128
-
+PSNR_F64_UNITS = R64.PSNR_F64_UNITS
 
 def _run_psnr(pred, target, N, per, want_mse=True):
     nblk = H.value("adh_psnr_num_blocks", per)
@@ -223,11 +215,11 @@ def test_ssim_small_images_unsupported():
 
 # ------------------------------------------------------------------------------------------------ paired augmentation
 AUG_HW = [(17, 33), (1, 1), (1, 300), (300, 1), (512, 1024), (1024, 2048)]
-AUG_BC = [(0.9, 1.1), (1.1, 0.9), (1.05, 0.9), (1.0, 1.0)]
+AUG_BC = R64.AUG_BC
 
 
 def _aug_params(b, c):
-    return torch.tensor([[i & 1, (i >> 1) & 1, (i >> 2) & 1, b, c] for i in range(8)], device=DEV, dtype=torch.float32)
+    return R64.aug_params(b, c).to(DEV)
 
 
 def _run_aug(x, params, Hh, Ww):
@@ -245,29 +237,6 @@ def _run_aug(x, params, Hh, Ww):
     return _twice(run)[0]
 
 
-def _aug_bound(x, params, gabs):
-    """fp32 forward error of brightness = clamp(b x) and contrast = clamp(c x + (1 - c) mean) in either order: one
-    rounding for b x; for the contrast step the products c x and (1 - c) mean, the difference 1 - c and the sum (3 |c x| +
-    4 |(1 - c) mean| roundings, FMA or not); the mean itself: fp32 grayscale (three coefficient roundings, three
-    products, two sums: 6 EPS of mean |gray terms|), summed in float64.  The clamps are 1-Lipschitz."""
-    out = []
-    for n in range(x.shape[0]):
-        fh, fv, bfirst, b, c = [float(v) for v in params[n]]
-        img = x[n].double()
-        if fh:
-            img = img.flip(-1)
-        if fv:
-            img = img.flip(-2)
-        xin = (b * img).clamp(0, 1) if bfirst else img
-        e_in = EPS * (b * img).abs() if bfirst else torch.zeros_like(img)
-        mean = (0.2989 * xin[0] + 0.587 * xin[1] + 0.114 * xin[2]).mean()
-        e = EPS * (3 * (c * xin).abs() + 4 * abs((1 - c) * mean)) + abs(1 - c) * 6 * EPS * gabs[n] + abs(c) * e_in
-        if not bfirst:
-            e = abs(b) * e + EPS * abs(b) * (c * xin + (1 - c) * mean).clamp(0, 1)
-        out.append(e)
-    return torch.stack(out)
-
-
 # every (b, c) pair and both input ranges at the small shapes; the two full-size shapes get one case per range, not the sweep
 AUG_CASES = [(h, w, b, c, lo, hi) for (h, w) in AUG_HW[:4] for (b, c) in AUG_BC for (lo, hi) in ((0.0, 1.0), (-0.3, 1.4))] + \
     [(h, w, b, c, lo, hi) for (h, w) in AUG_HW[4:] for (b, c, lo, hi) in ((0.9, 1.1, 0.0, 1.0), (1.05, 0.9, -0.3, 1.4))]
@@ -282,7 +251,7 @@ def test_paired_augment(Hh, Ww, b, c, lo, hi):
     params = _aug_params(b, c)
     out = _run_aug(x, params, Hh, Ww)
     ref, gabs = R64.paired_augment(x, params)
-    _assert_bound(out, ref, _aug_bound(x, params, gabs), f"augment b={b} c={c} range=[{lo}, {hi}]")
+    _assert_bound(out, ref, R64.aug_bound(x, params, gabs), f"augment b={b} c={c} range=[{lo}, {hi}]")
     assert float(out.min()) >= 0.0 and float(out.max()) <= 1.0
 
 
@@ -310,12 +279,7 @@ def test_paired_augment_rejects():
 
 
 # ------------------------------------------------------------------------------------------------ multi-tensor Adam
-# powf(beta, t) of the bias corrections, in EPS relative to beta^t: measured 1, bound 4 (test_adam_bias_correction_powf
-# prints it: 0.96 at worst over t = 1..128, 1000, 10000, 100001).  It matters because 1 - beta2^t amplifies it by
-# beta2^t / (1 - beta2^t), ~1000 at t = 1: the first update is good to ~57 EPS, not to 1.
-ADAM_POW_UNITS = 4
-ADAM_KW = dict(lr=1e-3, beta1=float(np.float32(0.9)), beta2=float(np.float32(0.999)), eps=float(np.float32(1e-8)))
-
+ADAM_POW_UNITS, ADAM_KW = R64.ADAM_POW_UNITS, R64.ADAM_KW
 
 class _AdamState:
     """p / g / m / v of several tensors carved out of four NaN arenas with 16-float gaps (the last tensor starts one float

@@ -6,8 +6,9 @@
 // -DADH_HOST_EMU (the section at the end), by tests/test_ema_hostemu_cpu.py on a copy of csrc/ema.hip; with
 // -DADH_HOST_EMU_DYN_LDS on top, by tests/test_fft_loss_hostemu_cpu.py on a copy of csrc/fft_loss.hip; with
 // -DADH_HOST_EMU_STREAM on top of ADH_HOST_EMU (the last section; the cross-lane shuffle and the wave reductions are ADH_HOST_EMU's), by
-// tests/test_{bn_act,depthwise,densenet,image_io,d4,ciede2000}_hostemu_cpu.py, by tests/test_{cbam,lpips,detect}_hostemu_cpu.py and
-// tests/test_wgrad_reduce_hostemu_cpu.py on copies of their kernel files, and by tests/test_hostemu_shuffle_cpu.py on the
+// tests/test_{bn_act,depthwise,densenet,image_io,d4,ciede2000}_hostemu_cpu.py, by
+// tests/test_{cbam,lpips,detect,pointwise,train_io}_hostemu_cpu.py and tests/test_wgrad_reduce_hostemu_cpu.py on copies of their kernel
+// files (pointwise and train_io a second time with their grid caps set small by -D), and by tests/test_hostemu_shuffle_cpu.py on the
 // shuffle itself.
 #pragma once
 #include <cmath>
@@ -78,7 +79,7 @@ int adh_wgrad32_class_taps(const adh_conv_desc* d, adh_wg32_taps* tp);
 // accesses).  The counters run on over the workgroups of a launch; stream_rt.cpp clears them before the next one, and under a
 // launcher that does not (wgrad_reduce_main.cpp) they run on over the launches too, which pairs as well.  A lane whose partner
 // has left the kernel waits for ever: the tests run every driver under a timeout.  mask is 1..63 and the partner must be a
-// lane of the workgroup; the value travels bit for bit (a NaN payload, -0.0f).
+// lane of the workgroup; the value travels bit for bit (a NaN payload, -0.0f; a double as two such exchanges).
 struct emu_channel {
     std::atomic<unsigned> seq;
     uint32_t val[2];
@@ -106,6 +107,16 @@ static inline float __shfl_xor(float v, int mask, int) {
     memcpy(&b, &v, 4);
     b = emu_shfl_bits(b, mask);
     memcpy(&v, &b, 4);
+    return v;
+}
+// a double travels as two 32-bit exchanges on the pair's channel, low word first: both lanes make the same two, so the counts of
+// the channel stay in step and the 64 bits arrive bit for bit (csrc/train_io.hip's float64 butterflies)
+static inline double __shfl_xor(double v, int mask, int) {
+    uint32_t w[2];
+    memcpy(w, &v, 8);
+    w[0] = emu_shfl_bits(w[0], mask);
+    w[1] = emu_shfl_bits(w[1], mask);
+    memcpy(&v, w, 8);
     return v;
 }
 #include "../adam-dehaze_amd/csrc/wave.h"
@@ -154,5 +165,6 @@ static inline int adh_max_i(int a, int b) { return a > b ? a : b; }
 #define __builtin_amdgcn_readfirstlane(v) (v)   // csrc/d4.hip: a value its caller knows to be wave-uniform
 static inline float __fmul_rn(float a, float b) { return a * b; }   // csrc/image_io.hip: a product nothing is contracted into
 static inline int hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { memset(p, v, n); return 0; }   // csrc/detect.hip
+using std::isfinite;   // csrc/train_io.hip calls it unqualified, as device code does; <cmath> only declares std::isfinite
 #include "../adam-dehaze_amd/csrc/bn_stream.h"
 #endif

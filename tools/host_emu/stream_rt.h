@@ -1,4 +1,4 @@
-// The script interface of the streaming drivers (bn_act_main.cpp, depthwise_main.cpp, densenet_main.cpp; stream_rt.cpp holds the
+// The script interface of the streaming drivers (every *_main.cpp that includes this file; stream_rt.cpp holds the
 // runtime).  A driver is run as  <driver> in.bin out.bin  and only maps a call's numbers and buffers onto an entry point's
 // arguments; the test that wrote in.bin owns every layout.  All integers in both files are int64.
 //   in.bin  = nbuf, then per buffer: bytes, off, and the block's `bytes` bytes.  The block is a 16-byte-aligned heap allocation
