@@ -245,6 +245,9 @@ _SIGNATURES = {
     "adh_ciede2000_num_blocks": [i64],
     "adh_ciede2000": [vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp],
     "adh_d4_apply": [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, f32],
+    "adh_msssim_num_tiles": [i32, i32],
+    "adh_msssim_level_fwd": [vp, vp, vp, i32, i32, i32, i32, f64, vp, i32, vp, vp, vp, vp],
+    "adh_msssim_level_bwd": [vp, vp, vp, i32, i32, i32, i32, f64, vp, vp, vp, vp, i32],
 }
 
 # functions that return a count / size rather than a status code
@@ -253,7 +256,7 @@ _VALUE_FUNCS = {"adh_version", "adh_conv_fewout_supported", "adh_conv_fewin_supp
                 "adh_cbam_pool_num_blocks", "adh_cbam_bwd_b_num_blocks", "adh_head_blend_bwd_num_blocks",
                 "adh_reduce_num_blocks", "adh_lpips_layer_num_blocks", "adh_adam_chunk_elems", "adh_nms_words", "adh_augment_num_blocks", "adh_psnr_num_blocks", "adh_cbam_bwd_d_scratch_floats",
                 "adh_ssim_num_blocks", "adh_fft_l1_workspace_bytes", "adh_fft_l1_num_partials", "adh_dwconv_num_blocks", "adh_dwconv_wgrad_num_blocks", "adh_channel_scale_bwd_num_blocks",
-                "adh_bn_slice_stats_num_blocks", "adh_ciede2000_num_blocks"}
+                "adh_bn_slice_stats_num_blocks", "adh_ciede2000_num_blocks", "adh_msssim_num_tiles"}
 
 _ERRORS = {-1: "ADH_E_ARG (bad argument: shape / alignment / null pointer)",
            -2: "ADH_E_LAUNCH (hip kernel launch failed)",

@@ -220,6 +220,8 @@ def dehaze_batch(system: Dict, u8: torch.Tensor, panels: bool = False, self_ense
 # ---------------------------------------------------------------------------------------------------------------- ground truth
 DEMO_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp")
 SCORE_KEYS = ("psnr", "ssim", "ciede2000", "hazy_psnr", "hazy_ssim", "hazy_ciede2000")
+# what `ms_ssim=True` adds to every scored record; None for a file too small for the number
+MS_SSIM_SCORE_KEYS = ("ssim_gaussian", "ms_ssim", "hazy_ssim_gaussian", "hazy_ms_ssim")
 
 
 def pair_targets(paths: Iterable[str], target: str, exif: bool = False) -> Dict[str, Dict]:
@@ -267,29 +269,50 @@ def pair_targets(paths: Iterable[str], target: str, exif: bool = False) -> Dict[
 
 
 def score_batch(hazy: torch.Tensor, dehazed_u8: torch.Tensor, target_u8: torch.Tensor,
-                target_tags: Optional[List[int]] = None) -> List[Dict]:
+                target_tags: Optional[List[int]] = None, ms_ssim: bool = False) -> List[Dict]:
     """The six scores of every image of a chunk, all on the device with one read-back: `hazy` fp32 [n,3,H,W] (the unpacked
     input), `dehazed_u8` uint8 [n,H,W,3] (the packed output, i.e. the pixels of the written file) and `target_u8` uint8
     [n,H,W,C], both on the device.  The dehazed side is `u8_to_image` of the packed bytes, exactly v / 255, not the router's
     fp32 output: a score can be recomputed from the two files alone.  An infinite PSNR (identical images) becomes None.
-    `target_tags`: the EXIF orientation of every target, whose pixels are in file order and are turned upright here."""
+    `target_tags`: the EXIF orientation of every target, whose pixels are in file order and are turned upright here.
+    `ms_ssim`: also the four of MS_SSIM_SCORE_KEYS, the Gaussian-window SSIM and the five-level MS-SSIM of the literature
+    (metrics.ssim_gaussian_batch, metrics.ms_ssim_batch); None for images under 11 px (both) or under 176 px (MS-SSIM) on a side."""
     from .metrics import ciede2000_batch, psnr_batch, ssim_batch
     tgt = u8_to_image(target_u8)
     if target_tags is not None:
         tgt = _orient(tgt, target_tags)
+    sides = (u8_to_image(dehazed_u8), hazy)
     rows = []
-    for img in (u8_to_image(dehazed_u8), hazy):
+    for img in sides:
         rows += [psnr_batch(img, tgt), ssim_batch(img, tgt), ciede2000_batch(img, tgt)]
-    host = torch.stack(rows).double().cpu().tolist()                        # [6][n]
-    return [{k: (None if k.endswith("psnr") and host[j][i] == float("inf") else host[j][i]) for j, k in enumerate(SCORE_KEYS)}
+    keys = SCORE_KEYS
+    extra_none: List[str] = []
+    if ms_ssim:
+        from .metrics import SSIM_GAUSSIAN_WIN, ms_ssim_batch, ms_ssim_min_side, ssim_gaussian_batch
+        short = min(tgt.shape[2], tgt.shape[3])
+        for prefix, img in zip(("", "hazy_"), sides):
+            for name, fn, need in (("ssim_gaussian", ssim_gaussian_batch, SSIM_GAUSSIAN_WIN), ("ms_ssim", ms_ssim_batch, ms_ssim_min_side())):
+                if short >= need:
+                    rows.append(fn(img, tgt))
+                    keys = keys + (prefix + name,)
+                else:
+                    extra_none.append(prefix + name)
+    host = torch.stack(rows).double().cpu().tolist()                        # [6 (or up to 10)][n]
+    recs = [{k: (None if k.endswith("psnr") and host[j][i] == float("inf") else host[j][i]) for j, k in enumerate(keys)}
             for i in range(tgt.shape[0])]
+    if ms_ssim:                                                              # the four keys in one order whatever the size
+        recs = [{**{k: r[k] for k in SCORE_KEYS}, **{k: r.get(k) for k in MS_SSIM_SCORE_KEYS}} for r in recs]
+    return recs
 
 
 def summarize_scores(records: Iterable[Dict]) -> Dict:
     """`demo_scores.json`: the schema of ImageQualityMetrics.save_results twice over, {"dehazed": {category: {psnr, ssim,
     ciede2000, samples}}, "hazy": {...}}, over the scored records; the category is the routed intensity (`low_intensity`, ...)
     plus `all`.  Infinite PSNRs (None in the records) are left out of the PSNR mean and counted as `psnr_infinite`, a key that
-    appears only where there are any; a category in which every PSNR is infinite has `psnr: null`."""
+    appears only where there are any; a category in which every PSNR is infinite has `psnr: null`.  Records scored with
+    `ms_ssim` (they carry MS_SSIM_SCORE_KEYS) add `ssim_gaussian` and `ms_ssim` to every entry: the means over the records that
+    have the number; those too small for it (None) are counted as `ssim_gaussian_too_small` / `ms_ssim_too_small`, keys that
+    appear only where there are any, and a mean nobody contributes to is null."""
     scored = [r for r in records if r.get("scored")]
     out: Dict[str, Dict] = {"dehazed": {}, "hazy": {}}
     for side, prefix in (("dehazed", ""), ("hazy", "hazy_")):
@@ -303,12 +326,19 @@ def summarize_scores(records: Iterable[Dict]) -> Dict:
                      "ciede2000": sum(r[prefix + "ciede2000"] for r in rs) / len(rs), "samples": len(rs)}
             if len(finite) < len(rs):
                 entry["psnr_infinite"] = len(rs) - len(finite)
+            if any("ms_ssim" in r for r in rs):
+                for k in ("ssim_gaussian", "ms_ssim"):
+                    have = [r[prefix + k] for r in rs if r.get(prefix + k) is not None]
+                    entry[k] = sum(have) / len(have) if have else None
+                    if len(have) < len(rs):
+                        entry[k + "_too_small"] = len(rs) - len(have)
             out[side][cat] = entry
     return out
 
 
 def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: int = 4, panels: bool = False,
-                 targets: Optional[Dict[str, Dict]] = None, self_ensemble: Optional[str] = None, exif: bool = False) -> List[Dict]:
+                 targets: Optional[Dict[str, Dict]] = None, self_ensemble: Optional[str] = None, exif: bool = False,
+                 ms_ssim: bool = False) -> List[Dict]:
     """Dehaze image files through `system["router"]` (eval mode, no_grad) at their own size and write `<out_dir>/<name>.png` --
     with `panels` also `<name>_panel.png`, hazy | dehazed -- for every input `<name>.<ext>`.  Files of equal size go through
     together, `batch_size` at a time.  Returns one dict per processed file, in sorted order: `file`, `height`, `width` and the
@@ -316,7 +346,8 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
     `targets` (what `pair_targets` returns): every record also gains the fields of its entry there, and each input with a target
     of its size is scored against it -- `scored: True` and the six numbers of `score_batch`: `psnr`, `ssim`, `ciede2000` of the
     written file, `hazy_psnr`, `hazy_ssim`, `hazy_ciede2000` of the input.  A chunk's targets go to the device once and its
-    scores come back in one read.
+    scores come back in one read.  `ms_ssim` adds the four numbers of MS_SSIM_SCORE_KEYS to every scored record (None where the
+    file is too small); it needs `targets`.
     `self_ensemble` ('flip' | 'd8'): every chunk goes through the router under 4 or 8 symmetries and the outputs are averaged
     (d4.self_ensemble); every record gains `self_ensemble`: 4 | 8.
     `exif`: every file is turned upright by its EXIF orientation tag on the device (one d4_apply launch per chunk) before the
@@ -337,7 +368,10 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
         sizes, tags = {p: v[:2] for p, v in sized.items()}, {p: v[2] for p, v in sized.items()}
     else:
         sizes = {p: image_size(p) for p in paths}
+    if ms_ssim and targets is None:
+        raise ValueError("ms_ssim scores against ground truth: it needs `targets`")
     kw = {} if self_ensemble is None else {"self_ensemble": self_ensemble}     # absent options: exactly the plain calls
+    skw = {"ms_ssim": True} if ms_ssim else {}
     os.makedirs(out_dir, exist_ok=True)
     system["router"].eval()
     results = []
@@ -357,7 +391,7 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
                 tgt = _stack([load_image(extra[i]["target"]) for i in sel]).to(hazy.device)
                 whole = len(sel) == len(chunk)
                 scores = score_batch(hazy if whole else hazy.index_select(0, idx),
-                                     out if whole else out.index_select(0, idx), tgt)
+                                     out if whole else out.index_select(0, idx), tgt, **skw)
                 for i, sc in zip(sel, scores):
                     extra[i].update(scored=True, **sc)
             elif sel:
@@ -372,7 +406,8 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
                     tgt = _stack([loaded[i][0] for i in part]).to(hazy.device)
                     whole = len(part) == len(chunk)
                     scores = score_batch(hazy if whole else hazy.index_select(0, idx),
-                                         out if whole else out.index_select(0, idx), tgt, [loaded[i][1] for i in part])
+                                         out if whole else out.index_select(0, idx), tgt, [loaded[i][1] for i in part],
+                                         **skw)
                     for i, sc in zip(part, scores):
                         extra[i].update(scored=True, **sc)
             if panel is None:

@@ -1,7 +1,8 @@
 """Losses of the hot path (/root/reference training/loss.py) on the HIP kernels.
 
-`DehazingLoss` = 1.0*L1 + 0.1*content(VGG16 taps) + 0.1*LPIPS(alex) (+ lambda_ssim * (1 - SSIM) and lambda_fft * the L1
-distance of the 2-D Fourier spectra, both off by default: terms that need no pretrained weights, not in the reference);
+`DehazingLoss` = 1.0*L1 + 0.1*content(VGG16 taps) + 0.1*LPIPS(alex) (+ lambda_ssim * (1 - SSIM), lambda_fft * the L1
+distance of the 2-D Fourier spectra and lambda_msssim * (1 - MS-SSIM), all off by default: terms that need no pretrained
+weights, not in the reference);
 `JointLoss` adds 0.2*CE
 (+ 0.5 * detection, always 0 in the drivers).  Forward signatures and returned dict keys follow
 loss.py:125-162 and :179-224.  The third-party feature networks (VGG16 / LPIPS-AlexNet) are built here
@@ -149,6 +150,56 @@ def ssim_per_image(pred: torch.Tensor, target: torch.Tensor, data_range: float =
     """Differentiable per-image SSIM [N] (channel-mean grayscale, skimage defaults): the value of metrics.ssim_batch, bit
     for bit, with a gradient for `pred`; `target` gets none."""
     return _SSIMFn.apply(pred, target.detach(), data_range)
+
+
+class _MSSSIMFn(torch.autograd.Function):
+    """Per-image MS-SSIM [N] of metrics.ms_ssim_batch (the same launches, so the same bits) with the gradient for `pred` from
+    csrc/msssim.hip.  Kept for the backward: the two images, the pooled levels (float64, a third of a pixel per pixel) and the
+    [L,N,3] level values; the window statistics are recomputed."""
+
+    @staticmethod
+    def forward(ctx, pred, target, data_range, weights, want_grad):
+        from .metrics import ms_ssim_pyramid
+        out, V, beta, levels = ms_ssim_pyramid(pred, target, data_range, weights, want_grad)
+        ctx.data_range = float(data_range)
+        ctx.levels = levels
+        ctx.save_for_backward(V, beta)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0] or ctx.levels is None:
+            return None, None, None, None, None
+        V, beta = ctx.saved_tensors
+        levels, ctx.levels = ctx.levels, None
+        L, N = V.shape[0], V.shape[1]
+        # d ms_ssim[n] / d V_s = beta_s M / (3 V_s) where every factor of the plane is > 0, exactly 0 where one is not
+        pos = (V > 0).all(0, keepdim=True)
+        M = V.clamp_min(0).pow(beta).prod(0, keepdim=True)
+        d = g.to(torch.float64).reshape(1, N, 1) * beta * M / (3.0 * torch.where(pos, V, torch.ones_like(V)))
+        d = torch.where(pos, d, torch.zeros_like(d)).contiguous()
+        zero = torch.zeros((N, 3), device=V.device, dtype=torch.float64)
+        grad = None
+        for s in reversed(range(L)):
+            x, y = levels[s]
+            _, _, Hh, Ww = x.shape
+            out = torch.empty(x.shape, device=x.device, dtype=torch.float32 if s == 0 else torch.float64)
+            a, b = (d[s], zero) if s == L - 1 else (zero, d[s])
+            H.call("adh_msssim_level_bwd", x.data_ptr(), y.data_ptr(), int(x.dtype == torch.float64), N, Hh, Ww, ctx.data_range,
+                   a.data_ptr(), b.data_ptr(), H.ptr(grad), out.data_ptr(), int(s > 0))
+            grad = out
+        return grad, None, None, None, None
+
+
+def ms_ssim_per_image(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0, weights=None) -> torch.Tensor:
+    """Differentiable per-image MS-SSIM [N] (Gaussian window, per colour plane): the value of
+    metrics.ms_ssim_batch, bit for bit, with a gradient for `pred`; `target` gets none.  `weights`: 1 to 5 positive numbers
+    (default Wang's five, which need 176 px on the shorter side)."""
+    from .metrics import MS_SSIM_WEIGHTS, check_ms_ssim_weights
+    want_grad = torch.is_grad_enabled() and pred.requires_grad          # (grad mode is off inside Function.forward)
+    return _MSSSIMFn.apply(pred, target.detach(), data_range, check_ms_ssim_weights(MS_SSIM_WEIGHTS if weights is None else weights),
+                           want_grad)
 
 
 FFT_MIN, FFT_MAX = 8, 4096                                 # csrc/fft_loss.hip: each of H and W a power of two in this range
@@ -571,6 +622,19 @@ class SSIMLoss(nn.Module):
         return 1.0 - ssim_per_image(pred, target, self.data_range).mean()
 
 
+class MSSSIMLoss(nn.Module):
+    """1 - mean over the batch of the per-image MS-SSIM (ms_ssim_per_image): 0 for identical images, at most 1."""
+
+    def __init__(self, data_range=1.0, weights=None):
+        super().__init__()
+        from .metrics import MS_SSIM_WEIGHTS, check_ms_ssim_weights
+        self.data_range = data_range
+        self.weights = check_ms_ssim_weights(MS_SSIM_WEIGHTS if weights is None else weights)
+
+    def forward(self, pred, target):
+        return 1.0 - ms_ssim_per_image(pred, target, self.data_range, self.weights).mean()
+
+
 class FrequencyLoss(nn.Module):
     """L1 distance between the 2-D Fourier spectra of prediction and target (frequency_l1): 0 for identical images."""
 
@@ -586,11 +650,13 @@ class DehazingLoss(nn.Module):
     """Combined loss for image dehazing (loss.py:110-162)."""
 
     def __init__(self, lambda_l1=1.0, lambda_content=0.1, lambda_perceptual=0.1, content=True, perceptual=True,
-                 lambda_ssim=0.0, lambda_fft=0.0, fft_norm="backward"):
+                 lambda_ssim=0.0, lambda_fft=0.0, fft_norm="backward", lambda_msssim=0.0, msssim_weights=None):
         """`content` / `perceptual` = False drop the VGG16 / LPIPS terms (their pretrained weights cannot be
         downloaded here: the extractors are randomly initialised until a checkpoint is loaded).  `lambda_ssim` > 0 adds
         lambda_ssim * (1 - mean SSIM) and the key 'ssim' to the returned dict; 0 (the reference) launches nothing extra.
-        `lambda_fft` > 0 likewise adds lambda_fft * frequency_l1(pred, target, fft_norm) and the key 'fft'."""
+        `lambda_fft` > 0 likewise adds lambda_fft * frequency_l1(pred, target, fft_norm) and the key 'fft'.
+        `lambda_msssim` > 0 adds lambda_msssim * (1 - mean MS-SSIM) and the key 'ms_ssim'; `msssim_weights` (1 to 5 positive
+        numbers, default Wang's five) sets the number of levels: frames under 176 px need fewer."""
         super().__init__()
         self.lambda_l1, self.lambda_content, self.lambda_perceptual = lambda_l1, lambda_content, lambda_perceptual
         self.lambda_ssim = float(lambda_ssim)
@@ -602,6 +668,10 @@ class DehazingLoss(nn.Module):
             raise ValueError(f"lambda_fft must be >= 0, got {lambda_fft}")
         self.fft_norm = _check_fft_norm(fft_norm)
         self.fft_loss = FrequencyLoss(self.fft_norm) if self.lambda_fft > 0 else None
+        self.lambda_msssim = float(lambda_msssim)
+        if self.lambda_msssim < 0:
+            raise ValueError(f"lambda_msssim must be >= 0, got {lambda_msssim}")
+        self.msssim_loss = MSSSIMLoss(weights=msssim_weights) if self.lambda_msssim > 0 else None
         self.content_loss = ContentLoss() if content else None
         self.perceptual_loss = PerceptualLoss() if perceptual else None
 
@@ -620,6 +690,9 @@ class DehazingLoss(nn.Module):
         if self.fft_loss is not None:
             comps["fft"] = self.fft_loss(pred, target)
             total = total + self.lambda_fft * comps["fft"]
+        if self.msssim_loss is not None:
+            comps["ms_ssim"] = self.msssim_loss(pred, target)
+            total = total + self.lambda_msssim * comps["ms_ssim"]
         comps["total"] = total
         return total, comps
 
@@ -632,7 +705,7 @@ class JointLoss(nn.Module):
         self.lambda_dehazing = lambda_dehazing
         self.lambda_classification = lambda_classification
         self.lambda_detection = lambda_detection
-        self.dehazing_loss = DehazingLoss(lambda_ssim=_lambda_ssim(config), **_lambda_fft(config))
+        self.dehazing_loss = DehazingLoss(lambda_ssim=_lambda_ssim(config), **_lambda_fft(config), **_lambda_msssim(config))
 
     def forward(self, pred, target_clear, pred_intensity=None, target_intensity=None, detection_loss=None):
         dehazing_loss, comps = self.dehazing_loss(pred, target_clear)
@@ -659,10 +732,21 @@ def _lambda_fft(config) -> dict:
     return {"lambda_fft": float(sec.get("lambda_fft", 0.0)), "fft_norm": sec.get("fft_norm", "backward")}
 
 
+def _lambda_msssim(config) -> dict:
+    """`loss.lambda_msssim` and `loss.msssim_weights` of the config as DehazingLoss's keywords; nothing at all where the term
+    is off (absent in the reference's: 0), so that the loss is built exactly as before."""
+    sec = (config or {}).get("loss") or {}
+    lam = float(sec.get("lambda_msssim", 0.0))
+    if lam == 0.0:
+        return {}
+    w = sec.get("msssim_weights")
+    return {"lambda_msssim": lam, "msssim_weights": None if w is None else tuple(w)}
+
+
 def get_dehazing_loss(config):
     """loss.py:226-232."""
     return DehazingLoss(lambda_l1=1.0, lambda_content=0.1, lambda_perceptual=0.1, lambda_ssim=_lambda_ssim(config),
-                        **_lambda_fft(config))
+                        **_lambda_fft(config), **_lambda_msssim(config))
 
 
 def get_joint_loss(config):

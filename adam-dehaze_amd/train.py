@@ -232,7 +232,7 @@ def build_joint_system(config, world_size: int = 1, adam_duplicates: str = "sequ
 
 
 # the opt-in terms of DehazingLoss: the key a step reports them under (when the config turns them on) -> the epoch report's label
-_OPT_IN_TERMS = {"ssim": "1 - SSIM", "fft": "FFT L1"}
+_OPT_IN_TERMS = {"ssim": "1 - SSIM", "fft": "FFT L1", "ms_ssim": "1 - MS-SSIM"}
 
 
 def joint_train_step(system: Dict, batch: Dict) -> Dict:
@@ -254,7 +254,7 @@ def joint_train_step(system: Dict, batch: Dict) -> Dict:
         system["ema"].update(system["optimizer"])
     stats = {"loss": loss.detach(), "dehazing": comps["dehazing"].detach(),
              "classification": comps["classification"].detach()}
-    for k in _OPT_IN_TERMS:                            # loss.lambda_ssim / loss.lambda_fft > 0 only
+    for k in _OPT_IN_TERMS:                            # loss.lambda_ssim / lambda_fft / lambda_msssim > 0 only
         if k in comps["dehazing_components"]:
             stats[k] = comps["dehazing_components"][k].detach()
     return stats
@@ -294,7 +294,7 @@ def dehazing_train_step(model, criterion, optimizer, batch: Dict, level: Optiona
     if empty:
         return None
     stats = {"loss": loss.detach(), "l1": comps["l1"].detach()}
-    for k in _OPT_IN_TERMS:                            # loss.lambda_ssim / loss.lambda_fft > 0 only
+    for k in _OPT_IN_TERMS:                            # loss.lambda_ssim / lambda_fft / lambda_msssim > 0 only
         if k in comps:
             stats[k] = comps[k].detach()
     return stats
@@ -814,6 +814,12 @@ def _ciede2000_switch(config):
     return {"use_ciede2000": True} if (config.get("evaluation") or {}).get("ciede2000") else {}
 
 
+def _ms_ssim_switch(config):
+    """`evaluation.ms_ssim: true` adds the columns `ssim_gaussian` and `ms_ssim` to the image-quality results the
+    same way; the evaluated frames then need 176 px on the shorter side."""
+    return {"use_ms_ssim": True} if (config.get("evaluation") or {}).get("ms_ssim") else {}
+
+
 def _self_ensemble_mode(config):
     """`evaluation.self_ensemble: 'flip' | 'd8'` averages every evaluated output over 4 or 8 symmetries of its input (DESIGN 4.27);
     absent, None: the evaluators make exactly the calls they made before."""
@@ -844,7 +850,7 @@ def evaluate_joint_model(config, test_loader=None, steps: int = 2, use_lpips: bo
     ensemble = _self_ensemble_mode(config)
     system, _ = _joint_system_for_evaluation(config)
     dev = system["device"]
-    metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips, **_ciede2000_switch(config))
+    metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips, **_ciede2000_switch(config), **_ms_ssim_switch(config))
     test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, dev, warn="evaluate_joint_model")
 
     def routed(h):                                     # every variant of the ensemble gets logits of its own
@@ -882,7 +888,7 @@ def evaluate_baseline_models(config, test_loader=None, steps: int = 2, use_lpips
                               prefer_ema=_evaluate_ema(config))
         m.eval()
     by_label = {0: system["models"]["low"], 1: system["models"]["medium"], 2: system["models"]["high"]}
-    metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips, **_ciede2000_switch(config))
+    metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips, **_ciede2000_switch(config), **_ms_ssim_switch(config))
     test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, dev, warn="evaluate_baseline_models")
     with torch.no_grad():
         for batch in test_loader:
@@ -952,7 +958,7 @@ def run_comprehensive_evaluation(config, steps: int = 2, use_lpips: bool = True)
 
 
 def run_demo(config, input: str, output: str = "demo", panels: bool = False, target: Optional[str] = None,
-             self_ensemble: Optional[str] = None, exif: bool = False):
+             self_ensemble: Optional[str] = None, exif: bool = False, ms_ssim: bool = False):
     """main.py:152-217 of the reference loads every checkpoint and stops at a TODO (load sample hazy images, classify, dehaze
     through the router, visualise); this is that mode.  `input` is one image file or a directory whose *.png / *.jpg / *.jpeg /
     *.bmp files are taken; every image goes through the routed system at its own size (image_io.dehaze_files, `demo.batch_size`
@@ -964,7 +970,11 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
     (image_io.summarize_scores).  No LPIPS here: without pretrained weights it would score with a random extractor.
     `self_ensemble` ('flip' | 'd8'; or `demo.self_ensemble` of the config): the output is the average over 4 or 8 symmetries of
     the input (d4.self_ensemble).  `exif` (or `demo.exif_orientation: true`): every file, and every target, is turned upright by
-    its EXIF orientation tag first.  An argument given here wins over the config; with neither, every call is the plain one."""
+    its EXIF orientation tag first.  An argument given here wins over the config; with neither, every call is the plain one.
+    `ms_ssim` (or `demo.ms_ssim: true`; needs `target`): every scored record also gains `ssim_gaussian`, `ms_ssim`,
+    `hazy_ssim_gaussian` and `hazy_ms_ssim` -- the 11x11 Gaussian-window SSIM per colour channel and the five-level MS-SSIM of
+    the published tables -- the printed lines show them and `demo_scores.json` their means; a file under 176 px on
+    a side has `ms_ssim: null` (under 11 px `ssim_gaussian: null` too) and is left out of that mean."""
     import json
     from . import image_io as IO
     if _world_rank()[0] > 1:
@@ -984,7 +994,10 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
     exif = bool(exif or demo.get("exif_orientation"))
     if self_ensemble is not None and self_ensemble not in ("flip", "d8"):
         raise SystemExit(f"self-ensemble mode {self_ensemble!r}: choose 'flip' (x4) or 'd8' (x8)")
-    if target is None:                                                       # before anything is built
+    ms_ssim = bool(ms_ssim or demo.get("ms_ssim"))
+    if ms_ssim and target is None:                                           # before anything is built
+        raise SystemExit("MS-SSIM scores against ground truth: --ms-ssim (demo.ms_ssim) needs --target")
+    if target is None:
         pairs = None
     else:
         pairs = IO.pair_targets(paths, target, exif=True) if exif else IO.pair_targets(paths, target)
@@ -997,6 +1010,8 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
         options["self_ensemble"] = self_ensemble
     if exif:
         options["exif"] = True
+    if ms_ssim:
+        options["ms_ssim"] = True
     results = IO.dehaze_files(system, paths, output, batch_size=batch_size, panels=panels, **options)
     for r in results:
         print(f"{r['file']}: {r['height']}x{r['width']}  {r['routing']} routing -> {r['intensity']}  weights "
@@ -1005,6 +1020,10 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
             db = lambda v: "inf" if v is None else f"{v:.2f}"
             print(f"    against {r['target']}: PSNR {db(r['psnr'])} dB  SSIM {r['ssim']:.4f}  CIEDE2000 {r['ciede2000']:.3f}"
                   f"   (hazy input: {db(r['hazy_psnr'])} dB  {r['hazy_ssim']:.4f}  {r['hazy_ciede2000']:.3f})")
+            if ms_ssim:
+                f4 = lambda v: "n/a (too small)" if v is None else f"{v:.4f}"
+                print(f"    SSIM (Gaussian window) {f4(r['ssim_gaussian'])}  MS-SSIM {f4(r['ms_ssim'])}"
+                      f"   (hazy input: {f4(r['hazy_ssim_gaussian'])}  {f4(r['hazy_ms_ssim'])})")
         elif pairs is not None:
             print("    not scored: " + (r.get("reason") or "no target"))
     with open(os.path.join(output, "demo_results.json"), "w") as f:
@@ -1018,7 +1037,10 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
             m = summary[side].get("all")
             if m:
                 print(f"{side:>7}: {m['samples']} scored  PSNR " + ("inf" if m["psnr"] is None else f"{m['psnr']:.2f}")
-                      + f" dB  SSIM {m['ssim']:.4f}  CIEDE2000 {m['ciede2000']:.3f}")
+                      + f" dB  SSIM {m['ssim']:.4f}  CIEDE2000 {m['ciede2000']:.3f}"
+                      + ("" if not ms_ssim else "".join(
+                          f"  {label} " + ("n/a" if m.get(k) is None else f"{m[k]:.4f}")
+                          for k, label in (("ssim_gaussian", "SSIM (Gaussian window)"), ("ms_ssim", "MS-SSIM")))))
         print(f"{sum(1 for r in results if r.get('scored'))} of {len(results)} scored against {target} (demo_scores.json)")
     return results
 

@@ -741,6 +741,30 @@ int adh_ciede2000_num_blocks(int64_t pixels);          /* pixels = H*W of one im
 int adh_ciede2000(void* stream, const float* pred_nchw, const float* target_nchw, int N, int H, int W, int lab_input,
                   double* partial, int nblk, float* map, float* mean);
 
+/* ---- Gaussian-window SSIM and the levels of MS-SSIM (csrc/msssim.hip, whose head carries the whole definition): Wang et al.
+ * (2004) per colour plane -- the 11x11 window g (x) g, g[i] = exp(-(i-5)^2 / 4.5) normalised in float64, "valid" filtering,
+ * population covariances, C1 = (0.01 R)^2, C2 = (0.03 R)^2 -- over dense planar [N,3,H,W] batches.  in_f64 == 0: pred and target
+ * are float; in_f64 == 1: double (the pooled levels of a pyramid).  Everything behind the loads is float64.
+ *   adh_msssim_level_fwd   ssim[n*3+c] = mean of l cs, cs[n*3+c] = mean of cs over the (H-10)(W-10) windows of plane (n, c), both
+ *                          double[N*3], by a fixed-order two-stage reduction without atomics: bit-reproducible, and the values of
+ *                          image i do not depend on N.  partial: double[N*3*ntiles*2] workspace, ntiles = adh_msssim_num_tiles(H, W).
+ *                          pool_pred / pool_target: both NULL, or double[N*3*(H/2)*(W/2)] that receive the 2x2 means with stride 2
+ *                          of pred / target (the last row / column of an odd side is dropped): the next level.
+ *   adh_msssim_level_bwd   g_out[n][c][p] = d(a[n*3+c] ssim[n*3+c] + b[n*3+c] cs[n*3+c]) / d pred[n][c][p], plus, where g_coarse
+ *                          (double[N*3*(H/2)*(W/2)], the gradient with respect to the pooled pred) is not NULL, a quarter of
+ *                          g_coarse at the pixel's 2x2 block.  coef_a, coef_b: double[N*3] on the device.  g_out: float (out_f64
+ *                          == 0) or double (== 1) [N*3*H*W], every element written once, no atomics; a plane whose a and b are
+ *                          both 0 gets the pool adjoint alone, exact zeros without g_coarse.  The statistics are recomputed,
+ *                          nothing is saved by the forward.  No gradient for target.
+ * ADH_E_ARG (nothing is launched): a null pointer other than the optional ones, only one of the pool pointers, N outside
+ * [1, 65535], a flag other than 0 or 1, data_range <= 0, a wrong ntiles, pooled outputs that overlap an input or each other, a
+ * g_out that overlaps pred, target or g_coarse.  ADH_E_UNSUPPORTED: H or W < 11. */
+int adh_msssim_num_tiles(int H, int W);
+int adh_msssim_level_fwd(void* stream, const void* pred, const void* target, int in_f64, int N, int H, int W, double data_range,
+                         double* partial, int ntiles, double* ssim, double* cs, double* pool_pred, double* pool_target);
+int adh_msssim_level_bwd(void* stream, const void* pred, const void* target, int in_f64, int N, int H, int W, double data_range,
+                         const double* coef_a, const double* coef_b, const double* g_coarse, void* g_out, int out_f64);
+
 /* ---- the symmetries of the square (csrc/d4.hip): flips and 90-degree rotations of a dense fp32 [N,C,H,W] batch, which are also
  * the eight EXIF orientations.  dst is dense [N,C,Hd,Wd] with (Hd,Wd) = transpose ? (W,H) : (H,W), and
  *   v(n,c,y',x') = src[n,c,y,x],  u = bit1 ? Hd-1-y' : y',  w = bit0 ? Wd-1-x' : x',  (y,x) = transpose ? (w,u) : (u,w)

@@ -8,6 +8,7 @@ the hot path run on the HIP engine; dataset preprocessing is outside this build'
     torchrun --nproc-per-node 8 main.py --mode train_joint        # data-parallel over RCCL
     python main.py --mode demo --input DIR --output OUT --panels   # dehaze image files at their own size
     python main.py --mode demo --input HAZY --target CLEAR         # ... and score them: PSNR, SSIM, CIEDE2000 per file
+    python main.py --mode demo --input HAZY --target CLEAR --ms-ssim   # ... plus Gaussian-window SSIM and MS-SSIM
 
 `--resume` is the reference's flag (main.py:50-51 parses it and never reads it); here it restores model, optimiser,
 scheduler, epoch and best-PSNR from the latest checkpoint of the mode's checkpoint directory (or from the file given
@@ -49,6 +50,9 @@ def parse_args():
     p.add_argument("--exif", action="store_true",
                    help="--mode demo --input ...: turn every file (and every --target file) upright by its EXIF orientation "
                         "tag first; same as demo.exif_orientation: true in the config")
+    p.add_argument("--ms-ssim", dest="ms_ssim", action="store_true",
+                   help="--mode demo --input ... --target ...: also score the 11x11 Gaussian-window SSIM per colour channel and "
+                        "the five-level MS-SSIM of the published tables; same as demo.ms_ssim: true in the config")
     return p.parse_args()
 
 
@@ -70,6 +74,9 @@ def main():
     if (args.self_ensemble or args.exif) and not (args.mode == "demo" and args.input):
         raise SystemExit("--self-ensemble and --exif need --mode demo --input DIR_OR_FILE: they are options of dehazing image "
                          "files.")
+    if args.ms_ssim and not args.target:
+        raise SystemExit("--ms-ssim needs --mode demo --input DIR_OR_FILE --target DIR_OR_FILE: MS-SSIM is a score against "
+                         "the ground truth.")
     with open(args.config) as f:
         config = yaml.safe_load(f)
     if args.data_dir:   # main.py:66-69
@@ -164,6 +171,8 @@ def main():
             options["self_ensemble"] = args.self_ensemble
         if args.exif:
             options["exif"] = True
+        if args.ms_ssim:
+            options["ms_ssim"] = True
         T.run_demo(config, args.input, args.output, args.panels, **options)
     elif args.mode == "demo":
         # without --input: one synthetic batch through the router

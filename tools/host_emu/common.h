@@ -8,7 +8,8 @@
 // -DADH_HOST_EMU_STREAM on top of ADH_HOST_EMU (the last section; the cross-lane shuffle and the wave reductions are ADH_HOST_EMU's), by
 // tests/test_{bn_act,depthwise,densenet,image_io,d4,ciede2000}_hostemu_cpu.py, by
 // tests/test_{cbam,lpips,detect,pointwise,train_io}_hostemu_cpu.py and tests/test_wgrad_reduce_hostemu_cpu.py on copies of their kernel
-// files (pointwise and train_io a second time with their grid caps set small by -D), and by tests/test_hostemu_shuffle_cpu.py on the
+// files (pointwise and train_io a second time with their grid caps set small by -D), by tests/test_msssim_hostemu_cpu.py on a copy of
+// csrc/msssim.hip (its grid.y cap set to 2 by -D, so that the plane loop runs), and by tests/test_hostemu_shuffle_cpu.py on the
 // shuffle itself.
 #pragma once
 #include <cmath>
