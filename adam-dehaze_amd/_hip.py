@@ -248,6 +248,7 @@ _SIGNATURES = {
     "adh_msssim_num_tiles": [i32, i32],
     "adh_msssim_level_fwd": [vp, vp, vp, i32, i32, i32, i32, f64, vp, i32, vp, vp, vp, vp],
     "adh_msssim_level_bwd": [vp, vp, vp, i32, i32, i32, i32, f64, vp, vp, vp, vp, i32],
+    "adh_draw_boxes": [vp, vp, i64, i64, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32],
 }
 
 # functions that return a count / size rather than a status code

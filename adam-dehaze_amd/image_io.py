@@ -338,7 +338,8 @@ def summarize_scores(records: Iterable[Dict]) -> Dict:
 
 def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: int = 4, panels: bool = False,
                  targets: Optional[Dict[str, Dict]] = None, self_ensemble: Optional[str] = None, exif: bool = False,
-                 ms_ssim: bool = False) -> List[Dict]:
+                 ms_ssim: bool = False, detector=None, detect_threshold: float = 0.5,
+                 detect_style: Optional[Dict] = None) -> List[Dict]:
     """Dehaze image files through `system["router"]` (eval mode, no_grad) at their own size and write `<out_dir>/<name>.png` --
     with `panels` also `<name>_panel.png`, hazy | dehazed -- for every input `<name>.<ext>`.  Files of equal size go through
     together, `batch_size` at a time.  Returns one dict per processed file, in sorted order: `file`, `height`, `width` and the
@@ -354,7 +355,15 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
     router sees it; files are grouped by stored size and by whether the orientation transposes, `height` / `width` are the
     upright ones, every record gains `orientation` (the tag, 1 where there is none), the written PNG is upright and carries no
     tag, panels show the upright input, and every target is turned upright by its own tag (`targets` from
-    `pair_targets(..., exif=True)`, which compares upright sizes).  Without it pixels are taken in file order, as before."""
+    `pair_targets(..., exif=True)`, which compares upright sizes).  Without it pixels are taken in file order, as before.
+    `detector` (a detection.DetectionModel on the system's device, eval mode): every chunk runs it twice, on the upright hazy
+    batch and on `u8_to_image` of the dehazed bytes the written file holds, both through the detector's own transform and
+    nothing else (no `pre_affine`: the two sides are treated alike), and keeps the detections above `detect_threshold`
+    (detection.filter_detections).  Every record gains `detections` ({"hazy": [...], "dehazed": [...]}, items {"label", "score",
+    "box": [x, y, w, h]}), `detect_counts` ({"hazy", "dehazed"}) and `detect_match` (overlay.match_detections(hazy, dehazed)), and
+    `<name>_detect.png` is written: the hazy | dehazed panel with each pane's detections drawn on the device
+    (overlay.draw_boxes on pane views of one buffer; `detect_style`: its thickness / scale / alpha) before the one copy back.
+    `<name>.png` and `<name>_panel.png` stay unannotated, byte for byte what they are without a detector."""
     if self_ensemble is not None and self_ensemble not in _d4.SELF_ENSEMBLE_MODES:
         raise ValueError(f"self_ensemble must be one of {sorted(_d4.SELF_ENSEMBLE_MODES)}, got {self_ensemble!r}")
     paths = sorted(str(p) for p in paths)
@@ -372,6 +381,10 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
         raise ValueError("ms_ssim scores against ground truth: it needs `targets`")
     kw = {} if self_ensemble is None else {"self_ensemble": self_ensemble}     # absent options: exactly the plain calls
     skw = {"ms_ssim": True} if ms_ssim else {}
+    if detector is not None:
+        from . import overlay as _ov
+        from .detection import filter_detections
+        style = dict(detect_style or {})
     os.makedirs(out_dir, exist_ok=True)
     system["router"].eval()
     results = []
@@ -380,12 +393,35 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
         if tags is not None:
             kw["tags"] = [tags[p] for p in chunk]
         extra: List[Dict] = [{} for _ in chunk]
-        if targets is None:
+        marked = None                                  # the annotated panels of the chunk, on the host
+        if targets is None and detector is None:
             out, panel, records = dehaze_batch(system, u8, panels, **kw)
         else:
             hazy, out, panel, records = _dehaze_on_device(system, u8, panels, **kw)
-            extra = [dict(targets.get(p) or {"target": None}) for p in chunk]
-            sel = [i for i, e in enumerate(extra) if e["target"] is not None and e.get("scored", True)]
+            if targets is not None:
+                extra = [dict(targets.get(p) or {"target": None}) for p in chunk]
+            if detector is not None:
+                with torch.no_grad():
+                    sides = {"hazy": filter_detections(detector(hazy), detect_threshold),
+                             "dehazed": filter_detections(detector(u8_to_image(out)), detect_threshold)}
+                items = {k: [_ov.detection_items(d) for d in v] for k, v in sides.items()}
+                w = hazy.shape[3]
+                if panel is not None:
+                    marked = panel.clone()
+                else:
+                    marked = torch.empty((hazy.shape[0], hazy.shape[2], 2 * w, 3), device=hazy.device, dtype=torch.uint8)
+                    image_to_u8(hazy, out=marked[:, :, :w])
+                    marked[:, :, w:].copy_(out)
+                # drawn from the recorded numbers, so the picture can be redrawn from the record
+                _ov.draw_boxes(marked[:, :, :w], [_ov.items_to_dets(it) for it in items["hazy"]], **style)
+                _ov.draw_boxes(marked[:, :, w:], [_ov.items_to_dets(it) for it in items["dehazed"]], **style)
+                marked = marked.cpu()
+                for i in range(len(chunk)):
+                    a, b = items["hazy"][i], items["dehazed"][i]
+                    extra[i].update(detections={"hazy": a, "dehazed": b}, detect_counts={"hazy": len(a), "dehazed": len(b)},
+                                    detect_match=_ov.match_detections(a, b))
+            extra_t = extra if targets is not None else [{"target": None} for _ in chunk]
+            sel = [i for i, e in enumerate(extra_t) if e["target"] is not None and e.get("scored", True)]
             if sel and tags is None:
                 idx = torch.tensor(sel, device=hazy.device)
                 tgt = _stack([load_image(extra[i]["target"]) for i in sel]).to(hazy.device)
@@ -420,6 +456,8 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
             save_image(os.path.join(out_dir, name + ".png"), out[i])
             if panel is not None:
                 save_image(os.path.join(out_dir, name + "_panel.png"), panel[i])
+            if marked is not None:
+                save_image(os.path.join(out_dir, name + "_detect.png"), marked[i])
             h, w = sizes[p] if tags is None else upright_size(*sizes[p], tags[p])
             results.append({"file": p, "height": h, "width": w, **rec, **({} if tags is None else {"orientation": tags[p]}),
                             **extra[i]})

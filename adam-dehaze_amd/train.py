@@ -958,7 +958,8 @@ def run_comprehensive_evaluation(config, steps: int = 2, use_lpips: bool = True)
 
 
 def run_demo(config, input: str, output: str = "demo", panels: bool = False, target: Optional[str] = None,
-             self_ensemble: Optional[str] = None, exif: bool = False, ms_ssim: bool = False):
+             self_ensemble: Optional[str] = None, exif: bool = False, ms_ssim: bool = False, detect: bool = False,
+             detect_threshold: Optional[float] = None):
     """main.py:152-217 of the reference loads every checkpoint and stops at a TODO (load sample hazy images, classify, dehaze
     through the router, visualise); this is that mode.  `input` is one image file or a directory whose *.png / *.jpg / *.jpeg /
     *.bmp files are taken; every image goes through the routed system at its own size (image_io.dehaze_files, `demo.batch_size`
@@ -974,7 +975,16 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
     `ms_ssim` (or `demo.ms_ssim: true`; needs `target`): every scored record also gains `ssim_gaussian`, `ms_ssim`,
     `hazy_ssim_gaussian` and `hazy_ms_ssim` -- the 11x11 Gaussian-window SSIM per colour channel and the five-level MS-SSIM of
     the published tables -- the printed lines show them and `demo_scores.json` their means; a file under 176 px on
-    a side has `ms_ssim: null` (under 11 px `ssim_gaussian: null` too) and is left out of that mean."""
+    a side has `ms_ssim: null` (under 11 px `ssim_gaussian: null` too) and is left out of that mean.
+    `detect` (or `demo.detect: true`): the detector of evaluate_detection (`_detector_for_evaluation`; `demo.detector` holds
+    keyword arguments of DetectionModel, e.g. min_size) runs on every upright hazy input and on every written dehazed file, and the
+    detections scoring above `detect_threshold` (or `demo.detect_threshold`; 0.5; within [0, 1]) are recorded per file
+    (`detections`, `detect_counts`, `detect_match`: image_io.dehaze_files), printed, and drawn by the HIP overlay kernel into
+    `<name>_detect.png`, the hazy | dehazed panel with both panes annotated (`demo.detect_style`: thickness, scale, alpha;
+    DESIGN 4.29).  `<output>/demo_detections.json` (overlay.summarize_detections) holds the threshold, where the detector's
+    weights came from, and per routed intensity and overall the file count, the mean detections per file on either side and the
+    summed matched / gained / lost.  Both sides go through the detector's own transform alone: the second normalisation of
+    the reference's IntegratedDetectionSystem is not applied to either, so the comparison is like for like."""
     import json
     from . import image_io as IO
     if _world_rank()[0] > 1:
@@ -997,6 +1007,16 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
     ms_ssim = bool(ms_ssim or demo.get("ms_ssim"))
     if ms_ssim and target is None:                                           # before anything is built
         raise SystemExit("MS-SSIM scores against ground truth: --ms-ssim (demo.ms_ssim) needs --target")
+    detect = bool(detect or demo.get("detect"))
+    if detect:                                                               # before anything is built
+        detect_threshold = float(detect_threshold if detect_threshold is not None else demo.get("detect_threshold", 0.5))
+        if not 0.0 <= detect_threshold <= 1.0:                               # NaN fails too
+            raise SystemExit(f"--detect-threshold {detect_threshold}: a detection score lies in [0, 1]")
+        unknown = sorted(set(demo.get("detect_style") or {}) - {"thickness", "scale", "alpha"})
+        if unknown:
+            raise SystemExit(f"demo.detect_style: unknown key(s) {', '.join(unknown)} (thickness, scale, alpha)")
+    elif detect_threshold is not None:
+        raise SystemExit("--detect-threshold needs --detect (demo.detect)")
     if target is None:
         pairs = None
     else:
@@ -1012,6 +1032,11 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
         options["exif"] = True
     if ms_ssim:
         options["ms_ssim"] = True
+    if detect:
+        detector, det_weights = _detector_for_evaluation(config, system["device"], **(demo.get("detector") or {}))
+        options.update(detector=detector, detect_threshold=detect_threshold)
+        if demo.get("detect_style"):
+            options["detect_style"] = {k: int(v) for k, v in demo["detect_style"].items()}
     results = IO.dehaze_files(system, paths, output, batch_size=batch_size, panels=panels, **options)
     for r in results:
         print(f"{r['file']}: {r['height']}x{r['width']}  {r['routing']} routing -> {r['intensity']}  weights "
@@ -1026,9 +1051,22 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
                       f"   (hazy input: {f4(r['hazy_ssim_gaussian'])}  {f4(r['hazy_ms_ssim'])})")
         elif pairs is not None:
             print("    not scored: " + (r.get("reason") or "no target"))
+        if detect:
+            c, m = r["detect_counts"], r["detect_match"]
+            print(f"    detections above {detect_threshold:g}: hazy {c['hazy']}, dehazed {c['dehazed']}  (matched {m['matched']}, "
+                  f"gained {m['gained']}, lost {m['lost']})")
     with open(os.path.join(output, "demo_results.json"), "w") as f:
         json.dump(results, f, indent=2)
     print(f"{len(results)} of {len(paths)} images dehazed into {output}/ (demo_results.json lists them)")
+    if detect:
+        from .overlay import summarize_detections
+        dsum = summarize_detections(results, detect_threshold, det_weights)
+        with open(os.path.join(output, "demo_detections.json"), "w") as f:
+            json.dump(dsum, f, indent=2)
+        a = dsum["all"]
+        if a["files"]:
+            print(f"detections per file: hazy {a['mean_hazy']:.2f}, dehazed {a['mean_dehazed']:.2f}; matched {a['matched']}, gained "
+                  f"{a['gained']}, lost {a['lost']} over {a['files']} files (demo_detections.json; *_detect.png show them)")
     if pairs is not None:
         summary = IO.summarize_scores(results)
         with open(os.path.join(output, "demo_scores.json"), "w") as f:
@@ -1045,6 +1083,34 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
     return results
 
 
+def _detector_for_evaluation(config, dev, **detector_kwargs):
+    """The detector of evaluate_detection and of `--mode demo --detect`, on `dev` in eval mode, and where its weights came from:
+    (detector, {"detector_checkpoint": path or None, "detector_random_init": bool}).  evaluation/evaluate.py:201-227: the
+    detector's own checkpoint, `detection.checkpoint_dir`/best_model.pth, when there is one; without it the detector runs on what
+    it was built with, and says so.  `detector_kwargs` go to DetectionModel (e.g. min_size; `demo.detector` of the config)."""
+    from .detection import DetectionModel, create_detection_model
+    cfg = dict(config)
+    cfg.setdefault("detection", {"model": "faster_rcnn_resnet50_fpn", "pretrained": False})
+    if detector_kwargs:
+        detector = DetectionModel(num_classes=91, model_name=cfg["detection"]["model"], pretrained=cfg["detection"]["pretrained"],
+                                  **detector_kwargs)
+    else:
+        detector = create_detection_model(cfg)
+    detector = detector.to(dev).eval()
+    weights = {"detector_checkpoint": None}
+    dck = os.path.join(str(cfg["detection"].get("checkpoint_dir", "checkpoints/detection")), "best_model.pth")
+    if os.path.exists(dck):
+        c = torch.load(dck, map_location="cpu")
+        detector.load_state_dict(c["model_state_dict"] if "model_state_dict" in c else c)
+        weights["detector_checkpoint"] = dck
+        print(f"Loaded detection model from {dck}")
+    else:
+        print(f"Detection checkpoint {dck} not found: the detector runs on its "
+              f"{'pretrained' if cfg['detection'].get('pretrained') else 'RANDOM-INIT'} weights (its detections carry no meaning then).")
+    weights["detector_random_init"] = weights["detector_checkpoint"] is None and not cfg["detection"].get("pretrained")
+    return detector, weights
+
+
 @_rank0_only
 def evaluate_detection(config, test_loader=None, steps: int = 1, score_threshold: float = 0.5, annotation_file=None):
     """Detection half of evaluation/evaluate.py:179-383 on device: the detector on the hazy frames and on the routed (dehazed)
@@ -1056,7 +1122,7 @@ def evaluate_detection(config, test_loader=None, steps: int = 1, score_threshold
     evaluate.py:346-377.  Without one the reference writes an empty annotation file into the dataset directory and then fails in
     `loadRes` on the first detection; here that case reports the detections only."""
     import json
-    from .detection import create_detection_model, create_integrated_system, filter_detections
+    from .detection import create_integrated_system, filter_detections
     from .metrics import CATEGORY_BY_LABEL, DetectionMetrics
     # evaluation/evaluate.py:201-227: the JOINT checkpoint into classifier + router + branches, and the detector's own
     # checkpoint when there is one (ADVICE r3: this used to score 'dehazed' detections with the pre-joint weights and an always
@@ -1064,20 +1130,8 @@ def evaluate_detection(config, test_loader=None, steps: int = 1, score_threshold
     system, joint_ck = _joint_system_for_evaluation(config)
     dev = system["device"]
     router = system["router"]
-    weights = {"joint_checkpoint": joint_ck, "detector_checkpoint": None}
-    cfg = dict(config)
-    cfg.setdefault("detection", {"model": "faster_rcnn_resnet50_fpn", "pretrained": False})
-    detector = create_detection_model(cfg).to(dev).eval()
-    dck = os.path.join(str(cfg["detection"].get("checkpoint_dir", "checkpoints/detection")), "best_model.pth")
-    if os.path.exists(dck):
-        c = torch.load(dck, map_location="cpu")
-        detector.load_state_dict(c["model_state_dict"] if "model_state_dict" in c else c)
-        weights["detector_checkpoint"] = dck
-        print(f"Loaded detection model from {dck}")
-    else:
-        print(f"Detection checkpoint {dck} not found: the detector runs on its "
-              f"{'pretrained' if cfg['detection'].get('pretrained') else 'RANDOM-INIT'} weights (its detections carry no meaning then).")
-    weights["detector_random_init"] = weights["detector_checkpoint"] is None and not cfg["detection"].get("pretrained")
+    detector, det_weights = _detector_for_evaluation(config, dev)
+    weights = {"joint_checkpoint": joint_ck, **det_weights}
 
     class _Routed(torch.nn.Module):        # evaluate.py:262-286 process_batch: classifier -> router
         def forward(self, images):

@@ -777,6 +777,36 @@ int adh_msssim_level_bwd(void* stream, const void* pred, const void* target, int
 int adh_d4_apply(void* stream, const float* src, int N, int C, int H, int W, int transpose, int flips, const int32_t* flip_ops,
                  float* dst, int accumulate, float scale);
 
+/* ---- detection overlays (csrc/overlay.hip): box outlines and caption tags drawn in place on the interleaved 8-bit image that
+ * adh_image_to_u8 writes, with its addressing: pixel (n, y, x) is the C bytes at img + n * image_pitch + y * row_pitch + x * C,
+ * pitches in bytes, any base alignment (one pane of a panel is a pointer offset), image_pitch not looked at when N == 1.  C is 3
+ * or 4; with C == 4 the alpha byte is never touched.  A byte of a pixel that no box covers is neither read nor written: pitch
+ * slack, the other pane and every uncovered pixel keep their bytes.  One launch covers the batch.
+ *   first   device int32[N+1]: the boxes of image n are first[n] .. first[n+1]-1; entries are clamped to [0, M] on the device
+ *   boxes   float[M][4], x1 y1 x2 y2 in pixels      colors  uint8[M][2][3]: RGB of the box, RGB of its text
+ *   text    int8_t[M][T] glyph indices; the first negative entry ends a box's caption      glyphs  uint8[G][7]: the rows of a
+ *           5 x 7 glyph, bit 4 the leftmost column
+ * After one floorf / ceilf per coordinate everything is integer arithmetic, so the bytes are reproducible exactly.
+ *   box      x_lo = clamp(floor(x1), 0, W-1), x_hi = clamp(ceil(x2) - 1, 0, W-1); y the same with H.  A box with a coordinate that
+ *            is not finite, or with x2 <= x1 or y2 <= y1, is skipped.
+ *   outline  the pixels of [x_lo..x_hi] x [y_lo..y_hi] outside [x_lo+t..x_hi-t] x [y_lo+t..y_hi-t], t = thickness; a box narrower
+ *            than 2 t is filled.
+ *   tag      len = the leading non-negative entries of the box's text row; none for len == 0 (a null text reads as T = 0).
+ *            Columns x_lo .. min(x_lo + scale (6 len + 1) - 1, W-1).  Rows y_lo - 9 scale .. y_lo - 1 where y_lo - 9 scale >= 0,
+ *            otherwise y_lo .. min(y_lo + 9 scale - 1, H-1); row0 is the first.  u = (x - x_lo - scale) / scale and
+ *            v = (y - row0 - scale) / scale are defined where both numerators are >= 0; the pixel is a glyph pixel when
+ *            k = u / 6 < len, u % 6 < 5, v < 7, text[k] < G and bit 4 - u % 6 of glyphs[text[k]][v] is set.
+ *   layers   every pixel walks its image's boxes in list order; the first box whose tag or outline holds it decides it: inside
+ *            a tag opaque, the text colour on a glyph pixel and the box colour elsewhere; on an outline
+ *            out = (alpha c + (255 - alpha) old + 127) / 255 per channel, in integers.  Sort by descending score to have the
+ *            strongest detection on top.  The result does not depend on the launch geometry; no atomics.
+ * ADH_E_ARG (nothing is launched) for a null img or first; N, H or W < 1; C outside {3, 4}; row_pitch < W * C; image_pitch <
+ * H * row_pitch when N > 1; thickness < 1, scale < 1, alpha outside 0..255; M, T or G < 0; M > 0 with a null boxes or colors;
+ * T > 0 and G > 0 with a null text or glyphs.  M == 0 is a success without a launch. */
+int adh_draw_boxes(void* stream, uint8_t* img, int64_t row_pitch, int64_t image_pitch, int N, int H, int W, int C,
+                   const int32_t* first, int M, const float* boxes, const uint8_t* colors, const void* text, int T,
+                   const uint8_t* glyphs, int G, int thickness, int scale, int alpha);
+
 #ifdef __cplusplus
 }
 #endif

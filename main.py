@@ -9,6 +9,7 @@ the hot path run on the HIP engine; dataset preprocessing is outside this build'
     python main.py --mode demo --input DIR --output OUT --panels   # dehaze image files at their own size
     python main.py --mode demo --input HAZY --target CLEAR         # ... and score them: PSNR, SSIM, CIEDE2000 per file
     python main.py --mode demo --input HAZY --target CLEAR --ms-ssim   # ... plus Gaussian-window SSIM and MS-SSIM
+    python main.py --mode demo --input DIR --detect                # ... detect on hazy and dehazed, boxes drawn on the device
 
 `--resume` is the reference's flag (main.py:50-51 parses it and never reads it); here it restores model, optimiser,
 scheduler, epoch and best-PSNR from the latest checkpoint of the mode's checkpoint directory (or from the file given
@@ -53,6 +54,12 @@ def parse_args():
     p.add_argument("--ms-ssim", dest="ms_ssim", action="store_true",
                    help="--mode demo --input ... --target ...: also score the 11x11 Gaussian-window SSIM per colour channel and "
                         "the five-level MS-SSIM of the published tables; same as demo.ms_ssim: true in the config")
+    p.add_argument("--detect", action="store_true",
+                   help="--mode demo --input ...: run the detector on every hazy input and dehazed output, record and compare "
+                        "the detections, and write <name>_detect.png (both panes annotated) and demo_detections.json; same as "
+                        "demo.detect: true in the config")
+    p.add_argument("--detect-threshold", dest="detect_threshold", type=float, default=None,
+                   help="--detect: keep detections scoring above this (0..1; demo.detect_threshold, 0.5)")
     return p.parse_args()
 
 
@@ -74,6 +81,9 @@ def main():
     if (args.self_ensemble or args.exif) and not (args.mode == "demo" and args.input):
         raise SystemExit("--self-ensemble and --exif need --mode demo --input DIR_OR_FILE: they are options of dehazing image "
                          "files.")
+    if (args.detect or args.detect_threshold is not None) and not (args.mode == "demo" and args.input):
+        raise SystemExit("--detect and --detect-threshold need --mode demo --input DIR_OR_FILE: they are options of dehazing "
+                         "image files.")
     if args.ms_ssim and not args.target:
         raise SystemExit("--ms-ssim needs --mode demo --input DIR_OR_FILE --target DIR_OR_FILE: MS-SSIM is a score against "
                          "the ground truth.")
@@ -173,6 +183,10 @@ def main():
             options["exif"] = True
         if args.ms_ssim:
             options["ms_ssim"] = True
+        if args.detect:
+            options["detect"] = True
+        if args.detect_threshold is not None:
+            options["detect_threshold"] = args.detect_threshold
         T.run_demo(config, args.input, args.output, args.panels, **options)
     elif args.mode == "demo":
         # without --input: one synthetic batch through the router

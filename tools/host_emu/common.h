@@ -9,8 +9,9 @@
 // tests/test_{bn_act,depthwise,densenet,image_io,d4,ciede2000}_hostemu_cpu.py, by
 // tests/test_{cbam,lpips,detect,pointwise,train_io}_hostemu_cpu.py and tests/test_wgrad_reduce_hostemu_cpu.py on copies of their kernel
 // files (pointwise and train_io a second time with their grid caps set small by -D), by tests/test_msssim_hostemu_cpu.py on a copy of
-// csrc/msssim.hip (its grid.y cap set to 2 by -D, so that the plane loop runs), and by tests/test_hostemu_shuffle_cpu.py on the
-// shuffle itself.
+// csrc/msssim.hip (its grid.y cap set to 2 by -D, so that the plane loop runs), by tests/test_overlay_hostemu_cpu.py on a copy of
+// csrc/overlay.hip (its grid cap set to 2 by -D; the wave vote __ballot is built on the shuffle), and by
+// tests/test_hostemu_shuffle_cpu.py on the shuffle itself.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -167,5 +168,17 @@ static inline int adh_max_i(int a, int b) { return a > b ? a : b; }
 static inline float __fmul_rn(float a, float b) { return a * b; }   // csrc/image_io.hip: a product nothing is contracted into
 static inline int hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { memset(p, v, n); return 0; }   // csrc/detect.hip
 using std::isfinite;   // csrc/train_io.hip calls it unqualified, as device code does; <cmath> only declares std::isfinite
+// csrc/overlay.hip: the wave's vote as a 64-bit mask, bit l = lane l's predicate, here an OR butterfly of two 32-bit halves over
+// the shuffle above; every lane of a whole 64-lane wave must call it, as on the device.  And the population count.
+static inline unsigned long long __ballot(int pred) {
+    const unsigned l = threadIdx.x & 63;
+    unsigned lo = (pred && l < 32) ? 1u << l : 0u, hi = (pred && l >= 32) ? 1u << (l - 32) : 0u;
+    for (int o = 32; o > 0; o >>= 1) {
+        lo |= __shfl_xor(lo, o, 64);
+        hi |= __shfl_xor(hi, o, 64);
+    }
+    return ((unsigned long long)hi << 32) | lo;
+}
+static inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
 #include "../adam-dehaze_amd/csrc/bn_stream.h"
 #endif
