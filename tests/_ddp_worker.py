@@ -60,6 +60,9 @@ def main():
         if step == 0:   # the ReLU masks this rank's kernels used, for the kink-matched oracle of the parent test
             rec["masks"] = {k: (E.RELU_CAPTURE[id(p)] > 0).permute(0, 3, 1, 2).cpu() for k, p in model.named_parameters()
                             if id(p) in E.RELU_CAPTURE}
+            # ... and the post-activation values they were taken from (tests/_util.py kink_audit: gap_dev)
+            rec["post"] = {k: E.RELU_CAPTURE[id(p)].detach().permute(0, 3, 1, 2).cpu() for k, p in model.named_parameters()
+                           if id(p) in E.RELU_CAPTURE}
             E.RELU_CAPTURE = None
             # ... and the arg-max positions of its attention blocks (the network's other kinks: one flipped arg-max moves the
             # gradients behind the block by 1e-3 .. 1e-2, tests/_util.py kink_matched.cbam_indices)

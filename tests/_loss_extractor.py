@@ -92,12 +92,15 @@ def alex_features(x, sd):
     return R._alex_taps(((2 * x - 1) - shift) / scale, sd, "loss_fn.net.")
 
 
-def run_forced(fn, masks, pools):
-    """fn() with the listed ReLUs and max-pools of the oracle forced to `masks` / `pools`."""
+def run_forced(fn, masks, pools, audit=None):
+    """fn() with the listed ReLUs and max-pools of the oracle forced to `masks` / `pools`; `audit`: the KinkAudit
+    (tests/_util.py kink_audit) of these very masks and choices: a forced key it did not audit is an error."""
+    if audit is not None:
+        audit.covers(masks, pools=pools)
     old = R.POOL_INDICES
     R.POOL_INDICES = pools
     try:
-        return oracle_with_masks(fn, masks)
+        return oracle_with_masks(fn, masks, audit=audit)
     finally:
         R.POOL_INDICES = old
 

@@ -107,6 +107,10 @@ def state_dict(name, seed=0):
 
 
 # ---------------------------------------------------------------------------------------------------------------- forward
+# test hook of the kink audit (tests/_util.py: kink_recording): RECORD(conv weight key, pre-activation) at every ReLU / ReLU6
+RECORD = None
+
+
 def _act(x, a):
     return {"RE": F.relu, "RE6": F.relu6, "HS": F.hardswish, None: lambda v: v}[a](x)
 
@@ -114,7 +118,8 @@ def _act(x, a):
 def features(x, sd, name, training, masks=None):
     """Backbone features [N, feature_dim] (train-mode BN updates the running statistics in sd, as nn.BatchNorm2d does).
     masks: {conv weight key: bool [N, C, H, W]} -- the ReLU / ReLU6 derivative masks another implementation used, replayed
-    as this graph's derivative at those layers (values unchanged), so both differentiate the same piece of the network."""
+    as this graph's derivative at those layers (values unchanged), so both differentiate the same piece of the network; the
+    ReLU between a squeeze-excite block's two 1x1 convolutions goes under its fc1.weight key."""
     v3 = name != "mobilenet_v2"
     eps, mom = (1e-3, 0.01) if v3 else (1e-5, 0.1)
 
@@ -127,6 +132,8 @@ def features(x, sd, name, training, masks=None):
         if training:
             sd[p + ".1.num_batches_tracked"] += 1
         z = bn(h, p + ".1")
+        if RECORD is not None and a in ("RE", "RE6"):
+            RECORD(p + ".0.weight", z)
         m = masks.get(p + ".0.weight") if masks is not None else None
         if m is not None and a in ("RE", "RE6"):
             return _act(z, a).detach() + (z - z.detach()) * m.to(z.dtype)
@@ -166,7 +173,11 @@ def features(x, sd, name, training, masks=None):
             if se:
                 p = q + str(j)
                 sc = F.adaptive_avg_pool2d(o, 1)
-                sc = F.relu(F.conv2d(sc, sd[p + ".fc1.weight"], sd[p + ".fc1.bias"]))
+                z = F.conv2d(sc, sd[p + ".fc1.weight"], sd[p + ".fc1.bias"])
+                if RECORD is not None:
+                    RECORD(p + ".fc1.weight", z)
+                m = masks.get(p + ".fc1.weight") if masks is not None else None
+                sc = F.relu(z) if m is None else F.relu(z).detach() + (z - z.detach()) * m.to(z.dtype)
                 sc = F.hardsigmoid(F.conv2d(sc, sd[p + ".fc2.weight"], sd[p + ".fc2.bias"]))
                 o = o * sc
                 j += 1

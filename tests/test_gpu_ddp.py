@@ -13,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import ref_cpu as R
-from tests._util import oracle_with_masks
+from tests._util import kink_audit, kink_recording, oracle_with_masks
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,6 +37,18 @@ def _run_ranks(tmp_path, world, port_base, **extra_env):
         outs.append(o.decode(errors="replace"))
     assert all(p.returncode == 0 for p in procs), "\n".join(o[-3000:] for o in outs)
     return [torch.load(tmp_path / f"rank{r}.pt", map_location="cpu") for r in range(world)]
+
+
+def _audit(site, sd0, hazy, masks, post, cbam, path):
+    """The ReLU masks and attention arg-max positions the ranks' kernels used, about to be replayed, against what a free-running
+    float64 forward of the same batch chooses on its own (tests/_util.py kink_audit; the fp32 CPU oracle is the yardstick)."""
+    recs = []
+    for dt in (torch.float64, torch.float32):
+        sd = {k: (v.clone().to(dt) if v.is_floating_point() else v.clone()) for k, v in sd0.items()}
+        with torch.no_grad(), kink_recording() as rec:
+            R.high_forward(hazy.to(dt), sd, training=True)
+        recs.append(rec)
+    return kink_audit(site, recs[0], family="branches", masks=masks, post=post, cbam=cbam, rec32=recs[1], path=path)
 
 
 BACKENDS = [pytest.param("gloo", id="gloo-one-gpu"),
@@ -71,7 +83,9 @@ def test_two_rank_training_step_matches_shardwise_oracle(tmp_path, backend):
             loss = F.l1_loss(out, clear[2 * r:2 * r + 2])
             loss.backward()
             return loss
-        loss = oracle_with_masks(run, recs[r]["masks"], recs[r]["cbam"])      # the ReLU masks / attention arg-max positions that rank's kernels used (tests/_util.py)
+        audit = _audit(f"ddp replica-bn rank{r}", recs[0]["sd0"], hazy[2 * r:2 * r + 2], recs[r]["masks"], recs[r]["post"], recs[r]["cbam"],
+                       "direct")
+        loss = oracle_with_masks(run, recs[r]["masks"], recs[r]["cbam"], audit=audit)      # the ReLU masks / attention arg-max positions that rank's kernels used (tests/_util.py)
         assert abs(float(loss) - recs[r]["loss"]) < 1e-5
         shard_grads.append({k: sd[k].grad for k in recs[0]["grads"]})
         shard_bn.append({k: v.detach() for k, v in sd.items() if "running" in k})
@@ -121,7 +135,8 @@ def test_one_rank_rccl_rehearsal_issues_every_collective(tmp_path, sync_bn):
         loss = F.l1_loss(out, clear)
         loss.backward()
         return loss
-    loss = oracle_with_masks(run, rec["masks"], rec["cbam"])
+    audit = _audit(f"ddp one-rank sync_bn={sync_bn}", rec["sd0"], hazy, rec["masks"], rec["post"], rec["cbam"], "direct")
+    loss = oracle_with_masks(run, rec["masks"], rec["cbam"], audit=audit)
     assert abs(float(loss) - rec["loss"]) < 1e-5
     for k, g in rec["grads"].items():
         ref = sd[k].grad
@@ -156,6 +171,10 @@ def test_two_rank_sync_bn_matches_the_unsharded_reference(tmp_path, kernels, bac
     # the attention blocks' arg-max positions as the ranks' kernels took them (per image: the shards concatenate)
     cbam = {k: tuple(torch.cat([recs[r]["cbam"][k][i] for r in range(world)], dim=0) for i in range(2)) for k in recs[0]["cbam"]}
 
+    post = {k: torch.cat([recs[r]["post"][k] for r in range(world)], dim=0) for k in recs[0]["post"]}
+    # synchronised BatchNorm spans the global batch: one audit of both ranks' records against the unsharded free run
+    audit = _audit("ddp sync-bn ranks 0+1", recs[0]["sd0"], hazy, masks, post, cbam, kernels)
+
     def oracle(dtype):
         sd = {k: (v.clone().to(dtype) if v.is_floating_point() else v.clone()) for k, v in recs[0]["sd0"].items()}
         for k, v in sd.items():
@@ -168,7 +187,7 @@ def test_two_rank_sync_bn_matches_the_unsharded_reference(tmp_path, kernels, bac
             loss = F.l1_loss(out, clear.to(dtype))
             loss.backward()
             return out.detach(), loss.detach()
-        out, loss = oracle_with_masks(run, masks, cbam)
+        out, loss = oracle_with_masks(run, masks, cbam, audit=audit)
         return out, float(loss), sd
     out32, loss32, sd32 = oracle(torch.float32)
     out64, loss64, sd64 = oracle(torch.float64)

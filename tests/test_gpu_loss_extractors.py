@@ -13,7 +13,9 @@ of the fp32 CPU oracle from the float64 one along the same graph.  Forward tenso
 continuous across every kink, so they are held against the FREE-RUNNING oracle: a reference that owes nothing to the output
 under test, and a tile, row or channel tail a kernel left at zero shows.  Only the gradients, which jump at a kink, take the
 replay: the SAME ReLU masks (engine.RELU_CAPTURE) and max-pool choices (computed here from the captured pool inputs, first
-index on ties) forced on the float64 and the fp32 oracle.  The
+index on ties) forced on the float64 and the fp32 oracle -- after an audit (tests/_util.py kink_audit) of those masks and
+choices against the ones the free-running float64 run took on its own: they come from the output under test, and only
+near-kinks may differ.  The
 factor 3 covers the MFMA kernels' other summation order and F(4x4,3x3), which the project's own comparison puts at up to 3x
 the direct kernel's rounding.  Floors (tests/_loss_extractor.py), per convolution in the chain: 4e-6 for forward tensors,
 1.2e-5 (at most 3e-4) for gradients.  Every row is printed and appended to profile_out/loss_extractor_gate.txt (or to the
@@ -33,7 +35,7 @@ from adam_dehaze_amd.engine import Act, Engine
 from oracle import ref_cpu as R
 from tests import _loss_extractor as LX
 from tests._thirdparty_init import lpips_alex_sd, vgg16_sd, vgg19_sd
-from tests._util import DEV, _same_bits, _twice
+from tests._util import DEV, KinkRecord, _same_bits, _twice, kink_audit, kink_recording
 
 pytestmark = pytest.mark.gpu
 
@@ -125,6 +127,11 @@ def _kinks(module, cap, pool_sources, k, s):
         if o is not None and o.shape[1] >= k and o.shape[2] >= k:
             pools[key] = LX.pool_choice(o.permute(0, 3, 1, 2).cpu(), k, s)
     return masks, pools
+
+
+def _post(module, cap):
+    """{conv weight name: the ReLU output the kernels wrote, NCHW on the CPU}: what _kinks derives the masks from."""
+    return {name: cap[id(p)].detach().permute(0, 3, 1, 2).cpu() for name, p in module.named_parameters() if id(p) in cap}
 
 
 def _vgg_kinks(c, cap, cfg):
@@ -250,9 +257,14 @@ def test_content_loss_value_and_gradient_vs_float64(model, names, shape, entries
         v = R.content_loss(p, target.to(dt), LX.cast_sd(sd, dt), taps=taps, cfg=cfg)
         (0.37 * v).backward()
         return v.detach().reshape(1), p.grad
-    (v64, _), (v32, _) = oracle(torch.float64), oracle(torch.float32)      # the value: free-running
-    _, g64 = LX.run_forced(lambda: oracle(torch.float64), masks, pools)    # the gradient: of the piece the kernels took
-    _, g32 = LX.run_forced(lambda: oracle(torch.float32), masks, pools)
+    with kink_recording() as rec64:
+        v64, _ = oracle(torch.float64)                                     # the value: free-running
+    with kink_recording() as rec32:
+        v32, _ = oracle(torch.float32)
+    audit = kink_audit(f"content {model} {'+'.join(names)} {'x'.join(map(str, shape))}", rec64, family="extractors", masks=masks,
+                       post=_post(c, run.cap), pools=pools, rec32=rec32)
+    _, g64 = LX.run_forced(lambda: oracle(torch.float64), masks, pools, audit)    # the gradient: of the piece the kernels took
+    _, g32 = LX.run_forced(lambda: oracle(torch.float32), masks, pools, audit)
     gate = LX.Gate(f"content {model} {'+'.join(names)} {'x'.join(map(str, shape))}")
     nconv = LX.vgg_convs_up_to(cfg, taps[-1])
     gate.check("value", val.reshape(1), v32, v64, LX.fwd_floor(nconv), run.fwd)
@@ -289,9 +301,14 @@ def test_perceptual_loss_value_and_gradient_vs_float64(shape, entries, engines):
         v = R.perceptual_loss(p, target.to(dt), LX.cast_sd(sd, dt))
         (v.view(-1) * wgt.to(dt)).sum().backward()
         return v.detach(), p.grad
-    (v64, _), (v32, _) = oracle(torch.float64), oracle(torch.float32)
-    _, g64 = LX.run_forced(lambda: oracle(torch.float64), masks, pools)
-    _, g32 = LX.run_forced(lambda: oracle(torch.float32), masks, pools)
+    with kink_recording() as rec64:
+        v64, _ = oracle(torch.float64)
+    with kink_recording() as rec32:
+        v32, _ = oracle(torch.float32)
+    audit = kink_audit(f"lpips {'x'.join(map(str, shape))}", rec64, family="extractors", masks=masks, post=_post(pl, run.cap),
+                       pools=pools, rec32=rec32)
+    _, g64 = LX.run_forced(lambda: oracle(torch.float64), masks, pools, audit)
+    _, g32 = LX.run_forced(lambda: oracle(torch.float32), masks, pools, audit)
     gate = LX.Gate(f"lpips {'x'.join(map(str, shape))}")
     gate.check("value", val, v32, v64, LX.fwd_floor(5), run.fwd)
     gate.check("grad", grad, g32, g64, LX.grad_floor(5), run.bwd)
@@ -353,11 +370,15 @@ def test_extractor_conv_layer_vs_float64(Cin, Cout, k, pad, N, Hh, Ww, entries):
     def oracle(dt, mask=None):
         xr = x.to(dt).clone().requires_grad_(True)
         y = F.conv2d(xr, w.to(dt), b.to(dt), padding=pad)
+        rec = KinkRecord()
+        rec.relu["conv"] = [y.detach()]
         y = F.relu(y) if mask is None else y * mask.to(dt)
         (y * gout.to(dt)).sum().backward()
-        return y.detach(), xr.grad
-    (y64, _), (y32, _) = oracle(torch.float64), oracle(torch.float32)                  # the output: free-running ReLU
-    (_, g64), (_, g32) = oracle(torch.float64, mask), oracle(torch.float32, mask)      # the gradient: the kernel's own mask
+        return y.detach(), xr.grad, rec
+    (y64, _, rec64), (y32, _, rec32) = oracle(torch.float64), oracle(torch.float32)    # the output: free-running ReLU
+    kink_audit(f"conv {Cin}->{Cout} k{k}p{pad} {N}x{Hh}x{Ww}", rec64, family="extractors", masks={"conv": mask},
+               post={"conv": out.detach().cpu()}, rec32=rec32)      # the mask about to be replayed: near-kinks only
+    (_, g64, _), (_, g32, _) = oracle(torch.float64, mask), oracle(torch.float32, mask)      # the gradient: the kernel's own mask
     gate = LX.Gate(f"conv {Cin}->{Cout} k{k}p{pad} {N}x{Hh}x{Ww}")
     gate.check("out", out, y32, y64, LX.fwd_floor(1), run.fwd)
     gate.check("dgrad", gx, g32, g64, LX.grad_floor(1), run.bwd)

@@ -12,7 +12,7 @@ from adam_dehaze_amd import classifier as CL
 from adam_dehaze_amd import loss as L
 from oracle import ref_cpu as R
 from tests import _mobilenet_ref as MR
-from tests._util import max_abs, rel_err
+from tests._util import kink_audit, kink_recording, max_abs, rel_err
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -200,7 +200,13 @@ def _check_train_forward_backward_vs_restatement(name):
     kernels used replayed in the restatement (engine.RELU_CAPTURE): with only 24 .. 96 samples per BatchNorm channel in the
     last stages, a pre-activation that rounds to the other side of a kink in fp32 moves whole gradients by percents (fp32
     torch itself lands 4 % from fp64 on mobilenet_v2 here); with the masks matched both sides differentiate the same piece
-    of the network and the gate is 2e-2 of each gradient's scale."""
+    of the network and the gate is 2e-2 of each gradient's scale.
+
+    The replay touches the derivative only: the restatement's forward under act_masks is relu / relu6 of its own
+    pre-activation (6, not 0, above the upper kink; tests/test_kink_audit_cpu.py pins that its values are bit-equal to the
+    free run's), so logits, loss and BN buffers are held against a reference that owes nothing to the kernels' output.  The
+    masks themselves are audited against the ones float64 chose on its own before they are used (tests/_util.py kink_audit,
+    both kinks of ReLU6; the fp32 restatement's own masks are the yardstick)."""
     import adam_dehaze_amd.engine as E
     sd = MR.state_dict(name, seed=4)
     m = _model(name, sd).train()
@@ -217,14 +223,19 @@ def _check_train_forward_backward_vs_restatement(name):
         cap = E.RELU_CAPTURE
     finally:
         E.RELU_CAPTURE = old
-    masks = {}
+    masks, post = {}, {}
     for k, p in m.named_parameters():
         if id(p) in cap:
-            o = cap[id(p)][..., :p.shape[0]].permute(0, 3, 1, 2).cpu()
+            o = post[k] = cap[id(p)][..., :p.shape[0]].detach().permute(0, 3, 1, 2).cpu()
             masks[k] = ((o > 0) & (o < 6)) if name == "mobilenet_v2" else (o > 0)   # V2: ReLU6 everywhere; V3: ReLU
     assert len(masks) >= 10
+    with torch.no_grad(), kink_recording() as rec32:
+        MR.classifier_forward(hazy, {k: v.clone() for k, v in sd.items()}, name, training=True)
     sdr = _sd64(sd)
-    ref_logits, _ = MR.classifier_forward(hazy.double(), sdr, name, training=True, act_masks=masks)
+    with kink_recording() as rec64:      # (its forward values are the free run's: see the docstring)
+        ref_logits, _ = MR.classifier_forward(hazy.double(), sdr, name, training=True, act_masks=masks)
+    kink_audit(f"{name} train 4x64x96", rec64, family="mobilenet", masks=masks, post=post, rec32=rec32,
+               relu6=name == "mobilenet_v2").covers(masks)
     ref_loss = F.cross_entropy(ref_logits, labels)
     ref_loss.backward()
     assert max_abs(logits, ref_logits.detach()) < 2e-3 * max(1.0, float(ref_logits.detach().abs().max()))

@@ -14,7 +14,7 @@ from adam_dehaze_amd import loss as L
 from adam_dehaze_amd.metrics import ssim_batch
 from oracle import ref_cpu as R
 from tests import _ssim_ref64 as S64
-from tests._util import DEV, EPS, _assert_bound, _pad_untouched, _padded, _same_bits, _twice, kink_matched, oracle_with_masks
+from tests._util import DEV, EPS, _assert_bound, _pad_untouched, _padded, _same_bits, _twice, kink_audit, kink_matched, kink_recording, oracle_with_masks
 
 pytestmark = pytest.mark.gpu
 U53 = 2.0 ** -53
@@ -248,15 +248,19 @@ def test_branch_trained_through_ssim_loss_vs_float64_oracle():
         loss.backward()
         return float(loss.detach()), {k: v.grad for k, v in sd.items() if v.is_floating_point() and "running" not in k}
 
-    _, g32_free = oracle(torch.float32)
-    _, g64_free = oracle(torch.float64)
+    with kink_recording() as rec32:
+        _, g32_free = oracle(torch.float32)
+    with kink_recording() as rec64:
+        _, g64_free = oracle(torch.float64)
     m = m.to(DEV).train()
     with kink_matched(m) as km:
         out = m(hazy.to(DEV))
         loss = L.SSIMLoss()(out, clear.to(DEV))
         loss.backward()
     torch.cuda.synchronize()
-    loss64, g64 = oracle_with_masks(lambda: oracle(torch.float64), km.masks())
+    # the masks about to be replayed against the ones float64 chose on its own (tests/_util.py kink_audit)
+    audit = kink_audit("ssim branch light_b8", rec64, family="branches", masks=km.masks(), post=km.post(), rec32=rec32)
+    loss64, g64 = oracle_with_masks(lambda: oracle(torch.float64), km.masks(), audit=audit)
     assert abs(float(loss.detach()) - loss64) < 1e-3                  # BASELINE.json north_star: losses within 1e-3 fp32
     bad, seen = [], 0
     for name, p in m.named_parameters():

@@ -9,7 +9,7 @@ import torch.nn.functional as F
 import adam_dehaze_amd as A
 from adam_dehaze_amd import train as T
 from oracle import ref_cpu as R
-from tests._util import kink_matched, max_abs, oracle_with_masks, rel_err
+from tests._util import kink_audit, kink_matched, kink_recording, max_abs, oracle_with_masks, rel_err
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -84,6 +84,8 @@ def test_joint_step_gradients_kink_matched():
     err_ref = the reference arithmetic itself (fp32 CPU oracle) with the SAME masks against that float64 run -- on this
     composition the reference's own fp32 rounding is ~1e-3 on a few tensors, and kinks that cannot be replayed (CBAM
     arg-max, max-pools of the loss networks, the backbone's ReLUs) are resolved by fp32 arithmetic on both sides.
+    Before they are replayed, each branch's masks are audited against the masks a free-running float64 forward of that
+    branch chooses on its own (tests/_util.py kink_audit; one forward-only run per branch and precision).
     The table goes to gpurun_out/grad_gate_joint.txt."""
     import os
     torch.manual_seed(1)
@@ -98,7 +100,13 @@ def test_joint_step_gradients_kink_matched():
     hazy, clear, labels = R.synthetic_batch(4, 32, 32, seed=3)      # CPU-generated: the same batch on every box
     fns = {"low": R.lightweight_forward, "medium": R.medium_forward, "high": R.high_forward}
 
-    def oracle(dtype, masks=None):
+    def free_record(n, dtype):
+        sd = {k: (v.clone().to(dtype) if v.is_floating_point() else v.clone()) for k, v in sds0[n].items()}
+        with torch.no_grad(), kink_recording() as rec:
+            fns[n](hazy.to(dtype), sd, training=True)
+        return rec
+
+    def oracle(dtype, masks=None, audits=None):
         def cast(sd, grad=True):
             out = {k: (v.clone().to(dtype) if v.is_floating_point() else v.clone()) for k, v in sd.items()}
             for k, v in out.items():
@@ -111,7 +119,7 @@ def test_joint_step_gradients_kink_matched():
         for n in fns:
             def run(n=n):
                 return fns[n](hazy.to(dtype), sds[n], training=True)
-            outs[n] = oracle_with_masks(run, masks[n]) if masks is not None else run()
+            outs[n] = oracle_with_masks(run, masks[n], audit=audits[n]) if masks is not None else run()
         blended, _ = R.soft_route(outs, logits, 0.5)
         total, _ = R.joint_loss(blended, clear.to(dtype), logits, labels, cast(vgg0, False), cast(lp0, False))
         total.backward()
@@ -129,8 +137,12 @@ def test_joint_step_gradients_kink_matched():
     allm = km.masks()
     masks = {n: {k[len("models.%s." % n):]: v for k, v in allm.items() if k.startswith("models.%s." % n)} for n in fns}
     assert all(len(masks[n]) >= 5 for n in fns)
-    tot32, clf32, sds32 = oracle(torch.float32, masks)
-    tot64, clf64, sds64 = oracle(torch.float64, masks)
+    allp = km.post()
+    audits = {n: kink_audit(f"joint step {n}", free_record(n, torch.float64), family="branches", masks=masks[n],
+                            post={k[len("models.%s." % n):]: v for k, v in allp.items() if k.startswith("models.%s." % n)},
+                            rec32=free_record(n, torch.float32)) for n in fns}
+    tot32, clf32, sds32 = oracle(torch.float32, masks, audits)
+    tot64, clf64, sds64 = oracle(torch.float64, masks, audits)
     assert abs(float(total) - tot64) < 1e-4 * max(1.0, abs(tot64))
     bad, lines = [], []
 
@@ -211,7 +223,15 @@ def test_branch_training_step_vs_oracle(monkeypatch):
         loss = F.l1_loss(out, clear[keep])
         loss.backward()
         return loss
-    loss_r = oracle_with_masks(run, km.masks())
+    recs = []
+    for dt in (torch.float64, torch.float32):      # the free-running forward, for the audit of the masks about to be replayed
+        with torch.no_grad(), kink_recording() as rec:
+            R.medium_forward(hazy[keep].to(dt), {k: (v.detach().to(dt) if v.is_floating_point() else v.clone()) for k, v in sd0.items()},
+                             training=True)
+        recs.append(rec)
+    audit = kink_audit("branch step medium_b8", recs[0], family="branches", masks=km.masks(), post=km.post(), rec32=recs[1],
+                       path="direct")
+    loss_r = oracle_with_masks(run, km.masks(), audit=audit)
     assert abs(float(st["loss"]) - float(loss_r)) < 1e-5 and abs(float(st["l1"]) - float(loss_r)) < 1e-5
     names = dict(model.named_parameters())
     stable = total = 0
