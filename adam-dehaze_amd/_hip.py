@@ -249,6 +249,9 @@ _SIGNATURES = {
     "adh_msssim_level_fwd": [vp, vp, vp, i32, i32, i32, i32, f64, vp, i32, vp, vp, vp, vp],
     "adh_msssim_level_bwd": [vp, vp, vp, i32, i32, i32, i32, f64, vp, vp, vp, vp, i32],
     "adh_draw_boxes": [vp, vp, i64, i64, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32],
+    "adh_u8_resize_bilinear": [vp, vp, i64, i32, i32, i32, vp, i32, i32],
+    "adh_batch_num_blocks": [i64],
+    "adh_batch_from_u8": [vp, vp, i64, i64, i32, i32, vp, vp, i32, vp, i32, vp],
 }
 
 # functions that return a count / size rather than a status code
@@ -257,7 +260,7 @@ _VALUE_FUNCS = {"adh_version", "adh_conv_fewout_supported", "adh_conv_fewin_supp
                 "adh_cbam_pool_num_blocks", "adh_cbam_bwd_b_num_blocks", "adh_head_blend_bwd_num_blocks",
                 "adh_reduce_num_blocks", "adh_lpips_layer_num_blocks", "adh_adam_chunk_elems", "adh_nms_words", "adh_augment_num_blocks", "adh_psnr_num_blocks", "adh_cbam_bwd_d_scratch_floats",
                 "adh_ssim_num_blocks", "adh_fft_l1_workspace_bytes", "adh_fft_l1_num_partials", "adh_dwconv_num_blocks", "adh_dwconv_wgrad_num_blocks", "adh_channel_scale_bwd_num_blocks",
-                "adh_bn_slice_stats_num_blocks", "adh_ciede2000_num_blocks", "adh_msssim_num_tiles"}
+                "adh_bn_slice_stats_num_blocks", "adh_ciede2000_num_blocks", "adh_msssim_num_tiles", "adh_batch_num_blocks"}
 
 _ERRORS = {-1: "ADH_E_ARG (bad argument: shape / alignment / null pointer)",
            -2: "ADH_E_LAUNCH (hip kernel launch failed)",

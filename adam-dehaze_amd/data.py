@@ -1,15 +1,25 @@
-"""Input side of the hot path on device: the reference's synthetic fog model as one HIP kernel and a synthetic
-foggy-frame loader that never leaves the GPU.
+"""Input side of the hot path on device: the reference's synthetic fog model as one HIP kernel, a synthetic
+foggy-frame loader that never leaves the GPU, and image folders served from a device-resident 8-bit cache.
 
 /root/reference utils/helpers.py:201-265 (`apply_random_fog`) converts every image to numpy, draws (beta, A) with
 `np.random.uniform`, builds the depth map and the transmission in float64 and loops over the channels on the host.
 Here the draws stay on the host in the reference's order (so `np.random.seed(s)` reproduces its parameters), and
-`I = clip(J*t + A*(1-t))` runs in `adh_apply_fog` for the whole batch.  Dataset files (cv2 image folders,
-data/dataset.py) are out of scope; `synthetic_loader` stands in for the DataLoader with the same batch dict keys.
+`I = clip(J*t + A*(1-t))` runs in `adh_apply_fog` for the whole batch.  `synthetic_loader` stands in for the DataLoader
+with the same batch dict keys when no image folders are configured.
+
+Image folders (data/dataset.py:9-124, 233-249 of the reference): `folder_index` lists the hazy / clear pairs of a split,
+`FolderDataset` decodes every file once on host threads (Pillow), brings it to `img_size` once on the GPU
+(`adh_u8_resize_bilinear`) and keeps the split as two dense uint8 [L,H,W,3] device tensors; `FolderDataset.epoch` yields the
+batch dicts, each image batch assembled by `adh_batch_from_u8` (v / 255 and the train transform in one gather pass over 3
+bytes per pixel).  `epoch_plan` is the pure host function that decides which samples a rank sees in which order;
+`folder_loader` is what the drivers call.  There are no worker processes and no streaming loader: a split that does not fit
+in half of the free device memory is refused.
 """
 from __future__ import annotations
 
-from typing import Dict, Iterator, Optional, Sequence, Union
+import os
+from concurrent.futures import ThreadPoolExecutor
+from typing import Callable, Dict, Iterator, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -130,3 +140,221 @@ def synthetic_loader(batch_size: int, size, steps: int, seed: int = 42, rank: in
             (hazy, clear), _ = paired_augment([hazy, clear], rng=host)
         yield {"hazy": hazy, "clear": clear, "intensity": labels.to(device),
                "name": [f"synthetic_{i}" for i in range(batch_size)]}
+
+
+# ---------------------------------------------------------------------------------------------------------------- image folders
+IMAGE_SUFFIXES = (".jpg", ".png")      # data/dataset.py:37, case-sensitive
+MAX_DECODE_THREADS = 16
+
+
+class FolderIndex(list):
+    """the records of `folder_index`, plus `skipped` (hazy files without a clear file of the same name) and `split_dir`"""
+    skipped = 0
+    split_dir = ""
+
+
+def _split_dir(root: str, split: str) -> Optional[str]:
+    """the directory that holds {low,medium,high}/hazy for `split`: <root>/<split>, else <root> itself, else None"""
+    if not root:
+        return None
+    for d in (os.path.join(root, split), root):
+        if any(os.path.isdir(os.path.join(d, level, "hazy")) for level in LEVEL_NAMES):
+            return d
+    return None
+
+
+def folder_index(root: str, split: str) -> Optional[FolderIndex]:
+    """The samples of one split as records {hazy, clear, intensity, name}, or None when there are no image folders.
+
+    Layout of data/dataset.py:20-52: `<root>/<split>/{low,medium,high}/{hazy,clear}/<name>`, labels low 0, medium 1, high 2.
+    When `<root>/<split>` holds no `<level>/hazy` directory but `<root>` does, `<root>` itself is the split directory (with
+    `--data_dir D` the reference's path handling asks for `D/train/train`, and no dataset is laid out like that).  Names
+    must end in `.jpg` or `.png` (case-sensitive, the reference's rule); each level's names are sorted (the reference takes
+    `os.listdir` order, which is arbitrary).  A hazy file without a clear file of the same name is skipped and counted in
+    the result's `skipped`.  Deviation from the reference: the `dehazed` folder is neither required nor read (the reference
+    lists a sample only when hazy, clear and dehazed all exist; nothing on the path reads `dehazed`, see `synthetic_loader`).
+    None: no `<level>/hazy` directory exists under either candidate, e.g. a root that holds only `annotations/`."""
+    d = _split_dir(root, split)
+    if d is None:
+        return None
+    out = FolderIndex()
+    out.split_dir = d
+    for label, level in enumerate(LEVEL_NAMES):
+        hazy_dir, clear_dir = os.path.join(d, level, "hazy"), os.path.join(d, level, "clear")
+        if not os.path.isdir(hazy_dir):
+            continue
+        for name in sorted(os.listdir(hazy_dir)):
+            if not name.endswith(IMAGE_SUFFIXES):
+                continue
+            hazy, clear = os.path.join(hazy_dir, name), os.path.join(clear_dir, name)
+            if not os.path.isfile(hazy):
+                continue
+            if not os.path.isfile(clear):
+                out.skipped += 1
+                continue
+            out.append({"hazy": hazy, "clear": clear, "intensity": label, "name": name})
+    return out
+
+
+def epoch_plan(M: int, world: int, rank: int, batch_size: int, seed: int, epoch: int, train: bool) -> List[np.ndarray]:
+    """The batches of one epoch on one rank, as int64 arrays of sample numbers 0..M-1 of the index.  Rank r owns the samples
+    r, r + world, ...
+
+    train: the rank's shard, padded by repeating its own first samples up to ceil(M / world), in the order of
+    `np.random.RandomState(seed + epoch).permutation`; every rank so yields ceil(ceil(M / world) / batch_size) batches (the
+    gradient all-reduce is per step: a rank with one batch fewer would leave the others waiting).  Otherwise: the shard in
+    index order, no padding and no repeats, so a metric counts every file once; a rank may have one sample fewer, or none.
+    The last batch may be short (the reference's drop_last=False)."""
+    if M < 1 or world < 1 or not 0 <= rank < world or batch_size < 1:
+        raise ValueError(f"epoch_plan: M={M}, world={world}, rank={rank}, batch_size={batch_size}")
+    own = np.arange(rank, M, world, dtype=np.int64)
+    if train:
+        if own.size == 0:
+            raise ValueError(f"epoch_plan: rank {rank} of {world} has no sample of its own among {M}: train on fewer ranks")
+        own = np.resize(own, -(-M // world))
+        own = own[np.random.RandomState(seed + epoch).permutation(own.size)]
+    return [own[i:i + batch_size] for i in range(0, own.size, batch_size)]
+
+
+def batch_from_cache(cache, index: torch.Tensor, params: Optional[torch.Tensor] = None):
+    """Images `index` of a dense uint8 [M,H,W,3] device cache as float32 [N,3,H,W], each value exactly v / 255; with `params`
+    ([N,5] rows of `draw_augment_params`) the train transform of `paired_augment` is applied in the same pass.  `cache` may be
+    a sequence of caches of one shape (hazy, clear): the result is then a list, one batch per cache, from ONE upload of the
+    index and of the parameter rows, so the roles of a pair get the same samples and the same choices.  `index` is a CPU
+    int64 tensor: it is checked against 0 <= index < M here, on the host, before anything touches the device (IndexError),
+    because the kernel does not validate it; there is no entry point that takes a device index."""
+    caches = [cache] if isinstance(cache, torch.Tensor) else list(cache)
+    if not isinstance(index, torch.Tensor) or index.is_cuda or index.dtype != torch.int64 or index.dim() != 1:
+        raise TypeError("batch_from_cache: index must be a 1-D int64 tensor on the CPU")
+    c0 = caches[0]
+    for c in caches:
+        if c.dim() != 4 or c.shape[3] != 3 or c.shape != c0.shape:
+            raise ValueError(f"batch_from_cache: the caches must be [M,H,W,3] of one shape, got {[tuple(c.shape) for c in caches]}")
+    M, Hh, Ww, _ = c0.shape
+    N = index.numel()
+    if N < 1:
+        raise ValueError("batch_from_cache: empty index")
+    if int(index.min()) < 0 or int(index.max()) >= M:
+        raise IndexError(f"batch_from_cache: index out of range for a cache of {M} images: {index.tolist()}")
+    for c in caches:
+        if not c.is_cuda or c.dtype != torch.uint8 or not c.is_contiguous() or c.device != c0.device:
+            raise RuntimeError(f"adam-dehaze_amd: the cache must be a dense uint8 tensor on one cuda device, got {c.dtype} on "
+                               f"{c.device} (no CPU fallback)")
+    if params is not None and tuple(params.shape) != (N, 5):
+        raise ValueError(f"batch_from_cache: params must be [{N},5], got {tuple(params.shape)}")
+    nblk = H.value("adh_batch_num_blocks", Hh * Ww)
+    outs = []
+    with torch.cuda.device(c0.device):
+        idx = index.contiguous().to(c0.device)
+        pd = None if params is None else params.to(device=c0.device, dtype=torch.float32).contiguous()
+        for c in caches:
+            partial = None if pd is None else torch.empty(N * nblk, device=c0.device, dtype=torch.float64)
+            out = torch.empty((N, 3, Hh, Ww), device=c0.device, dtype=torch.float32)
+            H.call("adh_batch_from_u8", c.data_ptr(), Hh * Ww * 3, M, Hh, Ww, idx.data_ptr(), H.ptr(pd), N, H.ptr(partial), nblk,
+                   out.data_ptr())
+            outs.append(out)
+    return outs[0] if isinstance(cache, torch.Tensor) else outs
+
+
+def _size2(img_size) -> tuple:
+    h, w = (img_size, img_size) if isinstance(img_size, int) else img_size
+    return int(h), int(w)
+
+
+class FolderDataset:
+    """One split of an image-folder dataset, resident on `device` as 8-bit pixels: `hazy` and `clear` uint8 [L,H,W,3], `labels`
+    (int64 [L], device) and `names`, for this rank's shard of `records` (samples rank, rank + world, ... of the index).
+
+    Every file is decoded once with `image_io.load_image` on `threads` host threads (at most 16; `dataset.num_workers` in the
+    drivers), uploaded, and brought to `img_size` (int or [h, w]) by `adh_u8_resize_bilinear`, which also replicates grey and
+    drops alpha.  A file that cannot be read raises, naming the path.  A cache that would take more than half of the free
+    device memory raises: a streaming loader is not built."""
+
+    def __init__(self, records: Sequence[Dict], img_size, device, rank: int = 0, world: int = 1, threads: int = 4,
+                 split: str = "train"):
+        from .image_io import load_image
+        self.H, self.W = _size2(img_size)
+        self.device = torch.device(device)
+        self.rank, self.world, self.total = rank, world, len(records)
+        own = list(records[rank::world])
+        self.names = [r["name"] for r in own]
+        L = len(own)
+        need = 2 * L * self.H * self.W * 3
+        if self.device.type != "cuda":
+            raise RuntimeError(f"adam-dehaze_amd: the dataset cache lives on a cuda device, got {self.device} (no CPU fallback)")
+        free = torch.cuda.mem_get_info(self.device)[0]
+        if need > free // 2:
+            raise RuntimeError(f"the {split} split needs {need} bytes of device memory as an 8-bit cache ({L} pairs at "
+                               f"{self.H}x{self.W}), more than half of the {free} bytes free on {self.device}; a streaming "
+                               "loader is not built: use a smaller dataset.img_size or more ranks")
+        self.hazy = torch.empty((L, self.H, self.W, 3), dtype=torch.uint8, device=self.device)
+        self.clear = torch.empty_like(self.hazy)
+        self.labels = torch.tensor([r["intensity"] for r in own], dtype=torch.int64).to(self.device)
+
+        def decode(job):
+            try:
+                return load_image(job[2])
+            except Exception as e:
+                raise RuntimeError(f"cannot read image file {job[2]}: {e}") from e
+        jobs = [(cache, slot, r[role]) for slot, r in enumerate(own) for role, cache in (("hazy", self.hazy), ("clear", self.clear))]
+        nthreads = max(1, min(int(threads), MAX_DECODE_THREADS))
+        with ThreadPoolExecutor(nthreads) as pool, torch.cuda.device(self.device):
+            for at in range(0, len(jobs), 4 * nthreads):        # a few files per thread in flight: decoded files do not pile up
+                chunk = jobs[at:at + 4 * nthreads]
+                for (cache, slot, path), img in zip(chunk, pool.map(decode, chunk)):
+                    h, w, c = img.shape
+                    src = img.contiguous().to(self.device)
+                    H.call("adh_u8_resize_bilinear", src.data_ptr(), w * c, h, w, c, cache[slot].data_ptr(), self.H, self.W)
+        print(f"Loaded {self.total} samples for {split} split")
+        print(f"  skipped {getattr(records, 'skipped', 0)} hazy files without a clear file of the same name")
+        print(f"  device cache: {L} pairs at {self.H}x{self.W} on {self.device}, {need / 2 ** 20:.1f} MiB"
+              + (f" (rank {rank} of {world})" if world > 1 else ""))
+
+    def __len__(self):
+        return len(self.names)
+
+    def epoch(self, epoch: int, batch_size: int, seed: int, train: bool, augment: bool = True) -> Iterator[Dict]:
+        """The batch dicts of `synthetic_loader` ('hazy', 'clear' float32 [n,3,H,W]; 'intensity' int64 [n], device; 'name' file
+        names) in the order of `epoch_plan`.  train and `augment`: one `draw_augment_params` row per sample from this loader's
+        own RandomState(seed + 1000 * rank + epoch); the same device rows drive hazy and clear."""
+        if self.total == 0 or (not train and len(self) == 0):
+            return
+        rng = np.random.RandomState(seed + 1000 * self.rank + epoch)
+        for samples in epoch_plan(self.total, self.world, self.rank, batch_size, seed, epoch, train):
+            index = torch.from_numpy((samples - self.rank) // self.world)
+            params = draw_augment_params(index.numel(), rng) if train and augment else None
+            hazy, clear = batch_from_cache((self.hazy, self.clear), index, params)
+            yield {"hazy": hazy, "clear": clear, "intensity": self.labels[index.to(self.device)],
+                   "name": [self.names[i] for i in index.tolist()]}
+
+
+_CACHES: Dict[tuple, FolderDataset] = {}     # (resolved split directory, split, (h, w), device, rank, world) -> the built cache
+
+
+def folder_loader(config, split: str, device, rank: Optional[int] = None, world: Optional[int] = None) -> Optional[Callable]:
+    """`epoch -> iterable of batch dicts` over the image folders of `split` ('train' | 'val' | 'test'), or None when
+    `folder_index` finds none under `dataset.train_path` / `val_path` / `test_path` (data/dataset.py:233-241).  rank / world
+    default to the process's RANK / WORLD_SIZE.  The cache of a split is built once per process and kept, so the stages of
+    train_all and the evaluators share it.  `dataset.num_workers` is the number of decode threads."""
+    ds = config.get("dataset", {})
+    root = ds.get({"train": "train_path", "val": "val_path"}.get(split, "test_path"))
+    split_dir = _split_dir(root, split)
+    if split_dir is None:
+        return None
+    rank = int(os.environ.get("RANK", "0")) if rank is None else rank
+    world = int(os.environ.get("WORLD_SIZE", "1")) if world is None else world
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (os.path.realpath(split_dir), split, _size2(ds["img_size"]), str(device), rank, world)
+    if key not in _CACHES:
+        records = folder_index(root, split)
+        if not records:
+            raise RuntimeError(f"{records.split_dir}: the {split} split has image folders but no hazy / clear pair "
+                               f"({records.skipped} hazy files without a clear file)")
+        _CACHES[key] = FolderDataset(records, ds["img_size"], device, rank, world, threads=int(ds.get("num_workers", 4)),
+                                     split=split)
+    cache = _CACHES[key]
+    batch_size, seed, train = int(ds["batch_size"]), int(config.get("seed", 0)), split == "train"
+    augment = bool(ds.get("augmentation", True))
+    return lambda epoch=0: cache.epoch(epoch, batch_size, seed, train, augment)

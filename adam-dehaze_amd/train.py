@@ -12,7 +12,7 @@ validation loss, rank 0 reports and writes `best_model.pth` / every fifth `check
 stage plugs in closures: `train_joint_model` (score val_psnr, reports the rank-averaged train loss, leaves its synchronizer
 installed), `train_dehazing_model` (score val_psnr, level-filtered steps, uninstalls its synchronizer in a `finally`),
 `train_classifier` (score accuracy from -1; single process, no resume, reloads the best model).  Written once beside it:
-`_loader_or_synthetic` (the given loader, else `data.synthetic_loader`: image folders are out of scope),
+`_loader_or_synthetic` (the given loader, else the image folders of the split through `data.folder_loader`, else `data.synthetic_loader`),
 `_restore_training_state` (what `resume=` restores after the stage's own key check; the reference parses `--resume` and
 ignores it, main.py:50-51), `_validation_sums` for `validate_joint` / `validate_dehazing`, `_joint_system_for_evaluation`
 for the evaluators.  Checkpoints carry the reference's keys (train_joint.py:272-283, train_dehazing.py:196-203) plus
@@ -533,15 +533,35 @@ def _warn_synthetic(config, what: str, rank: int, stacklevel: int = 3):
         msg = (f"{what}: no DataLoader was supplied -- training on SYNTHETIC foggy frames generated on the GPU "
                "(data.synthetic_loader); checkpoints written by this run are trained on noise-like images.")
         if any(paths):
+            # (the wording predates data.folder_loader and is pinned by the drivers' golden transcript: the paths were looked
+            # at, and no <path>/<split>/{low,medium,high}/hazy or <path>/{low,medium,high}/hazy folder was found under them)
             msg += (f"  Dataset paths are configured ({[p for p in paths if p]}) but this build does not read image "
                     "folders (data/dataset.py needs cv2, out of scope): pass train_loader= / val_loader=.")
         warnings.warn(msg, stacklevel=stacklevel)
 
 
-def _loader_or_synthetic(loader, config, steps: int, seed_offset: int, device, epoch: int = 0, warn: Optional[str] = None):
-    """The loader choice of every driver: `loader` as it is (a callable is asked for the epoch's iterable), else `steps`
+def _folder_loader(config, split: str, device):
+    """`data.folder_loader` for this process: the train and val splits are sharded over the ranks; the test split is read whole,
+    because every driver that reads it runs on one rank (_rank0_only evaluators, the single-process classifier stage)."""
+    from .data import folder_loader
+    world, rank = (1, 0) if split == "test" else _world_rank()
+    return folder_loader(config, split, device, rank=rank, world=world)
+
+
+def _uses_synthetic(config, device, **loaders) -> bool:
+    """True when one of the splits named by the keywords (train=..., val=...) has neither a supplied loader nor image folders,
+    so `_loader_or_synthetic` will generate it."""
+    return any(loader is None and _folder_loader(config, split, device) is None for split, loader in loaders.items())
+
+
+def _loader_or_synthetic(loader, config, steps: int, seed_offset: int, device, epoch: int = 0, warn: Optional[str] = None,
+                         split: str = "train"):
+    """The loader choice of every driver: `loader` as it is (a callable is asked for the epoch's iterable); else the image
+    folders of `split` under the configured dataset path (`data.folder_loader`, its cache built once per process); else `steps`
     synthetic batches seeded `seed + seed_offset + epoch`: offset 0 and the epoch for training frames, 500000 for the fixed
     validation set, 900000 / 910000 for the test sets, whose drivers pass their name as `warn` to say so."""
+    if loader is None:
+        loader = _folder_loader(config, split, device)
     if loader is not None:
         return loader(epoch) if callable(loader) else loader
     rank = _world_rank()[1]
@@ -618,7 +638,7 @@ def train_joint_model(config, train_loader=None, val_loader=None, steps_per_epoc
     path = _resolve_resume(resume, ck_dir)
     if path is not None:
         start_epoch, best_val_psnr = resume_joint(system, path), _best_psnr_on_disk(ck_dir)
-    if train_loader is None or val_loader is None:
+    if _uses_synthetic(config, dev, train=train_loader, val=val_loader):
         _warn_synthetic(config, "train_joint_model", _world_rank()[1])
     term_totals, n = {}, 0       # the opt-in loss terms summed over the epoch's steps on this rank, for the report
 
@@ -646,7 +666,7 @@ def train_joint_model(config, train_loader=None, val_loader=None, steps_per_epoc
               f"  Val PSNR: {val['val_psnr']:.2f} dB, Val SSIM: {val['val_ssim']:.4f}")
 
     def validate():
-        return validate_joint(system, _loader_or_synthetic(val_loader, config, val_steps, 500000, dev))
+        return validate_joint(system, _loader_or_synthetic(val_loader, config, val_steps, 500000, dev, split="val"))
 
     # (unlike the branch stage, this one leaves its synchronizer installed when it returns)
     history = _run_epochs(start_epoch, epochs, train_epoch, validate, system["scheduler"], loss_key="val_loss",
@@ -693,7 +713,7 @@ def train_dehazing_model(config, intensity_level: str, train_loader=None, val_lo
         model.load_state_dict(ck["model_state_dict"])
         start_epoch = _restore_training_state(ck, optimizer, scheduler, sync, model, ema=ema)
         best_val_psnr = _best_psnr_on_disk(ck_dir)
-    if train_loader is None or val_loader is None:
+    if _uses_synthetic(config, device, train=train_loader, val=val_loader):
         _warn_synthetic(config, f"train_dehazing_model[{intensity_level}]", _world_rank()[1])
     losses, opt_in_terms = [], {k: [] for k in _OPT_IN_TERMS}
 
@@ -717,7 +737,7 @@ def train_dehazing_model(config, intensity_level: str, train_loader=None, val_lo
                 print(f"  Train {_OPT_IN_TERMS[k]}: {float(torch.stack(terms).mean()):.4f}")
 
     def validate():
-        val_batches = _loader_or_synthetic(val_loader, config, val_steps, 500000, device)
+        val_batches = _loader_or_synthetic(val_loader, config, val_steps, 500000, device, split="val")
         return validate_dehazing(model, criterion, val_batches, level, device)
 
     try:
@@ -851,7 +871,7 @@ def evaluate_joint_model(config, test_loader=None, steps: int = 2, use_lpips: bo
     system, _ = _joint_system_for_evaluation(config)
     dev = system["device"]
     metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips, **_ciede2000_switch(config), **_ms_ssim_switch(config))
-    test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, dev, warn="evaluate_joint_model")
+    test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, dev, warn="evaluate_joint_model", split="test")
 
     def routed(h):                                     # every variant of the ensemble gets logits of its own
         return system["router"](h, system["classifier"](h)[0])
@@ -889,7 +909,8 @@ def evaluate_baseline_models(config, test_loader=None, steps: int = 2, use_lpips
         m.eval()
     by_label = {0: system["models"]["low"], 1: system["models"]["medium"], 2: system["models"]["high"]}
     metrics = ImageQualityMetrics(device=dev, use_lpips=use_lpips, **_ciede2000_switch(config), **_ms_ssim_switch(config))
-    test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, dev, warn="evaluate_baseline_models")
+    test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, dev, warn="evaluate_baseline_models",
+                                       split="test")
     with torch.no_grad():
         for batch in test_loader:
             hazy, clear = batch["hazy"].to(dev), batch["clear"].to(dev)
@@ -1138,7 +1159,7 @@ def evaluate_detection(config, test_loader=None, steps: int = 1, score_threshold
             logits, _ = system["classifier"](images)
             return router(images, logits)
     integrated = create_integrated_system(_Routed(), detector)
-    test_loader = _loader_or_synthetic(test_loader, config, steps, 910000, dev, warn="evaluate_detection")
+    test_loader = _loader_or_synthetic(test_loader, config, steps, 910000, dev, warn="evaluate_detection", split="test")
     if annotation_file is None:
         annotation_file = os.path.join(str(config.get("dataset", {}).get("test_path", "")), "annotations", "instances.json")
     dm = None
@@ -1270,7 +1291,7 @@ def train_classifier(config, train_loader=None, val_loader=None, steps: int = 4,
     ck_dir = cc["checkpoint_dir"]
     os.makedirs(ck_dir, exist_ok=True)
     epochs = cc["epochs"] if epochs is None else epochs
-    if train_loader is None or val_loader is None:
+    if _uses_synthetic(config, device, train=train_loader, val=val_loader):
         _warn_synthetic(config, "train_classifier", _world_rank()[1])
     tr = {}
 
@@ -1281,7 +1302,8 @@ def train_classifier(config, train_loader=None, val_loader=None, steps: int = 4,
 
     def validate():
         model.eval()
-        val = _classifier_pass(model, _loader_or_synthetic(val_loader, config, val_steps, 500000, device), device)
+        val = _classifier_pass(model, _loader_or_synthetic(val_loader, config, val_steps, 500000, device, split="val"),
+                               device)
         return {**val, "val_acc": _accuracy(val["confusion_matrix"])}
 
     def report(epoch, train_loss, val):
@@ -1313,7 +1335,7 @@ def evaluate_classifier(model, config, test_loader=None, steps: int = 2) -> Dict
     (synthetic frames without a loader)."""
     device = torch.device(config["device"])
     model = model.to(device).eval()
-    test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, device, warn="evaluate_classifier")
+    test_loader = _loader_or_synthetic(test_loader, config, steps, 900000, device, warn="evaluate_classifier", split="test")
     res = _classifier_pass(model, test_loader, device)
     cm = res["confusion_matrix"]
     acc = _accuracy(cm)

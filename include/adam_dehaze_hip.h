@@ -724,6 +724,36 @@ int adh_u8_to_image(void* stream, const uint8_t* src, int64_t row_pitch, int64_t
 int adh_image_to_u8(void* stream, const float* src_nchw, int N, int H, int W, uint8_t* dst, int64_t row_pitch,
                     int64_t image_pitch, int C);
 
+/* ---- device-resident 8-bit dataset cache (csrc/dataset.hip): a split of an image-folder dataset kept on the device as dense
+ * uint8 [M, H, W, 3] (image m at cache + m * image_pitch, image_pitch >= H * W * 3 bytes, rows W * 3 bytes apart), built once
+ * and gathered from every step.
+ *   adh_u8_resize_bilinear   one decoded file to one slot of the cache.  The source is addressed like adh_u8_to_image's for
+ *       N == 1: pixel (y, x) is the C bytes at src + y * row_pitch + x * C, any byte alignment, C == 1 (grey, replicated),
+ *       3 (RGB) or 4 (alpha ignored); bytes outside the W * C run of a row are never read.  dst is dense uint8 [OH, OW, 3].
+ *       Geometry of cv2.resize(INTER_LINEAR) = F.interpolate(mode='bilinear', align_corners=False), no antialiasing: the
+ *       source coordinate of destination index d is max((d + 0.5) * (in / out) - 0.5, 0), evaluated in fp32 exactly as
+ *       adh_bilinear does, the upper neighbour clamped to the last row / column.  Value: fp32 interpolation of the byte values,
+ *       rint (halves to even), clamped to 0..255.  OH == H and OW == W: every weight is exactly 0 or 1 and the bytes pass
+ *       through (only the channel conversion happens).  OpenCV's own 8-bit path uses 11-bit fixed-point weights and can differ
+ *       from this by one grey level; that difference is not measured here.
+ *       ADH_E_ARG (nothing is launched) for a null pointer, H, W, OH or OW < 1, a C outside {1, 3, 4}, row_pitch < W * C.
+ *   adh_batch_from_u8   out[n] = image index[n] of the cache as fp32 planes, value (float)v / 255.0f correctly rounded as
+ *       adh_u8_to_image gives it.  params == NULL: that is all (one launch; partial may be NULL).  params = float[N,5] rows
+ *       {flip_h, flip_v, brightness_first, b, c}: the transform of adh_paired_augment applied to those planes (two launches:
+ *       the grey mean the contrast step sees as a fixed-order two-stage float64 sum without atomics, then one gather pass).
+ *       Bit-reproducible; the planes of sample n depend neither on N nor on n's place in the batch; an index may repeat, with
+ *       different params.  partial: double[N * nblk] workspace, nblk = adh_batch_num_blocks(H * W).  The cache is only read.
+ *       index[n] is NOT validated on the device: the caller guarantees 0 <= index[n] < M (data.batch_from_cache checks it on
+ *       the host before the upload).  Dword reads where cache and image_pitch are multiples of 4 (and, in the gather pass,
+ *       W % 4 == 0), 16-byte stores where out is 16-byte aligned and W % 4 == 0; bytes and floats otherwise, same values.
+ *       ADH_E_ARG (nothing is launched) for a null cache / index / out, params without partial, N outside [1, 65535], H, W or
+ *       M < 1, image_pitch < H * W * 3, or nblk other than adh_batch_num_blocks(H * W). */
+int adh_u8_resize_bilinear(void* stream, const uint8_t* src, int64_t row_pitch, int H, int W, int C, uint8_t* dst, int OH,
+                           int OW);
+int adh_batch_num_blocks(int64_t HW);
+int adh_batch_from_u8(void* stream, const uint8_t* cache, int64_t image_pitch, int64_t M, int H, int W, const int64_t* index,
+                      const float* params, int N, double* partial, int nblk, float* out_nchw);
+
 /* ---- CIEDE2000 (csrc/ciede2000.hip): the per-pixel colour difference dE00 of Sharma, Wu and Dalal (2005), kL = kC = kH = 1,
  * between two dense fp32 [N,3,H,W] batches, and its mean per image.  lab_input == 0: the planes are sRGB in [0,1] (clamped as
  * adh_image_to_u8 clamps, NaN = 0) and go through skimage's rgb2lab constants (sRGB decoding, the 0.412453... matrix, the D65

@@ -13,13 +13,13 @@ the hot path run on the HIP engine; dataset preprocessing is outside this build'
 
 `--resume` is the reference's flag (main.py:50-51 parses it and never reads it); here it restores model, optimiser,
 scheduler, epoch and best-PSNR from the latest checkpoint of the mode's checkpoint directory (or from the file given
-as its optional value).  Image folders are not read by this build (data/dataset.py needs cv2): `--data_dir` is recorded
-in the config like the reference does, and the drivers then say loudly that they train on synthetic frames.
+as its optional value).  `--data_dir D` sets the dataset paths like the reference does (D/train, D/val, D/test); the drivers
+read `<path>/<split>/{low,medium,high}/{hazy,clear}` (or `<path>/{low,medium,high}/...`) from there into a device-resident
+cache, and only when no such folders exist do they say loudly that they train on synthetic frames.
 """
 import argparse
 import os
 import random
-import warnings
 
 import numpy as np
 import torch
@@ -93,8 +93,6 @@ def main():
         config["dataset"]["train_path"] = os.path.join(args.data_dir, "train")
         config["dataset"]["val_path"] = os.path.join(args.data_dir, "val")
         config["dataset"]["test_path"] = os.path.join(args.data_dir, "test")
-        warnings.warn(f"--data_dir {args.data_dir}: this build does not read image folders (cv2 dataset code is out of "
-                      "scope); the training modes fall back to synthetic foggy frames and say so.")
     if args.device:
         config["device"] = args.device
     if args.seed:

@@ -10,7 +10,8 @@
 // tests/test_{cbam,lpips,detect,pointwise,train_io}_hostemu_cpu.py and tests/test_wgrad_reduce_hostemu_cpu.py on copies of their kernel
 // files (pointwise and train_io a second time with their grid caps set small by -D), by tests/test_msssim_hostemu_cpu.py on a copy of
 // csrc/msssim.hip (its grid.y cap set to 2 by -D, so that the plane loop runs), by tests/test_overlay_hostemu_cpu.py on a copy of
-// csrc/overlay.hip (its grid cap set to 2 by -D; the wave vote __ballot is built on the shuffle), and by
+// csrc/overlay.hip (its grid cap set to 2 by -D; the wave vote __ballot is built on the shuffle), by
+// tests/test_dataset_hostemu_cpu.py on a copy of csrc/dataset.hip (float64 butterflies in both of its batch kernels), and by
 // tests/test_hostemu_shuffle_cpu.py on the shuffle itself.
 #pragma once
 #include <cmath>

@@ -1,0 +1,21 @@
+// Runs the entry points of a host-compiled copy of csrc/dataset.hip (common.h's ADH_HOST_EMU_STREAM section: the float64
+// butterfly of the grey-mean pass runs on the emulator's __shfl_xor(double); the script format is stream_rt.h's).
+// Calls, with their integers `i` and buffers `b` in order (a buffer index of -1 is a null pointer):
+//   0 adh_u8_resize_bilinear   i: row_pitch H W C OH OW                     b: src dst
+//   1 adh_batch_num_blocks     i: HW
+//   2 adh_batch_from_u8        i: image_pitch M H W N nblk                  b: cache index params partial out
+#include "common.h"
+#include "stream_rt.h"
+
+static int64_t dispatch(const emu_call& c) {
+    switch (c.fn) {
+        case 0: return adh_u8_resize_bilinear(nullptr, c.p<uint8_t>(0), c.i[0], c.I(1), c.I(2), c.I(3), c.p<uint8_t>(1), c.I(4), c.I(5));
+        case 1: return adh_batch_num_blocks(c.i[0]);
+        case 2:
+            return adh_batch_from_u8(nullptr, c.p<uint8_t>(0), c.i[0], c.i[1], c.I(2), c.I(3), c.p<int64_t>(1), c.f(2), c.I(4),
+                                     c.p<double>(3), c.I(5), c.f(4));
+    }
+    return -1000;
+}
+
+int main(int argc, char** argv) { return emu_run_script(argc, argv, dispatch); }
