@@ -252,6 +252,7 @@ _SIGNATURES = {
     "adh_u8_resize_bilinear": [vp, vp, i64, i32, i32, i32, vp, i32, i32],
     "adh_batch_num_blocks": [i64],
     "adh_batch_from_u8": [vp, vp, i64, i64, i32, i32, vp, vp, i32, vp, i32, vp],
+    "adh_batch_window_from_u8": [vp, vp, i64, vp, vp, i32, i32, i32, vp, i32, vp],
 }
 
 # functions that return a count / size rather than a status code

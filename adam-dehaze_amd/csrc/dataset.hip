@@ -9,6 +9,13 @@
 //                           v / 255, with the flips and the ColorJitter of adh_paired_augment (csrc/train_io.hip) when a parameter
 //                           row per sample is given.  Without parameters one launch; with them two: the grey mean the contrast
 //                           step sees (fixed-order two-stage float64 sum, no atomics), then one gather pass.
+//   adh_batch_window_from_u8  the same from a flat cache of images of any sizes: sample n is the CH x CW window whose row y
+//                           starts at cache + window[n][0] + y * window[n][1] (a crop of an image at its own resolution; the host
+//                           turns image offset, width and crop origin into that pair).  Bit for bit adh_batch_from_u8 on a dense
+//                           copy of the window's bytes: the mean pass walks the flat window-pixel number in the same quads, blocks
+//                           and lanes, the gather pass is the same kernel with another row address.  A quad's 12 bytes start at
+//                           any address there: three aligned dwords, a fourth when the address is off phase, and a funnel shift
+//                           (ds_load12), where the cache starts and ends on a multiple of 4; bytes otherwise.
 //
 // The gather pass is csrc/image_io.hip's u8_to_image_kernel with a source that moves: a lane owns four neighbouring pixels of one
 // OUTPUT row, which are four neighbouring pixels of one source row whatever the flips (flip_h reverses their order inside the quad
@@ -37,6 +44,25 @@
 
 // v / 255 correctly rounded (csrc/image_io.hip's u8_unit)
 __device__ __forceinline__ float ds_unit(uint32_t v) { return (float)v / 255.0f; }
+
+// the 12 bytes at p, any address, as the three dwords an aligned read of them would give: the dword that holds p and the next two,
+// a fourth only when p is off phase, shifted together.  No misaligned dword is dereferenced; the last byte touched is that of the
+// dword holding p + 11, so the caller needs [p rounded down to 4, p + 12 rounded up to 4) readable.
+__device__ __forceinline__ void ds_load12(const uint8_t* __restrict__ p, uint32_t (&w)[3]) {
+    const unsigned s = (unsigned)((uintptr_t)p & 3);
+    const uint32_t* __restrict__ in = reinterpret_cast<const uint32_t*>(p - s);
+    uint32_t d[4];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) d[k] = in[k];
+    if (s != 0) {
+        d[3] = in[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) w[k] = (d[k] >> (8 * s)) | (d[k + 1] << (32 - 8 * s));
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) w[k] = d[k];
+    }
+}
 
 // ------------------------------------------------------------------------------------------------ resize
 // adh_bilinear's source index for align_corners false (csrc/pointwise.hip bilin_src), the same fp32 operations in the same order
@@ -150,10 +176,68 @@ __global__ __launch_bounds__(256) void batch_gray_partial_kernel(const uint8_t* 
     if (threadIdx.x == 0) partial[(int64_t)n * gridDim.x + blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
 }
 
-// AUG == false: params and partial are not looked at
-template <bool AUG>
+// The same sum over the window window[n] = {byte offset of its first pixel, row pitch}: the flat window-pixel number
+// i = y * CW + x is dealt to quads, lanes and blocks exactly as batch_gray_partial_kernel deals the pixels of a dense image, and a
+// quad's pixels are added in the same order, so the partials are those of a dense copy of the window, bit for bit.  (y, x) of a
+// lane's next quad follow from the grid's stride without a division; a quad that straddles rows takes its pixels one by one.
+__global__ __launch_bounds__(256) void window_gray_partial_kernel(const uint8_t* __restrict__ cache,
+                                                                  const int64_t* __restrict__ window,
+                                                                  const float* __restrict__ params, int CW, int64_t HW, int flags,
+                                                                  double* __restrict__ partial) {
+    const int n = blockIdx.y;
+    const float* p = params + n * 5;
+    const bool bfirst = p[2] != 0.f;
+    const float b = p[3];
+    const uint8_t* __restrict__ win = cache + window[2 * n];
+    const int64_t pitch = window[2 * n + 1];
+    const int64_t step = (int64_t)gridDim.x * 256 * DS_QUAD;
+    const int64_t dy = step / CW;
+    const int64_t dx = step - dy * CW;
+    int64_t i = (blockIdx.x * (int64_t)256 + threadIdx.x) * DS_QUAD;
+    int64_t y = i / CW;
+    int64_t x = i - y * CW;                 // 64 bits: x + dx and x + DS_QUAD pass 2^31 for a CW close to it
+    double acc = 0.0;
+    for (; i < HW; i += step) {
+        const int npx = (HW - i) < DS_QUAD ? (int)(HW - i) : DS_QUAD;
+        const uint8_t* __restrict__ in = win + y * pitch + x * 3;
+        if (npx == DS_QUAD && x + DS_QUAD <= CW && (flags & DS_WIDE_U8)) {
+            uint32_t w[3];
+            ds_load12(in, w);
+#pragma unroll
+            for (int j = 0; j < DS_QUAD; ++j) {
+                float v[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int k = j * 3 + c;
+                    v[c] = ds_unit((w[k >> 2] >> ((k & 3) * 8)) & 255u);
+                }
+                acc += (double)ds_gray(v[0], v[1], v[2], bfirst, b);
+            }
+        } else {
+            int64_t yy = y, xx = x;
+            for (int j = 0; j < npx; ++j, ++xx) {
+                while (xx >= CW) xx -= CW, ++yy;
+                const uint8_t* __restrict__ px = win + yy * pitch + xx * 3;
+                acc += (double)ds_gray(ds_unit(px[0]), ds_unit(px[1]), ds_unit(px[2]), bfirst, b);
+            }
+        }
+        y += dy, x += dx;
+        if (x >= CW) x -= CW, ++y;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    __shared__ double s[4];
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[(int64_t)n * gridDim.x + blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// AUG == false: params and partial are not looked at.  WIN == false: where[n] is the number of a dense image, image_pitch bytes
+// apart, rows W * 3 bytes apart.  WIN == true: where[n] = {byte offset of the window's first pixel, row pitch}, H x W the window,
+// image_pitch unused, and DS_WIDE_U8 means ds_load12 may be used on every whole quad.
+template <bool AUG, bool WIN>
 __global__ __launch_bounds__(256) void batch_gather_kernel(const uint8_t* __restrict__ cache, int64_t image_pitch,
-                                                           const int64_t* __restrict__ index, const float* __restrict__ params,
+                                                           const int64_t* __restrict__ where, const float* __restrict__ params,
                                                            const double* __restrict__ partial, int nblk, int H, int W,
                                                            float* __restrict__ out, int flags) {
     const int lane = threadIdx.x & 63;
@@ -177,17 +261,22 @@ __global__ __launch_bounds__(256) void batch_gather_kernel(const uint8_t* __rest
     const int64_t x = ((int64_t)blockIdx.x * 64 + lane) * DS_QUAD;
     if (x >= W) return;
     const int npx = (W - x) < DS_QUAD ? (int)(W - x) : DS_QUAD;
-    const uint8_t* __restrict__ img = cache + index[n] * image_pitch;
+    const uint8_t* __restrict__ img = WIN ? cache + where[2 * n] : cache + where[n] * image_pitch;
+    const int64_t row_pitch = WIN ? where[2 * n + 1] : (int64_t)W * 3;
     float* __restrict__ dst = out + (int64_t)n * 3 * plane;
     for (int64_t y = (int64_t)blockIdx.y * DS_ROWS + (threadIdx.x >> 6); y < H; y += (int64_t)gridDim.y * DS_ROWS) {
-        const uint8_t* __restrict__ row = img + (fv ? H - 1 - y : y) * W * 3;
+        const uint8_t* __restrict__ row = img + (fv ? H - 1 - y : y) * row_pitch;
         float v[3][DS_QUAD];
         if (npx == DS_QUAD && (flags & DS_WIDE_U8)) {
             // the four source pixels are neighbours either way; under flip_h they start at W - 4 - x and arrive reversed
-            const uint32_t* __restrict__ in = reinterpret_cast<const uint32_t*>(row + (fh ? W - DS_QUAD - x : x) * 3);
+            const uint8_t* __restrict__ in = row + (fh ? W - DS_QUAD - x : x) * 3;
             uint32_t w[3];
+            if (WIN) {
+                ds_load12(in, w);
+            } else {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) w[k] = in[k];
+                for (int k = 0; k < 3; ++k) w[k] = reinterpret_cast<const uint32_t*>(in)[k];
+            }
             float s[3][DS_QUAD];
 #pragma unroll
             for (int j = 0; j < DS_QUAD; ++j)
@@ -261,11 +350,34 @@ extern "C" int adh_batch_from_u8(void* stream, const uint8_t* cache, int64_t ima
     if (params) {
         hipLaunchKernelGGL(batch_gray_partial_kernel, dim3(nblk, N), dim3(256), 0, (hipStream_t)stream, cache, image_pitch, index,
                            params, HW, flags, partial);
-        hipLaunchKernelGGL(batch_gather_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, cache, image_pitch, index, params,
+        hipLaunchKernelGGL((batch_gather_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, cache, image_pitch, index, params,
                            partial, nblk, H, W, out_nchw, flags);
     } else {
-        hipLaunchKernelGGL(batch_gather_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, cache, image_pitch, index, params,
+        hipLaunchKernelGGL((batch_gather_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, cache, image_pitch, index, params,
                            partial, nblk, H, W, out_nchw, flags);
+    }
+    return adh_check_launch();
+}
+
+extern "C" int adh_batch_window_from_u8(void* stream, const uint8_t* cache, int64_t cache_bytes, const int64_t* window,
+                                        const float* params, int N, int CH, int CW, double* partial, int nblk, float* out_nchw) {
+    if (!cache || !window || !out_nchw || (params && !partial)) return ADH_E_ARG;
+    if (N < 1 || N > 65535 || CH < 1 || CW < 1) return ADH_E_ARG;
+    const int64_t HW = (int64_t)CH * CW;
+    if (HW > INT64_MAX / 3 || cache_bytes < HW * 3) return ADH_E_ARG;
+    if (nblk != adh_batch_num_blocks(HW)) return ADH_E_ARG;
+    // aligned dwords around any byte of the cache stay inside it when it starts and ends on a multiple of 4
+    const bool al4 = ((((uintptr_t)cache) | (uintptr_t)cache_bytes) & 3) == 0;
+    const int flags = (al4 ? DS_WIDE_U8 : 0) | (((((uintptr_t)out_nchw) & 15) == 0 && (CW & 3) == 0) ? DS_WIDE_F32 : 0);
+    const dim3 grid((unsigned)adh_ceil_div(CW, 64 * DS_QUAD), (unsigned)adh_min_i(adh_ceil_div(CH, DS_ROWS), 65535), (unsigned)N);
+    if (params) {
+        hipLaunchKernelGGL(window_gray_partial_kernel, dim3(nblk, N), dim3(256), 0, (hipStream_t)stream, cache, window, params, CW,
+                           HW, flags, partial);
+        hipLaunchKernelGGL((batch_gather_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, cache, (int64_t)0, window,
+                           params, partial, nblk, CH, CW, out_nchw, flags);
+    } else {
+        hipLaunchKernelGGL((batch_gather_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, cache, (int64_t)0, window,
+                           params, partial, nblk, CH, CW, out_nchw, flags);
     }
     return adh_check_launch();
 }

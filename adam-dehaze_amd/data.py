@@ -12,7 +12,9 @@ Image folders (data/dataset.py:9-124, 233-249 of the reference): `folder_index` 
 (`adh_u8_resize_bilinear`) and keeps the split as two dense uint8 [L,H,W,3] device tensors; `FolderDataset.epoch` yields the
 batch dicts, each image batch assembled by `adh_batch_from_u8` (v / 255 and the train transform in one gather pass over 3
 bytes per pixel).  `epoch_plan` is the pure host function that decides which samples a rank sees in which order;
-`folder_loader` is what the drivers call.  There are no worker processes and no streaming loader: a split that does not fit
+`folder_loader` is what the drivers call.  With `dataset.crop_size` the files keep their own sizes in two flat uint8 tensors
+and a batch is random (train) or centre crops of them, assembled by `adh_batch_window_from_u8` from a byte offset and a row
+pitch per sample (`batch_from_windows`, `draw_crop_origins`, `centre_origins`, `upscaled_size`).  There are no worker processes and no streaming loader: a split that does not fit
 in half of the free device memory is refused.
 """
 from __future__ import annotations
@@ -256,6 +258,84 @@ def batch_from_cache(cache, index: torch.Tensor, params: Optional[torch.Tensor] 
     return outs[0] if isinstance(cache, torch.Tensor) else outs
 
 
+def batch_from_windows(cache, windows: torch.Tensor, crop, params: Optional[torch.Tensor] = None):
+    """`crop` = (CH, CW) windows of a flat uint8 device cache that holds images of any sizes, as float32 [N,3,CH,CW] of exactly
+    v / 255: row y of sample n is the CW * 3 interleaved RGB bytes at `cache[windows[n,0] + y * windows[n,1]:]`, so `windows` (CPU
+    int64 [N,2]) holds the byte offset of each window's first pixel and its image's row pitch (`crop_windows`).  With `params`
+    the train transform is applied in the same pass, the grey mean of the contrast step taken over the window: bit for bit
+    `batch_from_cache` on a dense copy of the windows' bytes.  `cache` may be a sequence of flat caches of one length (hazy,
+    clear): one upload of the windows and of the rows then serves all of them and the result is a list.  The windows are checked
+    here, on the host, before anything touches the device, because the kernel does not validate them: IndexError unless
+    offset >= 0, pitch >= CW * 3 and offset + (CH - 1) * pitch + CW * 3 <= cache.numel() in every row."""
+    caches = [cache] if isinstance(cache, torch.Tensor) else list(cache)
+    if not isinstance(windows, torch.Tensor) or windows.is_cuda or windows.dtype != torch.int64 or windows.dim() != 2 \
+            or windows.shape[1] != 2:
+        raise TypeError("batch_from_windows: windows must be an int64 [N,2] tensor on the CPU")
+    CH, CW = _size2(crop)
+    if CH < 1 or CW < 1:
+        raise ValueError(f"batch_from_windows: crop must be at least 1 x 1, got {(CH, CW)}")
+    c0 = caches[0]
+    for c in caches:
+        if c.dim() != 1 or c.shape != c0.shape:
+            raise ValueError(f"batch_from_windows: the caches must be flat and of one length, got {[tuple(c.shape) for c in caches]}")
+    N = windows.shape[0]
+    if N < 1:
+        raise ValueError("batch_from_windows: no windows")
+    if params is not None and tuple(params.shape) != (N, 5):
+        raise ValueError(f"batch_from_windows: params must be [{N},5], got {tuple(params.shape)}")
+    if any(o < 0 or p < CW * 3 or o + (CH - 1) * p + CW * 3 > c0.numel() for o, p in windows.tolist()):    # Python ints: no wrap
+        raise IndexError(f"batch_from_windows: a {CH}x{CW} window leaves a cache of {c0.numel()} bytes: {windows.tolist()}")
+    for c in caches:
+        if not c.is_cuda or c.dtype != torch.uint8 or not c.is_contiguous() or c.device != c0.device:
+            raise RuntimeError(f"adam-dehaze_amd: the cache must be a dense uint8 tensor on one cuda device, got {c.dtype} on "
+                               f"{c.device} (no CPU fallback)")
+    nblk = H.value("adh_batch_num_blocks", CH * CW)
+    outs = []
+    with torch.cuda.device(c0.device):
+        wd = windows.contiguous().to(c0.device)
+        pd = None if params is None else params.to(device=c0.device, dtype=torch.float32).contiguous()
+        for c in caches:
+            partial = None if pd is None else torch.empty(N * nblk, device=c0.device, dtype=torch.float64)
+            out = torch.empty((N, 3, CH, CW), device=c0.device, dtype=torch.float32)
+            H.call("adh_batch_window_from_u8", c.data_ptr(), c.numel(), wd.data_ptr(), H.ptr(pd), N, CH, CW, H.ptr(partial), nblk,
+                   out.data_ptr())
+            outs.append(out)
+    return outs[0] if isinstance(cache, torch.Tensor) else outs
+
+
+def crop_windows(offsets, sizes, origins) -> torch.Tensor:
+    """int64 [n,2] rows {byte offset of the window's first pixel, row pitch} for `batch_from_windows`: images of `sizes` [n,2]
+    (heights, widths) stored as dense interleaved RGB at byte `offsets` [n] of a flat cache, cropped at `origins` [n,2] (y0, x0)."""
+    offsets, sizes, origins = (np.asarray(a, dtype=np.int64) for a in (offsets, sizes, origins))
+    return torch.from_numpy(np.stack([offsets + (origins[:, 0] * sizes[:, 1] + origins[:, 1]) * 3, sizes[:, 1] * 3], axis=1))
+
+
+def draw_crop_origins(sizes, crop, rng) -> np.ndarray:
+    """int64 [n,2] random crop origins (y0, x0) for images of `sizes` [n,2] (heights, widths), uniform over the positions at
+    which a `crop` = (CH, CW) window lies inside the image.  Per sample, in order: rng.randint(0, H - CH + 1), then
+    rng.randint(0, W - CW + 1)."""
+    CH, CW = _size2(crop)
+    return np.array([[rng.randint(0, int(h) - CH + 1), rng.randint(0, int(w) - CW + 1)] for h, w in np.asarray(sizes)],
+                    dtype=np.int64).reshape(-1, 2)
+
+
+def centre_origins(sizes, crop) -> np.ndarray:
+    """int64 [n,2]: ((H - CH) // 2, (W - CW) // 2), the centre crop of validation"""
+    CH, CW = _size2(crop)
+    return (np.asarray(sizes, dtype=np.int64).reshape(-1, 2) - np.array([CH, CW], dtype=np.int64)) // 2
+
+
+def upscaled_size(h: int, w: int, crop) -> tuple:
+    """The size at which an h x w image is cached for `crop` = (CH, CW) windows: its own when the crop fits inside it, otherwise
+    the smallest size of its aspect ratio that holds one crop (the free side rounded half up, in integers)."""
+    CH, CW = _size2(crop)
+    if h >= CH and w >= CW:
+        return int(h), int(w)
+    if CH * w >= CW * h:
+        return CH, max(CW, (2 * w * CH + h) // (2 * h))
+    return max(CH, (2 * h * CW + w) // (2 * w)), CW
+
+
 def _size2(img_size) -> tuple:
     h, w = (img_size, img_size) if isinstance(img_size, int) else img_size
     return int(h), int(w)
@@ -268,26 +348,40 @@ class FolderDataset:
     Every file is decoded once with `image_io.load_image` on `threads` host threads (at most 16; `dataset.num_workers` in the
     drivers), uploaded, and brought to `img_size` (int or [h, w]) by `adh_u8_resize_bilinear`, which also replicates grey and
     drops alpha.  A file that cannot be read raises, naming the path.  A cache that would take more than half of the free
-    device memory raises: a streaming loader is not built."""
+    device memory raises: a streaming loader is not built.
+
+    `crop_size` (int or [h, w]; `dataset.crop_size` in the drivers) keeps every pair at its own resolution instead and serves
+    crops of that size: `hazy` and `clear` are then two flat uint8 tensors, pair k's images dense [sizes[k,0], sizes[k,1], 3]
+    at byte `offsets[k]` (a multiple of 4; `sizes` int64 [L,2] and `offsets` int64 [L] stay on the host).  The sizes come from
+    the files' headers before anything is decoded; a pair whose hazy and clear sizes differ raises.  A pair smaller than the
+    crop on either side is cached at `upscaled_size`; every other file's bytes pass through.  `img_size` is not used then."""
 
     def __init__(self, records: Sequence[Dict], img_size, device, rank: int = 0, world: int = 1, threads: int = 4,
-                 split: str = "train"):
+                 split: str = "train", crop_size=None):
         from .image_io import load_image
         self.H, self.W = _size2(img_size)
+        self.crop = None if crop_size is None else _size2(crop_size)
         self.device = torch.device(device)
         self.rank, self.world, self.total = rank, world, len(records)
         own = list(records[rank::world])
         self.names = [r["name"] for r in own]
         L = len(own)
-        need = 2 * L * self.H * self.W * 3
+        nthreads = max(1, min(int(threads), MAX_DECODE_THREADS))
+        if self.crop is None:
+            shape, what, advice = (L, self.H, self.W, 3), f"{self.H}x{self.W}", "a smaller dataset.img_size"
+        else:
+            upscaled = self._layout(own, nthreads)
+            shape, advice = (self.cache_bytes,), "a smaller dataset"
+            what = f"their own sizes ({upscaled} upscaled to hold a {self.crop[0]}x{self.crop[1]} crop)"
+        need = 2 * int(np.prod(shape, dtype=np.int64))
         if self.device.type != "cuda":
             raise RuntimeError(f"adam-dehaze_amd: the dataset cache lives on a cuda device, got {self.device} (no CPU fallback)")
         free = torch.cuda.mem_get_info(self.device)[0]
         if need > free // 2:
             raise RuntimeError(f"the {split} split needs {need} bytes of device memory as an 8-bit cache ({L} pairs at "
-                               f"{self.H}x{self.W}), more than half of the {free} bytes free on {self.device}; a streaming "
-                               "loader is not built: use a smaller dataset.img_size or more ranks")
-        self.hazy = torch.empty((L, self.H, self.W, 3), dtype=torch.uint8, device=self.device)
+                               f"{what}), more than half of the {free} bytes free on {self.device}; a streaming "
+                               f"loader is not built: use {advice} or more ranks")
+        self.hazy = torch.empty(shape, dtype=torch.uint8, device=self.device)
         self.clear = torch.empty_like(self.hazy)
         self.labels = torch.tensor([r["intensity"] for r in own], dtype=torch.int64).to(self.device)
 
@@ -297,18 +391,51 @@ class FolderDataset:
             except Exception as e:
                 raise RuntimeError(f"cannot read image file {job[2]}: {e}") from e
         jobs = [(cache, slot, r[role]) for slot, r in enumerate(own) for role, cache in (("hazy", self.hazy), ("clear", self.clear))]
-        nthreads = max(1, min(int(threads), MAX_DECODE_THREADS))
         with ThreadPoolExecutor(nthreads) as pool, torch.cuda.device(self.device):
             for at in range(0, len(jobs), 4 * nthreads):        # a few files per thread in flight: decoded files do not pile up
                 chunk = jobs[at:at + 4 * nthreads]
                 for (cache, slot, path), img in zip(chunk, pool.map(decode, chunk)):
                     h, w, c = img.shape
                     src = img.contiguous().to(self.device)
-                    H.call("adh_u8_resize_bilinear", src.data_ptr(), w * c, h, w, c, cache[slot].data_ptr(), self.H, self.W)
+                    if self.crop is None:
+                        dst, oh, ow = cache[slot].data_ptr(), self.H, self.W
+                    else:
+                        (oh, ow), dst = self.sizes[slot].tolist(), cache.data_ptr() + int(self.offsets[slot])
+                    H.call("adh_u8_resize_bilinear", src.data_ptr(), w * c, h, w, c, dst, oh, ow)
         print(f"Loaded {self.total} samples for {split} split")
         print(f"  skipped {getattr(records, 'skipped', 0)} hazy files without a clear file of the same name")
-        print(f"  device cache: {L} pairs at {self.H}x{self.W} on {self.device}, {need / 2 ** 20:.1f} MiB"
-              + (f" (rank {rank} of {world})" if world > 1 else ""))
+        print(f"  device cache: {L} pairs at {what} on {self.device}, {need / 2 ** 20:.1f} MiB"
+              + (f" ({need} bytes)" if self.crop is not None else "") + (f" (rank {rank} of {world})" if world > 1 else ""))
+
+    def _layout(self, own: Sequence[Dict], nthreads: int) -> int:
+        """crop mode: `sizes`, `offsets` and `cache_bytes` (per role) from the files' headers; returns the number of pairs that
+        are cached larger than their files"""
+        from .image_io import _pil
+
+        def header(path):
+            try:
+                with _pil().open(path) as im:       # reads the header, decodes nothing
+                    w, h = im.size
+            except Exception as e:
+                raise RuntimeError(f"cannot read image file {path}: {e}") from e
+            return int(h), int(w)
+        with ThreadPoolExecutor(nthreads) as pool:
+            hazy = list(pool.map(header, [r["hazy"] for r in own]))
+            clear = list(pool.map(header, [r["clear"] for r in own]))
+        sizes, offsets, at, upscaled = [], [], 0, 0
+        for r, hs, cs in zip(own, hazy, clear):
+            if hs != cs:
+                raise ValueError(f"the files of a pair differ in size: {r['hazy']} is {hs[0]}x{hs[1]}, {r['clear']} is "
+                                 f"{cs[0]}x{cs[1]}")
+            size = upscaled_size(hs[0], hs[1], self.crop)
+            upscaled += size != hs
+            sizes.append(size)
+            offsets.append(at)
+            at += -(-size[0] * size[1] * 3 // 4) * 4             # every slot starts on a multiple of 4
+        self.sizes = np.array(sizes, dtype=np.int64).reshape(-1, 2)
+        self.offsets = np.array(offsets, dtype=np.int64)
+        self.cache_bytes = at
+        return upscaled
 
     def __len__(self):
         return len(self.names)
@@ -316,26 +443,36 @@ class FolderDataset:
     def epoch(self, epoch: int, batch_size: int, seed: int, train: bool, augment: bool = True) -> Iterator[Dict]:
         """The batch dicts of `synthetic_loader` ('hazy', 'clear' float32 [n,3,H,W]; 'intensity' int64 [n], device; 'name' file
         names) in the order of `epoch_plan`.  train and `augment`: one `draw_augment_params` row per sample from this loader's
-        own RandomState(seed + 1000 * rank + epoch); the same device rows drive hazy and clear."""
+        own RandomState(seed + 1000 * rank + epoch); the same device rows drive hazy and clear.  In crop mode the images are
+        [n,3,CH,CW]: a train batch draws, after its parameter rows (when `augment`), `draw_crop_origins` from the same
+        RandomState, so every epoch sees fresh patches; every other batch takes the centre windows and no rows."""
         if self.total == 0 or (not train and len(self) == 0):
             return
         rng = np.random.RandomState(seed + 1000 * self.rank + epoch)
         for samples in epoch_plan(self.total, self.world, self.rank, batch_size, seed, epoch, train):
             index = torch.from_numpy((samples - self.rank) // self.world)
             params = draw_augment_params(index.numel(), rng) if train and augment else None
-            hazy, clear = batch_from_cache((self.hazy, self.clear), index, params)
+            if self.crop is None:
+                hazy, clear = batch_from_cache((self.hazy, self.clear), index, params)
+            else:
+                sizes = self.sizes[index.numpy()]
+                origins = draw_crop_origins(sizes, self.crop, rng) if train else centre_origins(sizes, self.crop)
+                windows = crop_windows(self.offsets[index.numpy()], sizes, origins)
+                hazy, clear = batch_from_windows((self.hazy, self.clear), windows, self.crop, params)
             yield {"hazy": hazy, "clear": clear, "intensity": self.labels[index.to(self.device)],
                    "name": [self.names[i] for i in index.tolist()]}
 
 
-_CACHES: Dict[tuple, FolderDataset] = {}     # (resolved split directory, split, (h, w), device, rank, world) -> the built cache
+_CACHES: Dict[tuple, FolderDataset] = {}     # (resolved split directory, split, (h, w), device, rank, world, crop) -> the built cache
 
 
 def folder_loader(config, split: str, device, rank: Optional[int] = None, world: Optional[int] = None) -> Optional[Callable]:
     """`epoch -> iterable of batch dicts` over the image folders of `split` ('train' | 'val' | 'test'), or None when
     `folder_index` finds none under `dataset.train_path` / `val_path` / `test_path` (data/dataset.py:233-241).  rank / world
     default to the process's RANK / WORLD_SIZE.  The cache of a split is built once per process and kept, so the stages of
-    train_all and the evaluators share it.  `dataset.num_workers` is the number of decode threads."""
+    train_all and the evaluators share it.  `dataset.num_workers` is the number of decode threads.  `dataset.crop_size` (int or
+    [h, w]; absent or null: off) caches every pair at its own resolution and serves random crops of that size to training and
+    centre crops to validation and test (`FolderDataset`); the synthetic fallback does not read it and keeps using `img_size`."""
     ds = config.get("dataset", {})
     root = ds.get({"train": "train_path", "val": "val_path"}.get(split, "test_path"))
     split_dir = _split_dir(root, split)
@@ -346,14 +483,16 @@ def folder_loader(config, split: str, device, rank: Optional[int] = None, world:
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    key = (os.path.realpath(split_dir), split, _size2(ds["img_size"]), str(device), rank, world)
+    crop = ds.get("crop_size")
+    crop = None if crop is None else _size2(crop)
+    key = (os.path.realpath(split_dir), split, _size2(ds["img_size"]), str(device), rank, world, crop)
     if key not in _CACHES:
         records = folder_index(root, split)
         if not records:
             raise RuntimeError(f"{records.split_dir}: the {split} split has image folders but no hazy / clear pair "
                                f"({records.skipped} hazy files without a clear file)")
         _CACHES[key] = FolderDataset(records, ds["img_size"], device, rank, world, threads=int(ds.get("num_workers", 4)),
-                                     split=split)
+                                     split=split, crop_size=crop)
     cache = _CACHES[key]
     batch_size, seed, train = int(ds["batch_size"]), int(config.get("seed", 0)), split == "train"
     augment = bool(ds.get("augmentation", True))

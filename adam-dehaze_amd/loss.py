@@ -705,7 +705,8 @@ class JointLoss(nn.Module):
         self.lambda_dehazing = lambda_dehazing
         self.lambda_classification = lambda_classification
         self.lambda_detection = lambda_detection
-        self.dehazing_loss = DehazingLoss(lambda_ssim=_lambda_ssim(config), **_lambda_fft(config), **_lambda_msssim(config))
+        self.dehazing_loss = DehazingLoss(lambda_ssim=_lambda_ssim(config), **_lambda_fft(config), **_lambda_msssim(config),
+                                          **_perceptual(config))
 
     def forward(self, pred, target_clear, pred_intensity=None, target_intensity=None, detection_loss=None):
         dehazing_loss, comps = self.dehazing_loss(pred, target_clear)
@@ -743,10 +744,19 @@ def _lambda_msssim(config) -> dict:
     return {"lambda_msssim": lam, "msssim_weights": None if w is None else tuple(w)}
 
 
+def _perceptual(config) -> dict:
+    """`loss.perceptual: false` of the config as DehazingLoss's keyword: the LPIPS term is dropped.  Nothing at all where the key
+    is absent or true (the reference has no such key), so that the loss is built exactly as before.  The term's AlexNet has no
+    output for images under 31 x 31 (an 11 x 11 stride-4 convolution, then two 3 x 3 stride-2 pools; torchvision's raises there
+    too), so training on smaller crops (`dataset.crop_size`) has to switch it off."""
+    sec = (config or {}).get("loss") or {}
+    return {} if sec.get("perceptual", True) else {"perceptual": False}
+
+
 def get_dehazing_loss(config):
     """loss.py:226-232."""
     return DehazingLoss(lambda_l1=1.0, lambda_content=0.1, lambda_perceptual=0.1, lambda_ssim=_lambda_ssim(config),
-                        **_lambda_fft(config), **_lambda_msssim(config))
+                        **_lambda_fft(config), **_lambda_msssim(config), **_perceptual(config))
 
 
 def get_joint_loss(config):

@@ -747,12 +747,29 @@ int adh_image_to_u8(void* stream, const float* src_nchw, int N, int H, int W, ui
  *       the host before the upload).  Dword reads where cache and image_pitch are multiples of 4 (and, in the gather pass,
  *       W % 4 == 0), 16-byte stores where out is 16-byte aligned and W % 4 == 0; bytes and floats otherwise, same values.
  *       ADH_E_ARG (nothing is launched) for a null cache / index / out, params without partial, N outside [1, 65535], H, W or
- *       M < 1, image_pitch < H * W * 3, or nblk other than adh_batch_num_blocks(H * W). */
+ *       M < 1, image_pitch < H * W * 3, or nblk other than adh_batch_num_blocks(H * W).
+ *   adh_batch_window_from_u8   the same from a flat cache of cache_bytes bytes that holds images of any sizes: out[n] is the
+ *       CH x CW window whose row y is the CW * 3 interleaved RGB bytes at cache + window[n][0] + y * window[n][1] (window:
+ *       device int64[N, 2] = {byte offset of the window's first pixel, row pitch in bytes}; for a crop at (y0, x0) of an image
+ *       of width Wi at byte offset o that is {o + (y0 * Wi + x0) * 3, Wi * 3}).  Windows may overlap or repeat.  params,
+ *       partial and the launches as above with nblk = adh_batch_num_blocks(CH * CW); the grey mean of the contrast step is
+ *       taken over the window (crop first, then the transform).  Bit contract: the result equals, bit for bit,
+ *       adh_batch_from_u8 on a dense copy of the windows' bytes, itself on one sample alone, and a second call.
+ *       window[n] is NOT validated on the device: the caller guarantees offset >= 0, pitch >= CW * 3 and
+ *       offset + (CH - 1) * pitch + CW * 3 <= cache_bytes (data.batch_from_windows checks it on the host before the upload).
+ *       No byte outside [cache, cache + cache_bytes) is read.  A quad's 12 bytes are read as three aligned dwords, plus a
+ *       fourth and a funnel shift when their address is no multiple of 4, where cache and cache_bytes are multiples of 4
+ *       (the last dword touched then ends at or before the window's end rounded up to 4 <= cache_bytes); byte by byte
+ *       otherwise, and for the partial quad at a row's right edge.  Stores as above.
+ *       ADH_E_ARG (nothing is launched) for a null cache / window / out, params without partial, N outside [1, 65535], CH or
+ *       CW < 1, cache_bytes < CH * CW * 3 (or that product overflowing), or nblk other than adh_batch_num_blocks(CH * CW). */
 int adh_u8_resize_bilinear(void* stream, const uint8_t* src, int64_t row_pitch, int H, int W, int C, uint8_t* dst, int OH,
                            int OW);
 int adh_batch_num_blocks(int64_t HW);
 int adh_batch_from_u8(void* stream, const uint8_t* cache, int64_t image_pitch, int64_t M, int H, int W, const int64_t* index,
                       const float* params, int N, double* partial, int nblk, float* out_nchw);
+int adh_batch_window_from_u8(void* stream, const uint8_t* cache, int64_t cache_bytes, const int64_t* window, const float* params,
+                             int N, int CH, int CW, double* partial, int nblk, float* out_nchw);
 
 /* ---- CIEDE2000 (csrc/ciede2000.hip): the per-pixel colour difference dE00 of Sharma, Wu and Dalal (2005), kL = kC = kH = 1,
  * between two dense fp32 [N,3,H,W] batches, and its mean per image.  lab_input == 0: the planes are sRGB in [0,1] (clamped as

@@ -4,6 +4,7 @@
 //   0 adh_u8_resize_bilinear   i: row_pitch H W C OH OW                     b: src dst
 //   1 adh_batch_num_blocks     i: HW
 //   2 adh_batch_from_u8        i: image_pitch M H W N nblk                  b: cache index params partial out
+//   3 adh_batch_window_from_u8 i: cache_bytes N CH CW nblk                  b: cache window params partial out
 #include "common.h"
 #include "stream_rt.h"
 
@@ -14,6 +15,9 @@ static int64_t dispatch(const emu_call& c) {
         case 2:
             return adh_batch_from_u8(nullptr, c.p<uint8_t>(0), c.i[0], c.i[1], c.I(2), c.I(3), c.p<int64_t>(1), c.f(2), c.I(4),
                                      c.p<double>(3), c.I(5), c.f(4));
+        case 3:
+            return adh_batch_window_from_u8(nullptr, c.p<uint8_t>(0), c.i[0], c.p<int64_t>(1), c.f(2), c.I(1), c.I(2), c.I(3),
+                                            c.p<double>(3), c.I(4), c.f(4));
     }
     return -1000;
 }
