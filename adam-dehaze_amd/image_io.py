@@ -336,10 +336,51 @@ def summarize_scores(records: Iterable[Dict]) -> Dict:
     return out
 
 
+NOREF_KEYS = ("niqe", "brisque")
+
+
+def noref_batch(hazy: torch.Tensor, dehazed_u8: torch.Tensor, niqe_model=None, brisque_model=None) -> List[Dict]:
+    """The no-reference scores of every image of a chunk (nss.niqe_batch, nss.brisque_batch): `niqe` / `hazy_niqe` with a
+    `niqe_model`, `brisque` / `hazy_brisque` with a `brisque_model`.  `hazy` fp32 [n,3,H,W]; the dehazed side is `u8_to_image`
+    of the packed bytes `dehazed_u8` [n,H,W,3], the pixels of the written file, as in `score_batch`."""
+    from .nss import brisque_batch, niqe_batch
+    recs: List[Dict] = [{} for _ in range(hazy.shape[0])]
+    for prefix, img in (("", u8_to_image(dehazed_u8)), ("hazy_", hazy)):
+        for key, model, fn in (("niqe", niqe_model, niqe_batch), ("brisque", brisque_model, brisque_batch)):
+            if model is not None:
+                for rec, v in zip(recs, fn(img, model)):
+                    rec[prefix + key] = v
+    return recs
+
+
+def summarize_noref(records: Iterable[Dict]) -> Dict:
+    """`demo_noref.json`: {"dehazed": {category: {niqe, brisque, samples}}, "hazy": {...}} over the records that carry a
+    no-reference score; the category is the routed intensity (`low_intensity`, ...) plus `all`; only the scores that were asked
+    for appear.  A mean is over the records that have the number; those without (None) are counted as `niqe_null` /
+    `brisque_null`, keys that appear only where there are any, and a mean nobody contributes to is null."""
+    rs_all = [r for r in records if any(k in r for k in NOREF_KEYS)]
+    out: Dict[str, Dict] = {"dehazed": {}, "hazy": {}}
+    for side, prefix in (("dehazed", ""), ("hazy", "hazy_")):
+        for cat in sorted({r["intensity"] + "_intensity" for r in rs_all}) + ["all"]:
+            rs = [r for r in rs_all if cat == "all" or r["intensity"] + "_intensity" == cat]
+            if not rs:
+                continue
+            entry: Dict = {}
+            for k in NOREF_KEYS:
+                if any(k in r for r in rs):
+                    have = [r[prefix + k] for r in rs if r.get(prefix + k) is not None]
+                    entry[k] = sum(have) / len(have) if have else None
+                    if len(have) < len(rs):
+                        entry[k + "_null"] = len(rs) - len(have)
+            entry["samples"] = len(rs)
+            out[side][cat] = entry
+    return out
+
+
 def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: int = 4, panels: bool = False,
                  targets: Optional[Dict[str, Dict]] = None, self_ensemble: Optional[str] = None, exif: bool = False,
                  ms_ssim: bool = False, detector=None, detect_threshold: float = 0.5,
-                 detect_style: Optional[Dict] = None) -> List[Dict]:
+                 detect_style: Optional[Dict] = None, niqe_model=None, brisque_model=None) -> List[Dict]:
     """Dehaze image files through `system["router"]` (eval mode, no_grad) at their own size and write `<out_dir>/<name>.png` --
     with `panels` also `<name>_panel.png`, hazy | dehazed -- for every input `<name>.<ext>`.  Files of equal size go through
     together, `batch_size` at a time.  Returns one dict per processed file, in sorted order: `file`, `height`, `width` and the
@@ -363,7 +404,11 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
     "box": [x, y, w, h]}), `detect_counts` ({"hazy", "dehazed"}) and `detect_match` (overlay.match_detections(hazy, dehazed)), and
     `<name>_detect.png` is written: the hazy | dehazed panel with each pane's detections drawn on the device
     (overlay.draw_boxes on pane views of one buffer; `detect_style`: its thickness / scale / alpha) before the one copy back.
-    `<name>.png` and `<name>_panel.png` stay unannotated, byte for byte what they are without a detector."""
+    `<name>.png` and `<name>_panel.png` stay unannotated, byte for byte what they are without a detector.
+    `niqe_model` (an nss.NiqeModel): every record gains `niqe` and `hazy_niqe`, the no-reference NIQE of the written file
+    (`u8_to_image` of its bytes, as `score_batch` takes it) and of the upright input; None for a file under 96 px on a side or
+    with fewer than two patches of finite features.  `brisque_model` (an nss.SvrModel): `brisque` and `hazy_brisque` in the same
+    way, None where a feature is not finite.  Neither needs `targets`; both work alongside them."""
     if self_ensemble is not None and self_ensemble not in _d4.SELF_ENSEMBLE_MODES:
         raise ValueError(f"self_ensemble must be one of {sorted(_d4.SELF_ENSEMBLE_MODES)}, got {self_ensemble!r}")
     paths = sorted(str(p) for p in paths)
@@ -394,7 +439,7 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
             kw["tags"] = [tags[p] for p in chunk]
         extra: List[Dict] = [{} for _ in chunk]
         marked = None                                  # the annotated panels of the chunk, on the host
-        if targets is None and detector is None:
+        if targets is None and detector is None and niqe_model is None and brisque_model is None:
             out, panel, records = dehaze_batch(system, u8, panels, **kw)
         else:
             hazy, out, panel, records = _dehaze_on_device(system, u8, panels, **kw)
@@ -446,6 +491,9 @@ def dehaze_files(system: Dict, paths: Iterable[str], out_dir: str, batch_size: i
                                          **skw)
                     for i, sc in zip(part, scores):
                         extra[i].update(scored=True, **sc)
+            if niqe_model is not None or brisque_model is not None:
+                for i, sc in enumerate(noref_batch(hazy, out, niqe_model, brisque_model)):
+                    extra[i].update(sc)
             if panel is None:
                 out = out.cpu()
             else:                                      # one copy back: the dehazed image is the panel's right pane

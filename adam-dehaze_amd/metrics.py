@@ -18,6 +18,7 @@ import torch
 
 from . import _hip as H
 from .detection_metrics import DetectionMetrics   # noqa: F401  (evaluation/metrics.py:126-270)
+from .nss import brisque_batch, niqe_batch         # noqa: F401  (the no-reference scores)
 
 CATEGORY_BY_LABEL = {0: "low_intensity", 1: "medium_intensity", 2: "high_intensity"}   # evaluate.py:160-166
 

@@ -978,9 +978,34 @@ def run_comprehensive_evaluation(config, steps: int = 2, use_lpips: bool = True)
     return comprehensive
 
 
+def fit_niqe_model(config, input: str, out_path: str):
+    """`main.py --mode demo --input CLEAR_DIR --fit-niqe OUT.npz`: NIQE's pristine model (nss.NiqeModel.fit) from the
+    image files of `input` -- the `clear/` folder of a dataset, say --, `demo.batch_size` files of one size at a time.  Prints
+    the image and patch counts and writes the model; builds no network."""
+    from .nss import NiqeModel
+    if os.path.isdir(input):
+        paths = sorted(os.path.join(input, f) for f in os.listdir(input) if f.lower().endswith(DEMO_EXTENSIONS))
+    elif os.path.isfile(input):
+        paths = [input]
+    else:
+        raise SystemExit(f"--input {input}: no such file or directory")
+    if not paths:
+        raise SystemExit(f"--input {input}: no {' / '.join('*' + e for e in DEMO_EXTENSIONS)} files")
+    demo = config.get("demo") or {}
+    try:
+        model = NiqeModel.fit(paths, batch_size=int(demo.get("batch_size", 4)), device=config.get("device", "cuda"))
+    except ValueError as e:
+        raise SystemExit(f"--fit-niqe: {e}") from None
+    model.save(out_path)
+    print(f"NIQE model from {model.meta['images']} images, {model.meta['patches']} sharp {model.meta['patch_size']}x"
+          f"{model.meta['patch_size']} patches -> {out_path}")
+    return model
+
+
 def run_demo(config, input: str, output: str = "demo", panels: bool = False, target: Optional[str] = None,
              self_ensemble: Optional[str] = None, exif: bool = False, ms_ssim: bool = False, detect: bool = False,
-             detect_threshold: Optional[float] = None):
+             detect_threshold: Optional[float] = None, niqe: Optional[str] = None, brisque_model: Optional[str] = None,
+             brisque_range: Optional[str] = None):
     """main.py:152-217 of the reference loads every checkpoint and stops at a TODO (load sample hazy images, classify, dehaze
     through the router, visualise); this is that mode.  `input` is one image file or a directory whose *.png / *.jpg / *.jpeg /
     *.bmp files are taken; every image goes through the routed system at its own size (image_io.dehaze_files, `demo.batch_size`
@@ -1005,7 +1030,13 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
     DESIGN 4.29).  `<output>/demo_detections.json` (overlay.summarize_detections) holds the threshold, where the detector's
     weights came from, and per routed intensity and overall the file count, the mean detections per file on either side and the
     summed matched / gained / lost.  Both sides go through the detector's own transform alone: the second normalisation of
-    the reference's IntegratedDetectionSystem is not applied to either, so the comparison is like for like."""
+    the reference's IntegratedDetectionSystem is not applied to either, so the comparison is like for like.
+    `niqe` (a model file written by `fit_niqe_model` / `--fit-niqe`; or `demo.niqe_model`): every record gains `niqe` and
+    `hazy_niqe`, the no-reference NIQE score (lower is better) of the written file and of the input, null for a file
+    under 96 px on a side; the scores are printed per file and `<output>/demo_noref.json` (image_io.summarize_noref) holds their
+    means per routed intensity and overall.  `brisque_model` (a libsvm epsilon-SVR model file with an RBF kernel, e.g. the
+    BRISQUE release's `allmodel`; or `demo.brisque_model`) with the optional svm-scale range file `brisque_range`
+    (`demo.brisque_range`): `brisque` and `hazy_brisque` in the same way.  Neither needs `target`; no model file is shipped."""
     import json
     from . import image_io as IO
     if _world_rank()[0] > 1:
@@ -1038,6 +1069,24 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
             raise SystemExit(f"demo.detect_style: unknown key(s) {', '.join(unknown)} (thickness, scale, alpha)")
     elif detect_threshold is not None:
         raise SystemExit("--detect-threshold needs --detect (demo.detect)")
+    niqe = niqe if niqe is not None else demo.get("niqe_model")
+    brisque_model = brisque_model if brisque_model is not None else demo.get("brisque_model")
+    brisque_range = brisque_range if brisque_range is not None else demo.get("brisque_range")
+    noref = {}                                                               # loaded before anything is built
+    if brisque_range is not None and brisque_model is None:
+        raise SystemExit("--brisque-range (demo.brisque_range) needs --brisque-model (demo.brisque_model)")
+    if niqe is not None or brisque_model is not None:
+        from . import nss as NSS
+        for what, path in (("--niqe", niqe), ("--brisque-model", brisque_model), ("--brisque-range", brisque_range)):
+            if path is not None and not os.path.isfile(path):
+                raise SystemExit(f"{what} {path}: no such file")
+        try:
+            if niqe is not None:
+                noref["niqe_model"] = NSS.NiqeModel.load(niqe)
+            if brisque_model is not None:
+                noref["brisque_model"] = NSS.SvrModel.load(brisque_model, brisque_range)
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
     if target is None:
         pairs = None
     else:
@@ -1058,6 +1107,7 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
         options.update(detector=detector, detect_threshold=detect_threshold)
         if demo.get("detect_style"):
             options["detect_style"] = {k: int(v) for k, v in demo["detect_style"].items()}
+    options.update(noref)
     results = IO.dehaze_files(system, paths, output, batch_size=batch_size, panels=panels, **options)
     for r in results:
         print(f"{r['file']}: {r['height']}x{r['width']}  {r['routing']} routing -> {r['intensity']}  weights "
@@ -1072,6 +1122,10 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
                       f"   (hazy input: {f4(r['hazy_ssim_gaussian'])}  {f4(r['hazy_ms_ssim'])})")
         elif pairs is not None:
             print("    not scored: " + (r.get("reason") or "no target"))
+        if noref:
+            nr = lambda v: "n/a" if v is None else f"{v:.3f}"
+            print("    no reference: " + "  ".join(f"{label} {nr(r[k])} (hazy input: {nr(r['hazy_' + k])})"
+                                                   for k, label in (("niqe", "NIQE"), ("brisque", "BRISQUE")) if k in r))
         if detect:
             c, m = r["detect_counts"], r["detect_match"]
             print(f"    detections above {detect_threshold:g}: hazy {c['hazy']}, dehazed {c['dehazed']}  (matched {m['matched']}, "
@@ -1088,6 +1142,16 @@ def run_demo(config, input: str, output: str = "demo", panels: bool = False, tar
         if a["files"]:
             print(f"detections per file: hazy {a['mean_hazy']:.2f}, dehazed {a['mean_dehazed']:.2f}; matched {a['matched']}, gained "
                   f"{a['gained']}, lost {a['lost']} over {a['files']} files (demo_detections.json; *_detect.png show them)")
+    if noref:
+        nsum = IO.summarize_noref(results)
+        with open(os.path.join(output, "demo_noref.json"), "w") as f:
+            json.dump(nsum, f, indent=2)
+        for side in ("dehazed", "hazy"):
+            m = nsum[side].get("all")
+            if m:
+                print(f"{side:>7}: " + "  ".join(f"{label} " + ("n/a" if m[k] is None else f"{m[k]:.3f}")
+                                                 for k, label in (("niqe", "NIQE"), ("brisque", "BRISQUE")) if k in m)
+                      + f" over {m['samples']} files (demo_noref.json)")
     if pairs is not None:
         summary = IO.summarize_scores(results)
         with open(os.path.join(output, "demo_scores.json"), "w") as f:

@@ -854,6 +854,26 @@ int adh_draw_boxes(void* stream, uint8_t* img, int64_t row_pitch, int64_t image_
                    const int32_t* first, int M, const float* boxes, const uint8_t* colors, const void* text, int T,
                    const uint8_t* glyphs, int G, int thickness, int scale, int alpha);
 
+/* ---- natural-scene statistics of NIQE and BRISQUE (csrc/nss.hip, whose head carries the whole definition).
+ * src_rgb == 1: src is float [N,3,H,W], the grey plane Y = 255 ((0.299 R + 0.587 G) + 0.114 B) is formed in float64 on the fly;
+ * src_rgb == 0: src is a double [N,H,W] grey plane.  Either way only the top-left Hc x Wc crop is used, and window and tap
+ * positions outside the crop take the nearest pixel inside it.  Everything behind the loads is float64.
+ *   adh_nss_halve     dst = double [N, (Hc+1)/2, (Wc+1)/2]: the crop halved by the antialiased bicubic (a = -0.5), output j from
+ *                     inputs 2j-3 .. 2j+4 (clamped) with weights [-3, -9, 29, 111, 111, 29, -9, -3] / 256, along W, then along H.
+ *   adh_nss_moments   out = double [N, Hc/rh, Wc/rw, 24]: per rh x rw region of the crop the sums [0] sum|M|, [1] sum M^2,
+ *                     [2] sum s of the MSCN coefficients M = -d / (s + 1) (7x7 Gaussian window, sigma 7/6, statistics centred on
+ *                     the pixel) and, for the neighbour directions k = (0,1), (1,0), (1,1), (1,-1) that wrap inside the region,
+ *                     at 3 + 5k: the count of products < 0, the sum of their squares, the count of products > 0, the sum of
+ *                     their squares, the sum of |p| over all; [23] = 0.  Counts are doubles.  partial: double
+ *                     [N * regions * ntiles * 24] workspace, ntiles = ceil(rh / 16) * ceil(rw / 32) (the kernel's tile is 16
+ *                     rows by 32 columns).  Fixed-order two-stage reduction without atomics: two runs are bit-equal and the
+ *                     numbers of image i do not depend on N.
+ * ADH_E_ARG (nothing is launched): a null pointer, N < 1, a flag other than 0 or 1, a size < 1, Hc > H, Wc > W, a region that
+ * does not tile the crop, a wrong ntiles, an output or the workspace overlapping the input or each other. */
+int adh_nss_halve(void* stream, const void* src, int src_rgb, int N, int H, int W, int Hc, int Wc, double* dst);
+int adh_nss_moments(void* stream, const void* src, int src_rgb, int N, int H, int W, int Hc, int Wc, int rh, int rw,
+                    double* partial, int ntiles, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,8 @@ the hot path run on the HIP engine; dataset preprocessing is outside this build'
     python main.py --mode demo --input HAZY --target CLEAR         # ... and score them: PSNR, SSIM, CIEDE2000 per file
     python main.py --mode demo --input HAZY --target CLEAR --ms-ssim   # ... plus Gaussian-window SSIM and MS-SSIM
     python main.py --mode demo --input DIR --detect                # ... detect on hazy and dehazed, boxes drawn on the device
+    python main.py --mode demo --input CLEAR --fit-niqe niqe.npz   # fit a NIQE model from clean files
+    python main.py --mode demo --input DIR --niqe niqe.npz         # ... and score without ground truth: NIQE per file
 
 `--resume` is the reference's flag (main.py:50-51 parses it and never reads it); here it restores model, optimiser,
 scheduler, epoch and best-PSNR from the latest checkpoint of the mode's checkpoint directory (or from the file given
@@ -60,6 +62,16 @@ def parse_args():
                         "demo.detect: true in the config")
     p.add_argument("--detect-threshold", dest="detect_threshold", type=float, default=None,
                    help="--detect: keep detections scoring above this (0..1; demo.detect_threshold, 0.5)")
+    p.add_argument("--niqe", type=str, default=None, metavar="MODEL.npz",
+                   help="--mode demo --input ...: score every dehazed file and every input with the no-reference NIQE against "
+                        "this model (written by --fit-niqe); needs no --target; same as demo.niqe_model in the config")
+    p.add_argument("--brisque-model", dest="brisque_model", type=str, default=None, metavar="FILE",
+                   help="--mode demo --input ...: score with BRISQUE through this libsvm epsilon-SVR model file (not shipped); "
+                        "same as demo.brisque_model in the config")
+    p.add_argument("--brisque-range", dest="brisque_range", type=str, default=None, metavar="FILE",
+                   help="--brisque-model: the svm-scale range file of its features (demo.brisque_range)")
+    p.add_argument("--fit-niqe", dest="fit_niqe", type=str, default=None, metavar="OUT.npz",
+                   help="--mode demo --input CLEAR_DIR: fit the NIQE model from these clean image files, write it and exit")
     return p.parse_args()
 
 
@@ -87,6 +99,22 @@ def main():
     if args.ms_ssim and not args.target:
         raise SystemExit("--ms-ssim needs --mode demo --input DIR_OR_FILE --target DIR_OR_FILE: MS-SSIM is a score against "
                          "the ground truth.")
+    if (args.niqe or args.brisque_model or args.brisque_range) and not (args.mode == "demo" and args.input):
+        raise SystemExit("--niqe, --brisque-model and --brisque-range need --mode demo --input DIR_OR_FILE: they score the "
+                         "image files given with --input.")
+    if args.brisque_range and not args.brisque_model:
+        raise SystemExit("--brisque-range needs --brisque-model: it is the range file of that model's features.")
+    if args.fit_niqe:
+        if not (args.mode == "demo" and args.input):
+            raise SystemExit("--fit-niqe needs --mode demo --input CLEAR_DIR: the clean image files the model is fitted from.")
+        others = [flag for flag, given in (("--target", args.target), ("--panels", args.panels),
+                                           ("--self-ensemble", args.self_ensemble), ("--exif", args.exif),
+                                           ("--ms-ssim", args.ms_ssim), ("--detect", args.detect),
+                                           ("--detect-threshold", args.detect_threshold is not None), ("--niqe", args.niqe),
+                                           ("--brisque-model", args.brisque_model), ("--brisque-range", args.brisque_range))
+                  if given]
+        if others:
+            raise SystemExit(f"--fit-niqe fits a model and exits; it does not go with {', '.join(others)}.")
     with open(args.config) as f:
         config = yaml.safe_load(f)
     if args.data_dir:   # main.py:66-69
@@ -171,6 +199,8 @@ def main():
         # evaluate.py:464-540 (the reference first rewrites the checkpoint paths to a hard-coded experiment directory, main.py:143-145:
         # here the paths of the config are used as they are)
         T.run_comprehensive_evaluation(config)   # baseline branches, routed system, detector on hazy vs dehazed frames
+    elif args.mode == "demo" and args.input and args.fit_niqe:
+        T.fit_niqe_model(config, args.input, args.fit_niqe)
     elif args.mode == "demo" and args.input:
         options = {}                                   # only the flags given: without any, the call is the plain one
         if args.target:
@@ -185,6 +215,12 @@ def main():
             options["detect"] = True
         if args.detect_threshold is not None:
             options["detect_threshold"] = args.detect_threshold
+        if args.niqe:
+            options["niqe"] = args.niqe
+        if args.brisque_model:
+            options["brisque_model"] = args.brisque_model
+        if args.brisque_range:
+            options["brisque_range"] = args.brisque_range
         T.run_demo(config, args.input, args.output, args.panels, **options)
     elif args.mode == "demo":
         # without --input: one synthetic batch through the router

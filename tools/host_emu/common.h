@@ -11,7 +11,8 @@
 // files (pointwise and train_io a second time with their grid caps set small by -D), by tests/test_msssim_hostemu_cpu.py on a copy of
 // csrc/msssim.hip (its grid.y cap set to 2 by -D, so that the plane loop runs), by tests/test_overlay_hostemu_cpu.py on a copy of
 // csrc/overlay.hip (its grid cap set to 2 by -D; the wave vote __ballot is built on the shuffle), by
-// tests/test_dataset_hostemu_cpu.py on a copy of csrc/dataset.hip (float64 butterflies in both of its batch kernels), and by
+// tests/test_dataset_hostemu_cpu.py on a copy of csrc/dataset.hip (float64 butterflies in both of its batch kernels), by
+// tests/test_nss_hostemu_cpu.py on a copy of csrc/nss.hip (its grid cap set to 2 by -D, so that the region loop runs), and by
 // tests/test_hostemu_shuffle_cpu.py on the shuffle itself.
 #pragma once
 #include <cmath>
