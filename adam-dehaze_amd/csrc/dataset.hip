@@ -381,3 +381,315 @@ extern "C" int adh_batch_window_from_u8(void* stream, const uint8_t* cache, int6
     }
     return adh_check_launch();
 }
+
+// ------------------------------------------------------------------------------------------------ depth cache, haze synthesis
+//   adh_u16_resize_bilinear  depth-cache build, one launch per file: single-channel 8-bit (v * 257, so v / 255 == v * 257 / 65535)
+//                           or 16-bit depth of any size to one dense uint16 [OH, OW] slot, with adh_u8_resize_bilinear's source
+//                           coordinates and fp32 arithmetic, rounded half-even and clamped to 0..65535.
+//   adh_batch_haze_from_u8  every step for the hazy role when the dataset holds clear images and depth maps: the CH x CW windows
+//                           geom[n] of a flat cache of clear RGB bytes, hazed by the scattering model at SOURCE coordinates
+//                           (I = J t + A (1 - t), t = exp(-beta d) in float64, one exp per pixel shared by the channels: fog_kernel
+//                           of csrc/train_io.hip), then the flips and the ColorJitter of batch_gather_kernel: augment(fog(x)).
+//                           d comes from a flat uint16 depth cache (near + (far - near) * u / 65535) or, without one, is fog_kernel's
+//                           radial map over the window.  The grey mean of the contrast step is that of the hazed window, so with
+//                           parameters it is two launches as above, each of which evaluates the model.
+// A lane's four pixels are 12 clear bytes (ds_load12) and 8 depth bytes at an even address: two aligned dwords, or three and a
+// funnel shift when the address is 2 mod 4 (hz_load8), where the respective cache starts and ends on a multiple of 4.
+#define DS_WIDE_U16 8        // flag: whole quads read their depth as dwords
+
+// the four uint16 at p (p even) as the dwords an aligned read gives; the last byte touched is that of the dword holding p + 7
+__device__ __forceinline__ void hz_load8(const uint8_t* __restrict__ p, uint32_t (&u)[DS_QUAD]) {
+    const unsigned s = (unsigned)((uintptr_t)p & 2);
+    const uint32_t* __restrict__ in = reinterpret_cast<const uint32_t*>(p - s);
+    uint32_t w0 = in[0], w1 = in[1];
+    if (s != 0) {
+        const uint32_t w2 = in[2];
+        w0 = (w0 >> 16) | (w1 << 16);
+        w1 = (w1 >> 16) | (w2 << 16);
+    }
+    u[0] = w0 & 0xFFFFu, u[1] = w0 >> 16, u[2] = w1 & 0xFFFFu, u[3] = w1 >> 16;
+}
+
+struct hz_ctx {
+    double b, A, dnear, span, sx, sy;
+};
+
+__device__ __forceinline__ hz_ctx hz_make(const float* __restrict__ fog, int n, double dnear, double dfar, int CH, int CW) {
+    hz_ctx k;
+    k.b = (double)fog[2 * n], k.A = (double)fog[2 * n + 1];
+    k.dnear = dnear, k.span = dfar - dnear;
+    k.sx = CW > 1 ? 1.0 / (double)(CW - 1) : 0.0, k.sy = CH > 1 ? 1.0 / (double)(CH - 1) : 0.0;
+    return k;
+}
+
+// one source pixel (y, x) of the window: bytes rgb, depth level u -> the hazed, clamped fp32 values (fog_kernel's expressions)
+template <bool DEPTH>
+__device__ __forceinline__ void hz_pixel(const hz_ctx& k, uint32_t r, uint32_t g, uint32_t bl, uint32_t u, int64_t y, int64_t x,
+                                         float& hr, float& hg, float& hb) {
+    double d;
+    if (DEPTH) {
+        d = k.dnear + k.span * ((double)u / 65535.0);
+    } else {
+        const double dx = (double)x * k.sx - 0.5, dy = (double)y * k.sy - 0.2;
+        d = 0.3 + 0.7 * sqrt(dx * dx + dy * dy);
+    }
+    const double t = exp(-k.b * d);
+    const double a = k.A * (1.0 - t);
+    hr = fminf(fmaxf((float)((double)ds_unit(r) * t + a), 0.f), 1.f);
+    hg = fminf(fmaxf((float)((double)ds_unit(g) * t + a), 0.f), 1.f);
+    hb = fminf(fmaxf((float)((double)ds_unit(bl) * t + a), 0.f), 1.f);
+}
+
+// the pixel at cp / dp, byte by byte (dp is even: one uint16)
+template <bool DEPTH>
+__device__ __forceinline__ void hz_one(const hz_ctx& k, const uint8_t* __restrict__ cp, const uint8_t* __restrict__ dp, int64_t y,
+                                       int64_t x, float& hr, float& hg, float& hb) {
+    const uint32_t u = DEPTH ? (uint32_t)*reinterpret_cast<const uint16_t*>(dp) : 0u;
+    hz_pixel<DEPTH>(k, cp[0], cp[1], cp[2], u, y, x, hr, hg, hb);
+}
+
+// four neighbouring source pixels (y, x .. x + 3) at cp / dp, in source order
+template <bool DEPTH>
+__device__ __forceinline__ void hz_quad(const hz_ctx& k, const uint8_t* __restrict__ cp, const uint8_t* __restrict__ dp, int flags,
+                                        int64_t y, int64_t x, float (&s)[3][DS_QUAD]) {
+    uint32_t px[DS_QUAD * 3], u[DS_QUAD] = {0u, 0u, 0u, 0u};
+    if (flags & DS_WIDE_U8) {
+        uint32_t w[3];
+        ds_load12(cp, w);
+#pragma unroll
+        for (int i = 0; i < DS_QUAD * 3; ++i) px[i] = (w[i >> 2] >> ((i & 3) * 8)) & 255u;
+    } else {
+#pragma unroll
+        for (int i = 0; i < DS_QUAD * 3; ++i) px[i] = cp[i];
+    }
+    if (DEPTH) {
+        if (flags & DS_WIDE_U16) {
+            hz_load8(dp, u);
+        } else {
+#pragma unroll
+            for (int j = 0; j < DS_QUAD; ++j) u[j] = reinterpret_cast<const uint16_t*>(dp)[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < DS_QUAD; ++j) hz_pixel<DEPTH>(k, px[j * 3], px[j * 3 + 1], px[j * 3 + 2], u[j], y, x + j, s[0][j], s[1][j], s[2][j]);
+}
+
+// window_gray_partial_kernel over the hazed window: the same deal of the flat window-pixel number to quads, lanes and blocks and
+// the same order of additions, so the partials are those of a dense copy of the window (and of its depth), bit for bit
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void haze_gray_partial_kernel(const uint8_t* __restrict__ clear, const uint8_t* __restrict__ depth,
+                                                                const int64_t* __restrict__ geom, const float* __restrict__ fog,
+                                                                double dnear, double dfar, const float* __restrict__ params,
+                                                                int CH, int CW, int64_t HW, int flags,
+                                                                double* __restrict__ partial) {
+    const int n = blockIdx.y;
+    const float* p = params + n * 5;
+    const bool bfirst = p[2] != 0.f;
+    const float b = p[3];
+    const hz_ctx k = hz_make(fog, n, dnear, dfar, CH, CW);
+    const uint8_t* __restrict__ win = clear + geom[4 * n];
+    const int64_t pitch = geom[4 * n + 1];
+    const uint8_t* __restrict__ dwin = DEPTH ? depth + geom[4 * n + 2] : nullptr;
+    const int64_t dpitch = DEPTH ? geom[4 * n + 3] : 0;
+    const int64_t step = (int64_t)gridDim.x * 256 * DS_QUAD;
+    const int64_t dy = step / CW;
+    const int64_t dx = step - dy * CW;
+    int64_t i = (blockIdx.x * (int64_t)256 + threadIdx.x) * DS_QUAD;
+    int64_t y = i / CW;
+    int64_t x = i - y * CW;
+    double acc = 0.0;
+    for (; i < HW; i += step) {
+        const int npx = (HW - i) < DS_QUAD ? (int)(HW - i) : DS_QUAD;
+        if (npx == DS_QUAD && x + DS_QUAD <= CW) {
+            float s[3][DS_QUAD];
+            hz_quad<DEPTH>(k, win + y * pitch + x * 3, DEPTH ? dwin + y * dpitch + x * 2 : nullptr, flags, y, x, s);
+#pragma unroll
+            for (int j = 0; j < DS_QUAD; ++j) acc += (double)ds_gray(s[0][j], s[1][j], s[2][j], bfirst, b);
+        } else {
+            int64_t yy = y, xx = x;
+            for (int j = 0; j < npx; ++j, ++xx) {
+                while (xx >= CW) xx -= CW, ++yy;
+                float hr, hg, hb;
+                hz_one<DEPTH>(k, win + yy * pitch + xx * 3, DEPTH ? dwin + yy * dpitch + xx * 2 : nullptr, yy, xx, hr, hg, hb);
+                acc += (double)ds_gray(hr, hg, hb, bfirst, b);
+            }
+        }
+        y += dy, x += dx;
+        if (x >= CW) x -= CW, ++y;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    __shared__ double s4[4];
+    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[(int64_t)n * gridDim.x + blockIdx.x] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+}
+
+// batch_gather_kernel<AUG, true> with the scattering model between the bytes and the transform: the lane's four output pixels
+// are hazed at their source coordinates (row fv ? H - 1 - y : y, columns from fh ? W - 4 - x : x) and arrive reversed under flip_h
+template <bool AUG, bool DEPTH>
+__global__ __launch_bounds__(256) void haze_gather_kernel(const uint8_t* __restrict__ clear, const uint8_t* __restrict__ depth,
+                                                          const int64_t* __restrict__ geom, const float* __restrict__ fog,
+                                                          double dnear, double dfar, const float* __restrict__ params,
+                                                          const double* __restrict__ partial, int nblk, int H, int W,
+                                                          float* __restrict__ out, int flags) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.z;
+    const int64_t plane = (int64_t)H * W;
+    bool fh = false, fv = false, bfirst = false;
+    float b = 1.f, c = 1.f, mean = 0.f;
+    if (AUG) {
+        const float* p = params + n * 5;
+        fh = p[0] != 0.f, fv = p[1] != 0.f, bfirst = p[2] != 0.f;
+        b = p[3], c = p[4];
+        double m = 0.0;                     // batch_gather_kernel's sum of the partials: one order in every lane of every wave
+        for (int i = lane; i < nblk; i += 64) m += partial[(int64_t)n * nblk + i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m += __shfl_xor(m, o, 64);
+        mean = (float)(m / (double)plane);
+    }
+    const int64_t x = ((int64_t)blockIdx.x * 64 + lane) * DS_QUAD;
+    if (x >= W) return;
+    const int npx = (W - x) < DS_QUAD ? (int)(W - x) : DS_QUAD;
+    const hz_ctx k = hz_make(fog, n, dnear, dfar, H, W);
+    const uint8_t* __restrict__ img = clear + geom[4 * n];
+    const int64_t row_pitch = geom[4 * n + 1];
+    const uint8_t* __restrict__ dimg = DEPTH ? depth + geom[4 * n + 2] : nullptr;
+    const int64_t dpitch = DEPTH ? geom[4 * n + 3] : 0;
+    float* __restrict__ dst = out + (int64_t)n * 3 * plane;
+    for (int64_t y = (int64_t)blockIdx.y * DS_ROWS + (threadIdx.x >> 6); y < H; y += (int64_t)gridDim.y * DS_ROWS) {
+        const int64_t sy = fv ? H - 1 - y : y;
+        const uint8_t* __restrict__ row = img + sy * row_pitch;
+        const uint8_t* __restrict__ drow = DEPTH ? dimg + sy * dpitch : nullptr;
+        float v[3][DS_QUAD];
+        if (npx == DS_QUAD) {
+            const int64_t sx = fh ? W - DS_QUAD - x : x;
+            float s[3][DS_QUAD];
+            hz_quad<DEPTH>(k, row + sx * 3, DEPTH ? drow + sx * 2 : nullptr, flags, sy, sx, s);
+#pragma unroll
+            for (int j = 0; j < DS_QUAD; ++j)
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) v[ch][j] = fh ? s[ch][DS_QUAD - 1 - j] : s[ch][j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < DS_QUAD; ++j) {
+                v[0][j] = v[1][j] = v[2][j] = 0.0f;
+                if (j < npx) {
+                    const int64_t sx = fh ? W - 1 - (x + j) : x + j;
+                    hz_one<DEPTH>(k, row + sx * 3, DEPTH ? drow + sx * 2 : nullptr, sy, sx, v[0][j], v[1][j], v[2][j]);
+                }
+            }
+        }
+        if (AUG) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+                for (int j = 0; j < DS_QUAD; ++j) {
+                    float t = v[ch][j];         // aug_apply_kernel's expressions
+                    if (bfirst) {
+                        t = fminf(fmaxf(b * t, 0.f), 1.f);
+                        t = fminf(fmaxf(c * t + (1.f - c) * mean, 0.f), 1.f);
+                    } else {
+                        t = fminf(fmaxf(c * t + (1.f - c) * mean, 0.f), 1.f);
+                        t = fminf(fmaxf(b * t, 0.f), 1.f);
+                    }
+                    v[ch][j] = t;
+                }
+        }
+        float* __restrict__ o = dst + y * W + x;
+        if (npx == DS_QUAD && (flags & DS_WIDE_F32)) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                f32x4 q;
+#pragma unroll
+                for (int j = 0; j < DS_QUAD; ++j) q[j] = v[ch][j];
+                *reinterpret_cast<f32x4*>(o + ch * plane) = q;
+            }
+        } else {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+                for (int j = 0; j < DS_QUAD; ++j)
+                    if (j < npx) o[ch * plane + j] = v[ch][j];
+        }
+    }
+}
+
+// B: bytes per source pixel.  u8_resize_kernel's arithmetic on one channel of 16-bit levels.
+template <int B>
+__global__ __launch_bounds__(256) void u16_resize_kernel(const uint8_t* __restrict__ src, int64_t row_pitch, int H, int W,
+                                                         uint16_t* __restrict__ dst, int OH, int OW) {
+    const int64_t total = (int64_t)OH * OW;
+    for (int64_t t = blockIdx.x * (int64_t)256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
+        const int oy = (int)(t / OW), ox = (int)(t - (int64_t)oy * OW);
+        int y0, y1, x0, x1;
+        float ly, lx;
+        ds_src(oy, H, OH, y0, y1, ly);
+        ds_src(ox, W, OW, x0, x1, lx);
+        const float hy = 1.f - ly, hx = 1.f - lx;
+        const uint8_t* __restrict__ r0 = src + (int64_t)y0 * row_pitch;
+        const uint8_t* __restrict__ r1 = src + (int64_t)y1 * row_pitch;
+        float v00, v01, v10, v11;
+        if (B == 1) {
+            v00 = (float)(r0[x0] * 257u), v01 = (float)(r0[x1] * 257u);
+            v10 = (float)(r1[x0] * 257u), v11 = (float)(r1[x1] * 257u);
+        } else {
+            v00 = (float)reinterpret_cast<const uint16_t*>(r0)[x0], v01 = (float)reinterpret_cast<const uint16_t*>(r0)[x1];
+            v10 = (float)reinterpret_cast<const uint16_t*>(r1)[x0], v11 = (float)reinterpret_cast<const uint16_t*>(r1)[x1];
+        }
+        const float r = (v00 * hx + v01 * lx) * hy + (v10 * hx + v11 * lx) * ly;
+        dst[t] = (uint16_t)(int)fminf(fmaxf(rintf(r), 0.f), 65535.f);      // halves to even
+    }
+}
+
+extern "C" int adh_u16_resize_bilinear(void* stream, const uint8_t* src, int64_t src_pitch_bytes, int h, int w, int bytes_per_px,
+                                       void* dst_u16, int OH, int OW) {
+    uint16_t* dst = reinterpret_cast<uint16_t*>(dst_u16);
+    if (!src || !dst_u16 || h < 1 || w < 1 || OH < 1 || OW < 1) return ADH_E_ARG;
+    if (bytes_per_px != 1 && bytes_per_px != 2) return ADH_E_ARG;
+    if (src_pitch_bytes < (int64_t)w * bytes_per_px) return ADH_E_ARG;
+    if ((uintptr_t)dst_u16 & 1) return ADH_E_ARG;
+    if (bytes_per_px == 2 && ((((uintptr_t)src) | (uintptr_t)src_pitch_bytes) & 1)) return ADH_E_ARG;
+    const dim3 grid((unsigned)adh_min_i(adh_ceil_div((int64_t)OH * OW, 256), DS_MAXBLK_RESIZE));
+    if (bytes_per_px == 1)
+        hipLaunchKernelGGL(u16_resize_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, src_pitch_bytes, h, w, dst, OH, OW);
+    else
+        hipLaunchKernelGGL(u16_resize_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, src, src_pitch_bytes, h, w, dst, OH, OW);
+    return adh_check_launch();
+}
+
+extern "C" int adh_batch_haze_from_u8(void* stream, const uint8_t* clear, int64_t clear_bytes, const void* depth,
+                                      int64_t depth_bytes, const int64_t* geom, const float* fog, double depth_near,
+                                      double depth_far, const float* params, int N, int CH, int CW, double* partial, int nblk,
+                                      float* out_nchw) {
+    if (!clear || !geom || !fog || !out_nchw || (params && !partial)) return ADH_E_ARG;
+    if (N < 1 || N > 65535 || CH < 1 || CW < 1) return ADH_E_ARG;
+    const int64_t HW = (int64_t)CH * CW;
+    if (HW > INT64_MAX / 3 || clear_bytes < HW * 3) return ADH_E_ARG;
+    if (depth && ((((uintptr_t)depth) & 1) || depth_bytes < HW * 2)) return ADH_E_ARG;
+    if (nblk != adh_batch_num_blocks(HW)) return ADH_E_ARG;
+    // aligned dwords around any byte of a cache stay inside it when it starts and ends on a multiple of 4
+    const bool al4 = ((((uintptr_t)clear) | (uintptr_t)clear_bytes) & 3) == 0;
+    const bool dal4 = depth && ((((uintptr_t)depth) | (uintptr_t)depth_bytes) & 3) == 0;
+    const int flags = (al4 ? DS_WIDE_U8 : 0) | (dal4 ? DS_WIDE_U16 : 0) |
+                      (((((uintptr_t)out_nchw) & 15) == 0 && (CW & 3) == 0) ? DS_WIDE_F32 : 0);
+    const uint8_t* dbytes = reinterpret_cast<const uint8_t*>(depth);
+    const dim3 grid((unsigned)adh_ceil_div(CW, 64 * DS_QUAD), (unsigned)adh_min_i(adh_ceil_div(CH, DS_ROWS), 65535), (unsigned)N);
+#define HZ_LAUNCH(D)                                                                                                              \
+    if (params) {                                                                                                                 \
+        hipLaunchKernelGGL((haze_gray_partial_kernel<D>), dim3(nblk, N), dim3(256), 0, (hipStream_t)stream, clear, dbytes, geom,  \
+                           fog, depth_near, depth_far, params, CH, CW, HW, flags, partial);                                       \
+        hipLaunchKernelGGL((haze_gather_kernel<true, D>), grid, dim3(256), 0, (hipStream_t)stream, clear, dbytes, geom, fog,      \
+                           depth_near, depth_far, params, partial, nblk, CH, CW, out_nchw, flags);                                \
+    } else {                                                                                                                      \
+        hipLaunchKernelGGL((haze_gather_kernel<false, D>), grid, dim3(256), 0, (hipStream_t)stream, clear, dbytes, geom, fog,     \
+                           depth_near, depth_far, params, partial, nblk, CH, CW, out_nchw, flags);                                \
+    }
+    if (depth) {
+        HZ_LAUNCH(true)
+    } else {
+        HZ_LAUNCH(false)
+    }
+#undef HZ_LAUNCH
+    return adh_check_launch();
+}

@@ -16,12 +16,17 @@ bytes per pixel).  `epoch_plan` is the pure host function that decides which sam
 and a batch is random (train) or centre crops of them, assembled by `adh_batch_window_from_u8` from a byte offset and a row
 pitch per sample (`batch_from_windows`, `draw_crop_origins`, `centre_origins`, `upscaled_size`).  There are no worker processes and no streaming loader: a split that does not fit
 in half of the free device memory is refused.
+
+Clear images plus depth maps (`dataset.synthetic_haze`, the RESIDE recipe): `haze_index` lists `<split>/clear/<name>` with
+`depth/<stem>.png`, `HazeSynthDataset` keeps the clear bytes and a uint16 depth cache on the device, and `batch_haze_from_windows`
+renders the hazy role of every batch from them (`adh_batch_haze_from_u8`: the scattering model at source pixels, then the paired
+transform), under a fresh (label, beta, A) per sample and epoch from `draw_haze_params`.
 """
 from __future__ import annotations
 
 import os
 from concurrent.futures import ThreadPoolExecutor
-from typing import Callable, Dict, Iterator, List, Optional, Sequence, Union
+from typing import Callable, Dict, Iterator, List, Mapping, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -463,7 +468,370 @@ class FolderDataset:
                    "name": [self.names[i] for i in index.tolist()]}
 
 
-_CACHES: Dict[tuple, FolderDataset] = {}     # (resolved split directory, split, (h, w), device, rank, world, crop) -> the built cache
+# ---------------------------------------------------------------------------------------------------------------- haze synthesis
+DEPTH_SOURCES = ("folder", "radial")
+DEFAULT_DEPTH_RANGE = (0.3, 1.0)      # the span of the reference's radial depth map (helpers.py:247)
+
+
+def draw_haze_params(n: int, rng):
+    """(labels int64 [n], fog float32 [n,2] = {beta, A}) for n synthesized samples.  Per sample, in order: `rng.randint(0, 3)` (the
+    density label), then beta and A from `FOG_RANGES[LEVEL_NAMES[label]]` in `draw_fog_params`' order."""
+    labels, fog = [], []
+    for _ in range(n):
+        label = int(rng.randint(0, 3))
+        beta, A = draw_fog_params([LEVEL_NAMES[label]], rng)
+        labels.append(label)
+        fog.append([float(beta[0]), float(A[0])])
+    return torch.tensor(labels, dtype=torch.int64), torch.tensor(fog, dtype=torch.float32).reshape(n, 2)
+
+
+def fixed_haze_params(seed: int, samples):
+    """`draw_haze_params` for evaluation: sample number g of the index (not of a shard) draws from RandomState((seed, g)) and from
+    nothing else, so its (label, beta, A) are the same in every epoch, on every rank and for every world size."""
+    drawn = [draw_haze_params(1, np.random.RandomState((int(seed) % 2 ** 32, int(g)))) for g in samples]
+    return torch.cat([d[0] for d in drawn]), torch.cat([d[1] for d in drawn])
+
+
+def batch_haze_from_windows(clear: torch.Tensor, depth: Optional[torch.Tensor], geom: torch.Tensor, fog: torch.Tensor, crop,
+                            params: Optional[torch.Tensor] = None, depth_range=DEFAULT_DEPTH_RANGE) -> torch.Tensor:
+    """The hazy role of a batch rendered from clear pixels: float32 [N,3,CH,CW] = augment(fog(window)) by `adh_batch_haze_from_u8`.
+    `clear` is a dense uint8 device tensor of interleaved RGB (the flat cache of crop mode or [M,H,W,3]), `depth` a dense uint16
+    device tensor (flat or [M,H,W]) or None for the reference's radial depth over the window.  `geom` (CPU int64 [N,4], bytes):
+    {clear offset of the window's first pixel, clear row pitch, depth offset, depth row pitch}; the last two are ignored without
+    `depth`.  `fog` float32 [N,2] = {beta, A} (`draw_haze_params`), on the CPU or already on the cache's device.  Per pixel
+    t = exp(-beta * d) in float64 with d = near + (far - near) * level / 65535 (`depth_range` = (near, far)), hazy =
+    clamp(J * t + A * (1 - t)); with `params` the train transform follows in the same pass, its grey mean taken over the hazed
+    window.  Everything is checked here, on the host, before anything touches the device, because the kernel does not validate
+    `geom`: TypeError for a wrong index type, ValueError for an odd depth offset or pitch or a depth pitch below CW * 2,
+    IndexError when a window leaves either cache, RuntimeError for a cache that is not on a cuda device."""
+    if not isinstance(geom, torch.Tensor) or geom.is_cuda or geom.dtype != torch.int64 or geom.dim() != 2 or geom.shape[1] != 4:
+        raise TypeError("batch_haze_from_windows: geom must be an int64 [N,4] tensor on the CPU")
+    if not isinstance(clear, torch.Tensor) or (depth is not None and not isinstance(depth, torch.Tensor)):
+        raise TypeError("batch_haze_from_windows: the caches must be tensors")
+    CH, CW = _size2(crop)
+    if CH < 1 or CW < 1:
+        raise ValueError(f"batch_haze_from_windows: crop must be at least 1 x 1, got {(CH, CW)}")
+    N = geom.shape[0]
+    if N < 1:
+        raise ValueError("batch_haze_from_windows: no windows")
+    if not isinstance(fog, torch.Tensor) or tuple(fog.shape) != (N, 2):
+        raise ValueError(f"batch_haze_from_windows: fog must be a [{N},2] tensor of (beta, A)")
+    if params is not None and tuple(params.shape) != (N, 5):
+        raise ValueError(f"batch_haze_from_windows: params must be [{N},5], got {tuple(params.shape)}")
+    near, far = (float(v) for v in depth_range)
+    if not (np.isfinite(near) and np.isfinite(far)):
+        raise ValueError(f"batch_haze_from_windows: depth_range must be finite, got {depth_range}")
+    rows = geom.tolist()                                                                                    # Python ints: no wrap
+    if depth is not None and any(do % 2 or dp % 2 or dp < CW * 2 for _, _, do, dp in rows):
+        raise ValueError(f"batch_haze_from_windows: depth offsets and pitches must be even and a pitch at least {CW * 2} bytes: "
+                         f"{rows}")
+    cbytes = clear.numel() * clear.element_size()
+    if any(o < 0 or p < CW * 3 or o + (CH - 1) * p + CW * 3 > cbytes for o, p, _, _ in rows):
+        raise IndexError(f"batch_haze_from_windows: a {CH}x{CW} window leaves a clear cache of {cbytes} bytes: {rows}")
+    dbytes = 0 if depth is None else depth.numel() * depth.element_size()
+    if depth is not None and any(do < 0 or do + (CH - 1) * dp + CW * 2 > dbytes for _, _, do, dp in rows):
+        raise IndexError(f"batch_haze_from_windows: a {CH}x{CW} window leaves a depth cache of {dbytes} bytes: {rows}")
+    for c, dt in ((clear, torch.uint8), (depth, torch.uint16)):
+        if c is not None and (not c.is_cuda or c.dtype != dt or not c.is_contiguous() or c.device != clear.device):
+            raise RuntimeError(f"adam-dehaze_amd: the cache must be a dense {dt} tensor on one cuda device, got {c.dtype} on "
+                               f"{c.device} (no CPU fallback)")
+    nblk = H.value("adh_batch_num_blocks", CH * CW)
+    with torch.cuda.device(clear.device):
+        gd = geom.contiguous().to(clear.device)
+        fd = fog.to(device=clear.device, dtype=torch.float32).contiguous()
+        pd = None if params is None else params.to(device=clear.device, dtype=torch.float32).contiguous()
+        partial = None if pd is None else torch.empty(N * nblk, device=clear.device, dtype=torch.float64)
+        out = torch.empty((N, 3, CH, CW), device=clear.device, dtype=torch.float32)
+        H.call("adh_batch_haze_from_u8", clear.data_ptr(), cbytes, H.ptr(depth), dbytes, gd.data_ptr(), fd.data_ptr(), near, far,
+               H.ptr(pd), N, CH, CW, H.ptr(partial), nblk, out.data_ptr())
+    return out
+
+
+def _haze_dir(root: str, split: str) -> Optional[str]:
+    """the directory that holds clear/ for `split`: <root>/<split>, else <root> itself, else None"""
+    if not root:
+        return None
+    for d in (os.path.join(root, split), root):
+        if os.path.isdir(os.path.join(d, "clear")):
+            return d
+    return None
+
+
+def haze_index(root: str, split: str, depth: str = "folder") -> Optional[FolderIndex]:
+    """The clear images of one split for haze synthesis, as records {clear, depth, name} sorted by name, or None when there is no
+    `<root>/<split>/clear` and no `<root>/clear` directory.  Names must end in `.jpg` or `.png` (`folder_index`'s rule).  With
+    `depth` 'folder' every record pairs with `depth/<stem>.png` beside `clear/`: a missing depth file raises FileNotFoundError
+    and names it, a depth file whose size differs from its clear file's raises ValueError (both sizes come from the headers;
+    nothing is decoded).  With 'radial' the records' `depth` is None and no depth folder is looked for."""
+    if depth not in DEPTH_SOURCES:
+        raise ValueError(f"dataset.synthetic_haze.depth must be one of {DEPTH_SOURCES}, got {depth!r}")
+    d = _haze_dir(root, split)
+    if d is None:
+        return None
+    from .image_io import image_size
+    out = FolderIndex()
+    out.split_dir = d
+    for name in sorted(os.listdir(os.path.join(d, "clear"))):
+        clear = os.path.join(d, "clear", name)
+        if not name.endswith(IMAGE_SUFFIXES) or not os.path.isfile(clear):
+            continue
+        dpath = None
+        if depth == "folder":
+            dpath = os.path.join(d, "depth", os.path.splitext(name)[0] + ".png")
+            if not os.path.isfile(dpath):
+                raise FileNotFoundError(f"{clear} has no depth map: {dpath} does not exist (dataset.synthetic_haze.depth: radial "
+                                        f"needs none)")
+            try:
+                cs, dsz = image_size(clear), image_size(dpath)
+            except Exception as e:
+                raise RuntimeError(f"cannot read the header of {clear} or {dpath}: {e}") from e
+            if cs != dsz:
+                raise ValueError(f"a depth map differs in size from its image: {dpath} is {dsz[0]}x{dsz[1]}, {clear} is "
+                                 f"{cs[0]}x{cs[1]}")
+        out.append({"clear": clear, "depth": dpath, "name": name})
+    return out
+
+
+class HazeSynthDataset:
+    """One split of clear images (and their depth maps), resident on `device`, whose hazy role is rendered every step by
+    `adh_batch_haze_from_u8`: `clear` uint8 and `depth` uint16 (None with `depth` 'radial'), for this rank's shard of the records
+    of `haze_index` (samples rank, rank + world, ...).  The sibling of `FolderDataset`, with the same two layouts: dense at
+    `img_size` ([L,H,W,3] and [L,H,W]; clear files through `adh_u8_resize_bilinear`, depth files through
+    `adh_u16_resize_bilinear`), or with `crop_size` flat at the files' own sizes (`upscaled_size` where a crop does not fit), image
+    k's pixels at byte `offsets[k]` and its depth at byte `depth_offsets[k]`, both multiples of 4.  The memory check counts 5 bytes
+    per pixel, 3 without depth maps.  `depth_range` = (near, far): the scene depth of levels 0 and 65535."""
+
+    def __init__(self, records: Sequence[Dict], img_size, device, rank: int = 0, world: int = 1, threads: int = 4,
+                 split: str = "train", crop_size=None, depth: str = "folder", depth_range=DEFAULT_DEPTH_RANGE):
+        from .image_io import image_size, load_depth, load_image
+        if depth not in DEPTH_SOURCES:
+            raise ValueError(f"dataset.synthetic_haze.depth must be one of {DEPTH_SOURCES}, got {depth!r}")
+        self.H, self.W = _size2(img_size)
+        self.crop = None if crop_size is None else _size2(crop_size)
+        self.device = torch.device(device)
+        self.rank, self.world, self.total = rank, world, len(records)
+        self.depth_source, self.depth_range = depth, (float(depth_range[0]), float(depth_range[1]))
+        own = list(records[rank::world])
+        self.names = [r["name"] for r in own]
+        L = len(own)
+        nthreads = max(1, min(int(threads), MAX_DECODE_THREADS))
+        per_px = 5 if depth == "folder" else 3
+        if self.crop is None:
+            pixels, what, advice = L * self.H * self.W, f"{self.H}x{self.W}", "a smaller dataset.img_size"
+            need = per_px * pixels
+        else:
+            def header(path):
+                try:
+                    return image_size(path)
+                except Exception as e:
+                    raise RuntimeError(f"cannot read image file {path}: {e}") from e
+            with ThreadPoolExecutor(nthreads) as pool:
+                own_sizes = list(pool.map(header, [r["clear"] for r in own]))
+            sizes, offsets, doffsets, at, dat, upscaled = [], [], [], 0, 0, 0
+            for hs in own_sizes:
+                size = upscaled_size(hs[0], hs[1], self.crop)
+                upscaled += size != tuple(hs)
+                sizes.append(size)
+                offsets.append(at)
+                doffsets.append(dat)
+                at += -(-size[0] * size[1] * 3 // 4) * 4             # every slot of either cache starts on a multiple of 4
+                dat += -(-size[0] * size[1] * 2 // 4) * 4
+            self.sizes = np.array(sizes, dtype=np.int64).reshape(-1, 2)
+            self.offsets, self.depth_offsets = np.array(offsets, dtype=np.int64), np.array(doffsets, dtype=np.int64)
+            self.cache_bytes, self.depth_bytes = at, dat
+            need, advice = at + (dat if depth == "folder" else 0), "a smaller dataset"
+            what = f"their own sizes ({upscaled} upscaled to hold a {self.crop[0]}x{self.crop[1]} crop)"
+        if self.device.type != "cuda":
+            raise RuntimeError(f"adam-dehaze_amd: the dataset cache lives on a cuda device, got {self.device} (no CPU fallback)")
+        free = torch.cuda.mem_get_info(self.device)[0]
+        if need > free // 2:
+            raise RuntimeError(f"the {split} split needs {need} bytes of device memory as a cache of clear images"
+                               f"{' and depth maps' if depth == 'folder' else ''} ({L} images at {what}, {per_px} bytes per "
+                               f"pixel), more than half of the {free} bytes free on {self.device}; a streaming loader is not "
+                               f"built: use {advice} or more ranks")
+        if self.crop is None:
+            self.clear = torch.empty((L, self.H, self.W, 3), dtype=torch.uint8, device=self.device)
+            self.depth = torch.empty((L, self.H, self.W), dtype=torch.uint16, device=self.device) if depth == "folder" else None
+        else:
+            self.clear = torch.empty((self.cache_bytes,), dtype=torch.uint8, device=self.device)
+            self.depth = torch.empty((self.depth_bytes // 2,), dtype=torch.uint16, device=self.device) if depth == "folder" else None
+
+        def decode(job):
+            try:
+                return load_depth(job[2], raw=True) if job[0] == "depth" else load_image(job[2])
+            except Exception as e:
+                raise RuntimeError(f"cannot read image file {job[2]}: {e}") from e
+        jobs = [(role, slot, r[role]) for slot, r in enumerate(own) for role in ("clear", "depth") if r.get(role) is not None
+                and (role == "clear" or depth == "folder")]
+        with ThreadPoolExecutor(nthreads) as pool, torch.cuda.device(self.device):
+            for at in range(0, len(jobs), 4 * nthreads):        # a few files per thread in flight: decoded files do not pile up
+                chunk = jobs[at:at + 4 * nthreads]
+                for (role, slot, path), img in zip(chunk, pool.map(decode, chunk)):
+                    h, w = img.shape[:2]
+                    oh, ow = (self.H, self.W) if self.crop is None else self.sizes[slot].tolist()
+                    src = img.contiguous().to(self.device)
+                    if role == "clear":
+                        at_byte = slot * oh * ow * 3 if self.crop is None else int(self.offsets[slot])
+                        c = img.shape[2]
+                        H.call("adh_u8_resize_bilinear", src.data_ptr(), w * c, h, w, c, self.clear.data_ptr() + at_byte, oh, ow)
+                    else:
+                        at_byte = slot * oh * ow * 2 if self.crop is None else int(self.depth_offsets[slot])
+                        bpp = img.element_size()
+                        H.call("adh_u16_resize_bilinear", src.data_ptr(), w * bpp, h, w, bpp, self.depth.data_ptr() + at_byte, oh, ow)
+        print(f"Loaded {self.total} clear images for {split} split (haze synthesized on the device, depth: {depth})")
+        print(f"  device cache: {L} images at {what} on {self.device}, {need / 2 ** 20:.1f} MiB ({need} bytes)"
+              + (f" (rank {rank} of {world})" if world > 1 else ""))
+
+    def __len__(self):
+        return len(self.names)
+
+    def geometry(self, index: np.ndarray, origins: Optional[np.ndarray] = None) -> torch.Tensor:
+        """int64 [n,4] rows of `batch_haze_from_windows` for the shard's images `index`: dense mode {i*H*W*3, W*3, i*H*W*2, W*2},
+        crop mode the windows at `origins` [n,2] (y0, x0)"""
+        index = np.asarray(index, dtype=np.int64)
+        if self.crop is None:
+            px = self.H * self.W
+            g = np.stack([index * px * 3, np.full_like(index, self.W * 3), index * px * 2, np.full_like(index, self.W * 2)], axis=1)
+        else:
+            sizes, origins = self.sizes[index], np.asarray(origins, dtype=np.int64)
+            at = origins[:, 0] * sizes[:, 1] + origins[:, 1]
+            g = np.stack([self.offsets[index] + at * 3, sizes[:, 1] * 3, self.depth_offsets[index] + at * 2, sizes[:, 1] * 2], axis=1)
+        return torch.from_numpy(np.ascontiguousarray(g, dtype=np.int64))
+
+    def epoch(self, epoch: int, batch_size: int, seed: int, train: bool, augment: bool = True) -> Iterator[Dict]:
+        """The batch dicts of `FolderDataset.epoch` plus 'beta' and 'airlight' (float32 [n], device), in the order of `epoch_plan`;
+        'intensity' is the drawn density label.  train: from this loader's RandomState(seed + 1000 * rank + epoch), per batch, the
+        augment rows (when `augment`), the crop origins (crop mode), then `draw_haze_params`: every epoch re-renders every image
+        under fresh haze.  Otherwise: the centre crop, no rows, and `fixed_haze_params(seed, sample numbers)`, the same in every
+        epoch and for every world size.  The clear role comes from `batch_from_cache` / `batch_from_windows` with the same rows."""
+        if self.total == 0 or (not train and len(self) == 0):
+            return
+        rng = np.random.RandomState(seed + 1000 * self.rank + epoch)
+        for samples in epoch_plan(self.total, self.world, self.rank, batch_size, seed, epoch, train):
+            index = torch.from_numpy((samples - self.rank) // self.world)
+            params = draw_augment_params(index.numel(), rng) if train and augment else None
+            origins = None
+            if self.crop is not None:
+                sizes = self.sizes[index.numpy()]
+                origins = draw_crop_origins(sizes, self.crop, rng) if train else centre_origins(sizes, self.crop)
+            labels, fog = draw_haze_params(index.numel(), rng) if train else fixed_haze_params(seed, samples)
+            geom = self.geometry(index.numpy(), origins)
+            fog = fog.to(self.device)
+            hazy = batch_haze_from_windows(self.clear, self.depth, geom, fog, self.crop or (self.H, self.W), params,
+                                           self.depth_range)
+            if self.crop is None:
+                clear = batch_from_cache(self.clear, index, params)
+            else:
+                clear = batch_from_windows(self.clear, geom[:, :2].contiguous(), self.crop, params)
+            yield {"hazy": hazy, "clear": clear, "intensity": labels.to(self.device), "beta": fog[:, 0].contiguous(),
+                   "airlight": fog[:, 1].contiguous(), "name": [self.names[i] for i in index.tolist()]}
+
+
+def synthesize_tree(input_dir: str, output_dir: str, depth_dir: Optional[str] = None, seed: int = 0, device="cuda",
+                    depth_range=DEFAULT_DEPTH_RANGE) -> List[Dict]:
+    """`main.py --mode synthesize`: every `.jpg` / `.png` file of `input_dir` (sorted) rendered once per density level at its own
+    size, as `<output_dir>/{low,medium,high}/{hazy,clear}/<stem>.png` -- the layout `folder_index` reads -- plus
+    `<output_dir>/synthesize.json` with each file's beta and A.  The hazy bytes are `image_io.image_to_u8` of what
+    `batch_haze_from_windows` gives for the whole image (no rows), i.e. what training with `dataset.synthetic_haze` sees for that
+    (beta, A); the clear file holds the cached RGB bytes.  `depth_dir`: `<stem>.png` per clear file (a missing or differently
+    sized one raises); None: the reference's radial depth map.  Per file, in order, from RandomState(seed): (beta, A) of low, of
+    medium, of high (`draw_fog_params`).  Returns the records written to the json."""
+    import json
+    from .image_io import image_size, image_to_u8, load_depth, load_image, save_image
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"adam-dehaze_amd: haze is synthesized on a cuda device, got {device} (no CPU fallback)")
+    if not os.path.isdir(input_dir):
+        raise ValueError(f"--input {input_dir}: not a directory of clear images")
+    names = [n for n in sorted(os.listdir(input_dir)) if n.endswith(IMAGE_SUFFIXES) and os.path.isfile(os.path.join(input_dir, n))]
+    if not names:
+        raise ValueError(f"--input {input_dir}: no .jpg or .png file")
+    stems = [os.path.splitext(n)[0] for n in names]
+    twice = sorted({s for s in stems if stems.count(s) > 1})
+    if twice:
+        raise ValueError(f"input files share a base name and would overwrite each other's output: {', '.join(twice)}")
+    for level in LEVEL_NAMES:
+        for role in ("hazy", "clear"):
+            os.makedirs(os.path.join(output_dir, level, role), exist_ok=True)
+    rng = np.random.RandomState(seed)
+    records = []
+    with torch.cuda.device(device):
+        for name, stem in zip(names, stems):
+            path = os.path.join(input_dir, name)
+            img = load_image(path)
+            h, w, c = img.shape
+            clear = torch.empty((h * w * 3 + 3) // 4 * 4, dtype=torch.uint8, device=device)
+            H.call("adh_u8_resize_bilinear", img.contiguous().to(device).data_ptr(), w * c, h, w, c, clear.data_ptr(), h, w)
+            depth, dpath = None, None
+            if depth_dir is not None:
+                dpath = os.path.join(depth_dir, stem + ".png")
+                if not os.path.isfile(dpath):
+                    raise FileNotFoundError(f"{path} has no depth map: {dpath} does not exist")
+                if image_size(dpath) != (h, w):
+                    raise ValueError(f"a depth map differs in size from its image: {dpath} is {image_size(dpath)}, {path} is {(h, w)}")
+                d = load_depth(dpath, raw=True)
+                depth = torch.empty((h * w + 1) // 2 * 2, dtype=torch.uint16, device=device)
+                H.call("adh_u16_resize_bilinear", d.contiguous().to(device).data_ptr(), w * d.element_size(), h, w, d.element_size(),
+                       depth.data_ptr(), h, w)
+            beta, A = draw_fog_params(LEVEL_NAMES, rng)
+            fog = torch.stack([beta, A], dim=1).to(torch.float32)
+            geom = torch.tensor([[0, w * 3, 0, w * 2]] * len(LEVEL_NAMES), dtype=torch.int64)
+            hazy = image_to_u8(batch_haze_from_windows(clear, depth, geom, fog, (h, w), None, depth_range)).cpu()
+            clear_host = clear[:h * w * 3].reshape(h, w, 3).cpu()
+            for k, level in enumerate(LEVEL_NAMES):
+                save_image(os.path.join(output_dir, level, "hazy", stem + ".png"), hazy[k])
+                save_image(os.path.join(output_dir, level, "clear", stem + ".png"), clear_host)
+                records.append({"file": path, "depth": dpath, "level": level, "name": stem + ".png", "height": h, "width": w,
+                                "beta": float(fog[k, 0]), "airlight": float(fog[k, 1])})
+    with open(os.path.join(output_dir, "synthesize.json"), "w") as f:
+        json.dump({"seed": int(seed), "depth_range": [float(v) for v in depth_range], "files": records}, f, indent=2)
+    print(f"synthesized {len(names)} clear files at 3 levels into {output_dir}")
+    return records
+
+
+def _haze_loader(config, ds, settings, split: str, device, rank: Optional[int], world: Optional[int]) -> Callable:
+    """`folder_loader` for `dataset.synthetic_haze` = `settings`"""
+    unknown = sorted(set(settings) - {"depth", "depth_range"})
+    if unknown:
+        raise ValueError(f"dataset.synthetic_haze: unknown keys {unknown} (known: depth, depth_range)")
+    depth = settings.get("depth", "folder")
+    if depth not in DEPTH_SOURCES:
+        raise ValueError(f"dataset.synthetic_haze.depth must be one of {DEPTH_SOURCES}, got {depth!r}")
+    rng_ = settings.get("depth_range", list(DEFAULT_DEPTH_RANGE))
+    if not isinstance(rng_, (list, tuple)) or len(rng_) != 2:
+        raise ValueError(f"dataset.synthetic_haze.depth_range must be [near, far], got {rng_!r}")
+    depth_range = (float(rng_[0]), float(rng_[1]))
+    root = ds.get({"train": "train_path", "val": "val_path"}.get(split, "test_path"))
+    split_dir = _haze_dir(root, split)
+    if split_dir is None:
+        raise RuntimeError(f"dataset.synthetic_haze is configured but the {split} split has no clear/ folder under {root!r} (looked "
+                           f"for <root>/{split}/clear and <root>/clear); noise frames are not substituted")
+    rank = int(os.environ.get("RANK", "0")) if rank is None else rank
+    world = int(os.environ.get("WORLD_SIZE", "1")) if world is None else world
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    crop = ds.get("crop_size")
+    crop = None if crop is None else _size2(crop)
+    key = ("synthetic_haze", os.path.realpath(split_dir), split, _size2(ds["img_size"]), str(device), rank, world, crop, depth,
+           depth_range)
+    if key not in _CACHES:
+        records = haze_index(root, split, depth)
+        if not records:
+            raise RuntimeError(f"{split_dir}/clear: the {split} split has no .jpg or .png file")
+        _CACHES[key] = HazeSynthDataset(records, ds["img_size"], device, rank, world, threads=int(ds.get("num_workers", 4)),
+                                        split=split, crop_size=crop, depth=depth, depth_range=depth_range)
+    cache = _CACHES[key]
+    batch_size, seed, train = int(ds["batch_size"]), int(config.get("seed", 0)), split == "train"
+    augment = bool(ds.get("augmentation", True))
+
+    def epochs(epoch=0):
+        return cache.epoch(epoch, batch_size, seed, train, augment)
+    epochs.dataset = cache          # the resident cache, for a caller that wants to look at what is served
+    return epochs
+
+
+_CACHES: Dict[tuple, object] = {}     # (resolved split directory, split, (h, w), device, rank, world, crop) -> the built cache
 
 
 def folder_loader(config, split: str, device, rank: Optional[int] = None, world: Optional[int] = None) -> Optional[Callable]:
@@ -472,8 +840,14 @@ def folder_loader(config, split: str, device, rank: Optional[int] = None, world:
     default to the process's RANK / WORLD_SIZE.  The cache of a split is built once per process and kept, so the stages of
     train_all and the evaluators share it.  `dataset.num_workers` is the number of decode threads.  `dataset.crop_size` (int or
     [h, w]; absent or null: off) caches every pair at its own resolution and serves random crops of that size to training and
-    centre crops to validation and test (`FolderDataset`); the synthetic fallback does not read it and keeps using `img_size`."""
+    centre crops to validation and test (`FolderDataset`); the synthetic fallback does not read it and keeps using `img_size`.
+    `dataset.synthetic_haze` (a mapping; absent: off) trains from clear images instead: `<root>/<split>/clear/<name>` (else
+    `<root>/clear/<name>`) with `depth/<stem>.png` beside it, the hazy role rendered on the device every step
+    (`HazeSynthDataset`).  Keys: `depth: folder | radial` (default folder) and `depth_range: [near, far]` (default [0.3, 1.0]); both
+    join the cache key.  A configured `synthetic_haze` whose split has no `clear/` folder raises."""
     ds = config.get("dataset", {})
+    if isinstance(ds.get("synthetic_haze"), Mapping):
+        return _haze_loader(config, ds, ds["synthetic_haze"], split, device, rank, world)
     root = ds.get({"train": "train_path", "val": "val_path"}.get(split, "test_path"))
     split_dir = _split_dir(root, split)
     if split_dir is None:

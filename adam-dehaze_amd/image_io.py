@@ -116,6 +116,25 @@ def load_image(path: str, orientation: bool = False):
     return (t, tag) if orientation else t
 
 
+DEPTH_MODES_16 = ("I;16", "I;16L", "I;16B", "I;16N")
+
+
+def load_depth(path: str, raw: bool = False) -> torch.Tensor:
+    """A single-channel depth file as a uint16 [h,w] CPU tensor of levels 0..65535: 16-bit grey (Pillow's I;16 modes) as stored,
+    8-bit grey (L) promoted to v * 257, so that v / 255 == v * 257 / 65535.  `raw`: an 8-bit file comes back as uint8 [h,w]
+    instead, for `adh_u16_resize_bilinear` to promote on the device (the depth cache uploads one byte per pixel).  Any other
+    mode (RGB, palette, 32-bit, float) raises a ValueError that names the path: what the levels of such a file mean as depth
+    is not for this loader to guess."""
+    import numpy as np
+    with _pil().open(path) as im:
+        if im.mode != "L" and im.mode not in DEPTH_MODES_16:
+            raise ValueError(f"{path}: a depth map must be 8-bit or 16-bit grey, got Pillow mode {im.mode}")
+        a = np.array(im)
+    if a.dtype == np.uint8:
+        a = a if raw else a.astype(np.uint16) * np.uint16(257)
+    return torch.from_numpy(np.ascontiguousarray(a if a.dtype == np.uint8 else a.astype(np.uint16)))
+
+
 def save_image(path: str, u8: torch.Tensor) -> None:
     """uint8 [H,W,C] (C = 1, 3 or 4) to a file whose format the extension of `path` names"""
     if u8.dim() != 3 or u8.shape[2] not in (1, 3, 4) or u8.dtype != torch.uint8:

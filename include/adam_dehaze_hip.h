@@ -771,6 +771,39 @@ int adh_batch_from_u8(void* stream, const uint8_t* cache, int64_t image_pitch, i
 int adh_batch_window_from_u8(void* stream, const uint8_t* cache, int64_t cache_bytes, const int64_t* window, const float* params,
                              int N, int CH, int CW, double* partial, int nblk, float* out_nchw);
 
+/* ---- haze synthesis from clear images and depth maps (csrc/dataset.hip): the hazy role of a batch rendered from the clear cache.
+ *   adh_u16_resize_bilinear   one decoded depth file to one dense uint16 [OH, OW] slot of the depth cache.  The source is single
+ *       channel: level (y, x) is the byte (bytes_per_px == 1, promoted to v * 257 so that v / 255 == v * 257 / 65535) or the
+ *       native-endian uint16 (bytes_per_px == 2; src and src_pitch_bytes even) at src + y * src_pitch_bytes + x * bytes_per_px.
+ *       Source coordinates and fp32 interpolation are adh_u8_resize_bilinear's; the value is rounded half-even and clamped to
+ *       0..65535.  OH == h and OW == w is an exact copy (promotion).  ADH_E_ARG for a null pointer, a size < 1, bytes_per_px
+ *       outside {1, 2}, src_pitch_bytes < w * bytes_per_px, an odd dst, or an odd src / pitch with bytes_per_px == 2.
+ *   adh_batch_haze_from_u8   out[n] = augment(fog(window n)).  Window n is CH x CW: row y is the CW * 3 RGB bytes at
+ *       clear + geom[n][0] + y * geom[n][1] and, with a depth cache, the CW uint16 at (bytes) depth + geom[n][2] + y * geom[n][3]
+ *       (geom: device int64[N, 4], all in bytes; columns 2 and 3 are not read when depth == NULL).  fog: device float[N, 2] =
+ *       {beta, A}.  Per SOURCE pixel (y, x) of the window, in float64 with one exp shared by the channels (adh_apply_fog's
+ *       expressions): J = (float)v / 255.0f; d = depth_near + (depth_far - depth_near) * (u / 65535.0), or without a depth cache
+ *       d = 0.3 + 0.7 * sqrt((x / (CW - 1) - 0.5)^2 + (y / (CH - 1) - 0.2)^2) (a one-pixel axis has coordinate 0);
+ *       t = exp(-beta * d); h = min(max((float)(J * t + A * (1 - t)), 0), 1).  Then params (NULL or float[N, 5]), partial, nblk
+ *       and the launches exactly as adh_batch_window_from_u8: the flips move the hazed pixels, and the grey mean of the contrast
+ *       step is that of the hazed window (both launches evaluate the model).  beta == 0 gives the bits of
+ *       adh_batch_window_from_u8.  Bit-reproducible; a sample's planes depend neither on N nor on its place in the batch; dense
+ *       geometry {i * H * W * 3, W * 3, i * H * W * 2, W * 2} gives the bits of the same windows in a flat cache.
+ *       geom[n] is NOT validated on the device: the caller guarantees that every row of every window lies inside its cache and
+ *       that the depth offsets and pitches are even (data.batch_haze_from_windows checks it on the host).  No byte outside
+ *       [clear, clear + clear_bytes) or [depth, depth + depth_bytes) is read.  A lane's four pixels are read as aligned dwords
+ *       (12 clear bytes as in adh_batch_window_from_u8; 8 depth bytes as two dwords, or three and a funnel shift at an address
+ *       2 mod 4) where that cache's pointer and byte count are multiples of 4; byte by byte and level by level otherwise.
+ *       ADH_E_ARG (nothing is launched) for a null clear / geom / fog / out, params without partial, N outside [1, 65535], CH or
+ *       CW < 1, clear_bytes < CH * CW * 3, depth_bytes < CH * CW * 2 or an odd depth pointer (depth != NULL), or nblk other than
+ *       adh_batch_num_blocks(CH * CW).
+ *   dst_u16 and depth point to uint16 levels (void* here: every pointer type of this header is one the binding's table knows). */
+int adh_u16_resize_bilinear(void* stream, const uint8_t* src, int64_t src_pitch_bytes, int h, int w, int bytes_per_px,
+                            void* dst_u16, int OH, int OW);
+int adh_batch_haze_from_u8(void* stream, const uint8_t* clear, int64_t clear_bytes, const void* depth, int64_t depth_bytes,
+                           const int64_t* geom, const float* fog, double depth_near, double depth_far, const float* params, int N,
+                           int CH, int CW, double* partial, int nblk, float* out_nchw);
+
 /* ---- CIEDE2000 (csrc/ciede2000.hip): the per-pixel colour difference dE00 of Sharma, Wu and Dalal (2005), kL = kC = kH = 1,
  * between two dense fp32 [N,3,H,W] batches, and its mean per image.  lab_input == 0: the planes are sRGB in [0,1] (clamped as
  * adh_image_to_u8 clamps, NaN = 0) and go through skimage's rgb2lab constants (sRGB decoding, the 0.412453... matrix, the D65

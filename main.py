@@ -12,6 +12,7 @@ the hot path run on the HIP engine; dataset preprocessing is outside this build'
     python main.py --mode demo --input DIR --detect                # ... detect on hazy and dehazed, boxes drawn on the device
     python main.py --mode demo --input CLEAR --fit-niqe niqe.npz   # fit a NIQE model from clean files
     python main.py --mode demo --input DIR --niqe niqe.npz         # ... and score without ground truth: NIQE per file
+    python main.py --mode synthesize --input CLEAR --depth DEPTH --output OUT   # render {low,medium,high}/{hazy,clear} pairs
 
 `--resume` is the reference's flag (main.py:50-51 parses it and never reads it); here it restores model, optimiser,
 scheduler, epoch and best-PSNR from the latest checkpoint of the mode's checkpoint directory (or from the file given
@@ -32,7 +33,8 @@ def parse_args():
     p = argparse.ArgumentParser(description="Adaptive fog intensity dehazing framework (MI355X build)")
     p.add_argument("--config", type=str, default="config/config.yaml")
     p.add_argument("--mode", type=str, default="train_all",
-                   choices=["preprocess", "train_classifier", "train_dehazing", "train_joint", "train_all", "evaluate", "demo"])
+                   choices=["preprocess", "train_classifier", "train_dehazing", "train_joint", "train_all", "evaluate", "demo",
+                            "synthesize"])
     p.add_argument("--exp_name", type=str, default=None)
     p.add_argument("--data_dir", type=str, default=None)
     p.add_argument("--device", type=str, default=None)
@@ -72,6 +74,9 @@ def parse_args():
                    help="--brisque-model: the svm-scale range file of its features (demo.brisque_range)")
     p.add_argument("--fit-niqe", dest="fit_niqe", type=str, default=None, metavar="OUT.npz",
                    help="--mode demo --input CLEAR_DIR: fit the NIQE model from these clean image files, write it and exit")
+    p.add_argument("--depth", type=str, default=None, metavar="DEPTH_DIR",
+                   help="--mode synthesize --input CLEAR_DIR: the directory of depth maps, <stem>.png (8-bit or 16-bit grey) per "
+                        "clear file; without it the reference's radial depth map is used")
     return p.parse_args()
 
 
@@ -104,6 +109,10 @@ def main():
                          "image files given with --input.")
     if args.brisque_range and not args.brisque_model:
         raise SystemExit("--brisque-range needs --brisque-model: it is the range file of that model's features.")
+    if args.depth and args.mode != "synthesize":
+        raise SystemExit("--depth needs --mode synthesize --input CLEAR_DIR: it names the depth maps of the clear files.")
+    if args.mode == "synthesize" and not args.input:
+        raise SystemExit("--mode synthesize needs --input CLEAR_DIR (and takes --depth DEPTH_DIR, --output OUT, --seed S).")
     if args.fit_niqe:
         if not (args.mode == "demo" and args.input):
             raise SystemExit("--fit-niqe needs --mode demo --input CLEAR_DIR: the clean image files the model is fitted from.")
@@ -134,8 +143,8 @@ def main():
         if args.resume is not None:
             raise SystemExit("--resume is not supported for --mode train_classifier: the classifier stage always trains from "
                              "scratch (drop --resume).")
-    if args.mode == "demo" and args.input and world > 1:
-        raise SystemExit("--mode demo runs in a single process.  Run it without torchrun (WORLD_SIZE=1).")
+    if args.mode in ("demo", "synthesize") and args.input and world > 1:
+        raise SystemExit(f"--mode {args.mode} runs in a single process.  Run it without torchrun (WORLD_SIZE=1).")
     if world > 1:
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -199,6 +208,9 @@ def main():
         # evaluate.py:464-540 (the reference first rewrites the checkpoint paths to a hard-coded experiment directory, main.py:143-145:
         # here the paths of the config are used as they are)
         T.run_comprehensive_evaluation(config)   # baseline branches, routed system, detector on hazy vs dehazed frames
+    elif args.mode == "synthesize":
+        from adam_dehaze_amd.data import synthesize_tree
+        synthesize_tree(args.input, args.output, depth_dir=args.depth, seed=config["seed"], device=config.get("device", "cuda"))
     elif args.mode == "demo" and args.input and args.fit_niqe:
         T.fit_niqe_model(config, args.input, args.fit_niqe)
     elif args.mode == "demo" and args.input:
