@@ -255,6 +255,7 @@ _SIGNATURES = {
     "adh_batch_window_from_u8": [vp, vp, i64, vp, vp, i32, i32, i32, vp, i32, vp],
     "adh_u16_resize_bilinear": [vp, vp, i64, i32, i32, i32, vp, i32, i32],
     "adh_batch_haze_from_u8": [vp, vp, i64, vp, i64, vp, vp, f64, f64, vp, i32, i32, i32, vp, i32, vp],
+    "adh_batch_nhhaze_from_u8": [vp, vp, i64, vp, i64, vp, vp, vp, f64, f64, vp, i32, i32, i32, vp, i32, vp],
     "adh_nss_halve": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "adh_nss_moments": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp],
 }

@@ -693,3 +693,362 @@ extern "C" int adh_batch_haze_from_u8(void* stream, const uint8_t* clear, int64_
 #undef HZ_LAUNCH
     return adh_check_launch();
 }
+
+// ------------------------------------------------------------------------------------------------ patchy, chromatic haze
+//   adh_batch_nhhaze_from_u8  adh_batch_haze_from_u8 with beta_c and A_c per channel and the optical depth scaled per source
+//                           pixel by m = 1 + s (2 f - 1), f in [0, 1] a density field anchored to the IMAGE: K octaves of value
+//                           noise on an integer-hashed lattice at image coordinates (y + oy, x + ox), evaluated in the lane's
+//                           registers (no LDS, no workspace, no launch of its own).
+// Octave k: p = (double)coordinate * (f0 2^k) is ONE multiplication and floor(p) the lattice cell, so a host restatement lands in
+// the same cells; the corner values are 32-bit hashes / 2^32 (exact), blended by the fade u u (3 - 2 u).  The field's arithmetic
+// is compiled with contraction off: every operation is the IEEE one a host restatement performs (a fused p - floor(p) would
+// differ from it by the rounding of p, which at coordinates near 2^31 is no small number), and a pixel's value does not depend
+// on which path (quad or single) computed it.  The host checks f0 2^(K-1) <= 0.5 and coordinate * f below 2^31.
+// The kernels are siblings of haze_gray_partial_kernel / haze_gather_kernel, statement for statement, with nh_quad / nh_one in
+// the place of hz_quad / hz_one: the same grid, flags, access paths and deal of pixels.  They are not one template with those,
+// because wrapping the old kernels' bodies changed the code the compiler makes for them.
+#ifndef NH_SHARE_CORNERS
+#define NH_SHARE_CORNERS 1   // 0: every pixel of a quad hashes its own four corners (A/B measurements only)
+#endif
+
+struct nh_ctx {
+    double b[3], A[3], s, f0;
+    int64_t oy, ox;
+    uint32_t seed;
+    int K;
+    bool grey;               // beta_r == beta_g == beta_b: one exp serves the three channels
+};
+
+__device__ __forceinline__ nh_ctx nh_make(const float* __restrict__ fog, const double* __restrict__ field, int n) {
+    nh_ctx q;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) q.b[c] = (double)fog[6 * n + c], q.A[c] = (double)fog[6 * n + 3 + c];
+    const double* f = field + 6 * n;
+    q.seed = (uint32_t)f[0], q.oy = (int64_t)f[1], q.ox = (int64_t)f[2], q.K = (int)f[3];
+    q.s = f[4], q.f0 = f[5];
+    q.grey = q.b[0] == q.b[1] && q.b[1] == q.b[2];
+    return q;
+}
+
+// hz_make without beta and A
+__device__ __forceinline__ hz_ctx nh_geom(double dnear, double dfar, int CH, int CW) {
+    hz_ctx k;
+    k.b = 0.0, k.A = 0.0;
+    k.dnear = dnear, k.span = dfar - dnear;
+    k.sx = CW > 1 ? 1.0 / (double)(CW - 1) : 0.0, k.sy = CH > 1 ? 1.0 / (double)(CH - 1) : 0.0;
+    return k;
+}
+
+__device__ __forceinline__ uint32_t nh_mix(uint32_t h) {
+    h ^= h >> 16, h *= 0x7FEB352Du;
+    h ^= h >> 15, h *= 0x846CA68Bu;
+    return h ^ (h >> 16);
+}
+
+// the hash's share of lattice row iy of octave o, and the lattice value at column ix of that row, in [0, 1)
+__device__ __forceinline__ uint32_t nh_row(uint32_t iy, int o, uint32_t seed) {
+    return (iy * 0x85EBCA77u) ^ ((uint32_t)o * 0xC2B2AE3Du) ^ seed;
+}
+__device__ __forceinline__ double nh_value(uint32_t ix, uint32_t row) {
+    return (double)nh_mix((ix * 0x9E3779B1u) ^ row) * (1.0 / 4294967296.0);
+}
+
+// the field at window pixels (y, x .. x + NPX - 1), NPX = 1 or DS_QUAD.  The pixels share the row and, with the finest cell at
+// least 2 pixels wide, start in at most three neighbouring lattice columns: four columns x two rows are hashed once per octave.
+template <int NPX>
+__device__ __forceinline__ void nh_field(const nh_ctx& q, int64_t y, int64_t x, double (&f)[NPX]) {
+#pragma clang fp contract(off)
+    constexpr int NCOL = NPX == 1 ? 2 : 4;
+    const double Y = (double)(y + q.oy);
+    double acc[NPX], norm = 0.0;
+#pragma unroll
+    for (int j = 0; j < NPX; ++j) acc[j] = 0.0;
+    for (int o = 0; o < q.K; ++o) {
+        const double fk = q.f0 * (double)(1 << o), wk = 1.0 / (double)(1 << o);
+        const double py = Y * fk, fy = floor(py), uy = py - fy;
+        const double wy = uy * uy * (3.0 - 2.0 * uy);
+        const uint32_t iy = (uint32_t)(int64_t)fy;
+        const uint32_t r0 = nh_row(iy, o, q.seed), r1 = nh_row(iy + 1u, o, q.seed);
+        const double fx0 = floor((double)(x + q.ox) * fk);
+        const uint32_t ix0 = (uint32_t)(int64_t)fx0;
+        double top[NCOL], bot[NCOL];
+#pragma unroll
+        for (int c = 0; c < NCOL; ++c) top[c] = bot[c] = 0.0;
+        if (NPX == 1 || NH_SHARE_CORNERS) {
+#pragma unroll
+            for (int c = 0; c < NCOL; ++c) top[c] = nh_value(ix0 + (uint32_t)c, r0), bot[c] = nh_value(ix0 + (uint32_t)c, r1);
+        }
+#pragma unroll
+        for (int j = 0; j < NPX; ++j) {
+            const double px = (double)(x + q.ox + j) * fk, fx = floor(px), ux = px - fx;
+            const double wx = ux * ux * (3.0 - 2.0 * ux);
+            double v00, v01, v10, v11;
+            if (NPX == 1) {
+                v00 = top[0], v01 = top[1], v10 = bot[0], v11 = bot[1];
+            } else if (NH_SHARE_CORNERS) {
+                const int c = (int)(fx - fx0);                 // 0, 1 or 2; selects: a runtime index would put the arrays in scratch
+                v00 = c == 0 ? top[0] : c == 1 ? top[1] : top[NCOL - 2];
+                v01 = c == 0 ? top[1] : c == 1 ? top[NCOL - 2] : top[NCOL - 1];
+                v10 = c == 0 ? bot[0] : c == 1 ? bot[1] : bot[NCOL - 2];
+                v11 = c == 0 ? bot[1] : c == 1 ? bot[NCOL - 2] : bot[NCOL - 1];
+            } else {
+                const uint32_t ix = (uint32_t)(int64_t)fx;
+                v00 = nh_value(ix, r0), v01 = nh_value(ix + 1u, r0), v10 = nh_value(ix, r1), v11 = nh_value(ix + 1u, r1);
+            }
+            const double t = v00 + wx * (v01 - v00), b = v10 + wx * (v11 - v10);
+            acc[j] = acc[j] + wk * (t + wy * (b - t));
+        }
+        norm = norm + wk;
+    }
+#pragma unroll
+    for (int j = 0; j < NPX; ++j) f[j] = acc[j] / norm;
+}
+
+// hz_pixel under the non-uniform model: field value f, beta and A per channel, the same expressions otherwise
+template <bool DEPTH>
+__device__ __forceinline__ void nh_pixel(const hz_ctx& k, const nh_ctx& q, double f, uint32_t r, uint32_t g, uint32_t bl, uint32_t u,
+                                         int64_t y, int64_t x, float& hr, float& hg, float& hb) {
+    double d;
+    if (DEPTH) {
+        d = k.dnear + k.span * ((double)u / 65535.0);
+    } else {
+        const double dx = (double)x * k.sx - 0.5, dy = (double)y * k.sy - 0.2;
+        d = 0.3 + 0.7 * sqrt(dx * dx + dy * dy);
+    }
+    double bm[3];
+    {
+#pragma clang fp contract(off)
+        const double m = 1.0 + q.s * (2.0 * f - 1.0);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) bm[c] = q.b[c] * m;
+    }
+    double t[3];
+    t[0] = exp(-bm[0] * d);
+    if (q.grey) {
+        t[1] = t[2] = t[0];
+    } else {
+        t[1] = exp(-bm[1] * d);
+        t[2] = exp(-bm[2] * d);
+    }
+    const double a0 = q.A[0] * (1.0 - t[0]), a1 = q.A[1] * (1.0 - t[1]), a2 = q.A[2] * (1.0 - t[2]);
+    hr = fminf(fmaxf((float)((double)ds_unit(r) * t[0] + a0), 0.f), 1.f);
+    hg = fminf(fmaxf((float)((double)ds_unit(g) * t[1] + a1), 0.f), 1.f);
+    hb = fminf(fmaxf((float)((double)ds_unit(bl) * t[2] + a2), 0.f), 1.f);
+}
+
+// hz_one
+template <bool DEPTH>
+__device__ __forceinline__ void nh_one(const hz_ctx& k, const nh_ctx& q, const uint8_t* __restrict__ cp,
+                                       const uint8_t* __restrict__ dp, int64_t y, int64_t x, float& hr, float& hg, float& hb) {
+    const uint32_t u = DEPTH ? (uint32_t)*reinterpret_cast<const uint16_t*>(dp) : 0u;
+    double f[1];
+    nh_field<1>(q, y, x, f);
+    nh_pixel<DEPTH>(k, q, f[0], cp[0], cp[1], cp[2], u, y, x, hr, hg, hb);
+}
+
+// hz_quad: its access paths, then the field of the four pixels at once
+template <bool DEPTH>
+__device__ __forceinline__ void nh_quad(const hz_ctx& k, const nh_ctx& q, const uint8_t* __restrict__ cp,
+                                        const uint8_t* __restrict__ dp, int flags, int64_t y, int64_t x, float (&s)[3][DS_QUAD]) {
+    uint32_t px[DS_QUAD * 3], u[DS_QUAD] = {0u, 0u, 0u, 0u};
+    if (flags & DS_WIDE_U8) {
+        uint32_t w[3];
+        ds_load12(cp, w);
+#pragma unroll
+        for (int i = 0; i < DS_QUAD * 3; ++i) px[i] = (w[i >> 2] >> ((i & 3) * 8)) & 255u;
+    } else {
+#pragma unroll
+        for (int i = 0; i < DS_QUAD * 3; ++i) px[i] = cp[i];
+    }
+    if (DEPTH) {
+        if (flags & DS_WIDE_U16) {
+            hz_load8(dp, u);
+        } else {
+#pragma unroll
+            for (int j = 0; j < DS_QUAD; ++j) u[j] = reinterpret_cast<const uint16_t*>(dp)[j];
+        }
+    }
+    double f[DS_QUAD];
+    nh_field<DS_QUAD>(q, y, x, f);
+#pragma unroll
+    for (int j = 0; j < DS_QUAD; ++j)
+        nh_pixel<DEPTH>(k, q, f[j], px[j * 3], px[j * 3 + 1], px[j * 3 + 2], u[j], y, x + j, s[0][j], s[1][j], s[2][j]);
+}
+
+// haze_gray_partial_kernel
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void nhhaze_gray_partial_kernel(const uint8_t* __restrict__ clear, const uint8_t* __restrict__ depth,
+                                                                  const int64_t* __restrict__ geom, const float* __restrict__ fog,
+                                                                  const double* __restrict__ field, double dnear, double dfar,
+                                                                  const float* __restrict__ params, int CH, int CW, int64_t HW,
+                                                                  int flags, double* __restrict__ partial) {
+    const int n = blockIdx.y;
+    const float* p = params + n * 5;
+    const bool bfirst = p[2] != 0.f;
+    const float b = p[3];
+    const hz_ctx k = nh_geom(dnear, dfar, CH, CW);
+    const nh_ctx q = nh_make(fog, field, n);
+    const uint8_t* __restrict__ win = clear + geom[4 * n];
+    const int64_t pitch = geom[4 * n + 1];
+    const uint8_t* __restrict__ dwin = DEPTH ? depth + geom[4 * n + 2] : nullptr;
+    const int64_t dpitch = DEPTH ? geom[4 * n + 3] : 0;
+    const int64_t step = (int64_t)gridDim.x * 256 * DS_QUAD;
+    const int64_t dy = step / CW;
+    const int64_t dx = step - dy * CW;
+    int64_t i = (blockIdx.x * (int64_t)256 + threadIdx.x) * DS_QUAD;
+    int64_t y = i / CW;
+    int64_t x = i - y * CW;
+    double acc = 0.0;
+    for (; i < HW; i += step) {
+        const int npx = (HW - i) < DS_QUAD ? (int)(HW - i) : DS_QUAD;
+        if (npx == DS_QUAD && x + DS_QUAD <= CW) {
+            float s[3][DS_QUAD];
+            nh_quad<DEPTH>(k, q, win + y * pitch + x * 3, DEPTH ? dwin + y * dpitch + x * 2 : nullptr, flags, y, x, s);
+#pragma unroll
+            for (int j = 0; j < DS_QUAD; ++j) acc += (double)ds_gray(s[0][j], s[1][j], s[2][j], bfirst, b);
+        } else {
+            int64_t yy = y, xx = x;
+            for (int j = 0; j < npx; ++j, ++xx) {
+                while (xx >= CW) xx -= CW, ++yy;
+                float hr, hg, hb;
+                nh_one<DEPTH>(k, q, win + yy * pitch + xx * 3, DEPTH ? dwin + yy * dpitch + xx * 2 : nullptr, yy, xx, hr, hg, hb);
+                acc += (double)ds_gray(hr, hg, hb, bfirst, b);
+            }
+        }
+        y += dy, x += dx;
+        if (x >= CW) x -= CW, ++y;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    __shared__ double s4[4];
+    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[(int64_t)n * gridDim.x + blockIdx.x] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+}
+
+// haze_gather_kernel
+template <bool AUG, bool DEPTH>
+__global__ __launch_bounds__(256) void nhhaze_gather_kernel(const uint8_t* __restrict__ clear, const uint8_t* __restrict__ depth,
+                                                            const int64_t* __restrict__ geom, const float* __restrict__ fog,
+                                                            const double* __restrict__ field, double dnear, double dfar,
+                                                            const float* __restrict__ params, const double* __restrict__ partial,
+                                                            int nblk, int H, int W, float* __restrict__ out, int flags) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.z;
+    const int64_t plane = (int64_t)H * W;
+    bool fh = false, fv = false, bfirst = false;
+    float b = 1.f, c = 1.f, mean = 0.f;
+    if (AUG) {
+        const float* p = params + n * 5;
+        fh = p[0] != 0.f, fv = p[1] != 0.f, bfirst = p[2] != 0.f;
+        b = p[3], c = p[4];
+        double m = 0.0;                     // batch_gather_kernel's sum of the partials: one order in every lane of every wave
+        for (int i = lane; i < nblk; i += 64) m += partial[(int64_t)n * nblk + i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m += __shfl_xor(m, o, 64);
+        mean = (float)(m / (double)plane);
+    }
+    const int64_t x = ((int64_t)blockIdx.x * 64 + lane) * DS_QUAD;
+    if (x >= W) return;
+    const int npx = (W - x) < DS_QUAD ? (int)(W - x) : DS_QUAD;
+    const hz_ctx k = nh_geom(dnear, dfar, H, W);
+    const nh_ctx q = nh_make(fog, field, n);
+    const uint8_t* __restrict__ img = clear + geom[4 * n];
+    const int64_t row_pitch = geom[4 * n + 1];
+    const uint8_t* __restrict__ dimg = DEPTH ? depth + geom[4 * n + 2] : nullptr;
+    const int64_t dpitch = DEPTH ? geom[4 * n + 3] : 0;
+    float* __restrict__ dst = out + (int64_t)n * 3 * plane;
+    for (int64_t y = (int64_t)blockIdx.y * DS_ROWS + (threadIdx.x >> 6); y < H; y += (int64_t)gridDim.y * DS_ROWS) {
+        const int64_t sy = fv ? H - 1 - y : y;
+        const uint8_t* __restrict__ row = img + sy * row_pitch;
+        const uint8_t* __restrict__ drow = DEPTH ? dimg + sy * dpitch : nullptr;
+        float v[3][DS_QUAD];
+        if (npx == DS_QUAD) {
+            const int64_t sx = fh ? W - DS_QUAD - x : x;
+            float s[3][DS_QUAD];
+            nh_quad<DEPTH>(k, q, row + sx * 3, DEPTH ? drow + sx * 2 : nullptr, flags, sy, sx, s);
+#pragma unroll
+            for (int j = 0; j < DS_QUAD; ++j)
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) v[ch][j] = fh ? s[ch][DS_QUAD - 1 - j] : s[ch][j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < DS_QUAD; ++j) {
+                v[0][j] = v[1][j] = v[2][j] = 0.0f;
+                if (j < npx) {
+                    const int64_t sx = fh ? W - 1 - (x + j) : x + j;
+                    nh_one<DEPTH>(k, q, row + sx * 3, DEPTH ? drow + sx * 2 : nullptr, sy, sx, v[0][j], v[1][j], v[2][j]);
+                }
+            }
+        }
+        if (AUG) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+                for (int j = 0; j < DS_QUAD; ++j) {
+                    float t = v[ch][j];         // aug_apply_kernel's expressions
+                    if (bfirst) {
+                        t = fminf(fmaxf(b * t, 0.f), 1.f);
+                        t = fminf(fmaxf(c * t + (1.f - c) * mean, 0.f), 1.f);
+                    } else {
+                        t = fminf(fmaxf(c * t + (1.f - c) * mean, 0.f), 1.f);
+                        t = fminf(fmaxf(b * t, 0.f), 1.f);
+                    }
+                    v[ch][j] = t;
+                }
+        }
+        float* __restrict__ o = dst + y * W + x;
+        if (npx == DS_QUAD && (flags & DS_WIDE_F32)) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                f32x4 q4;
+#pragma unroll
+                for (int j = 0; j < DS_QUAD; ++j) q4[j] = v[ch][j];
+                *reinterpret_cast<f32x4*>(o + ch * plane) = q4;
+            }
+        } else {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+                for (int j = 0; j < DS_QUAD; ++j)
+                    if (j < npx) o[ch * plane + j] = v[ch][j];
+        }
+    }
+}
+
+// fog [N,6] = {beta_r beta_g beta_b A_r A_g A_b}, field [N,6] (doubles) = {seed, oy, ox, K, s, f0}: adh_batch_haze_from_u8's
+// checks, flags, grid and launches.  Neither geom nor field is validated on the device.
+extern "C" int adh_batch_nhhaze_from_u8(void* stream, const uint8_t* clear, int64_t clear_bytes, const void* depth,
+                                        int64_t depth_bytes, const int64_t* geom, const float* fog, const double* field,
+                                        double depth_near, double depth_far, const float* params, int N, int CH, int CW,
+                                        double* partial, int nblk, float* out_nchw) {
+    if (!clear || !geom || !fog || !field || !out_nchw || (params && !partial)) return ADH_E_ARG;
+    if (N < 1 || N > 65535 || CH < 1 || CW < 1) return ADH_E_ARG;
+    const int64_t HW = (int64_t)CH * CW;
+    if (HW > INT64_MAX / 3 || clear_bytes < HW * 3) return ADH_E_ARG;
+    if (depth && ((((uintptr_t)depth) & 1) || depth_bytes < HW * 2)) return ADH_E_ARG;
+    if (nblk != adh_batch_num_blocks(HW)) return ADH_E_ARG;
+    const bool al4 = ((((uintptr_t)clear) | (uintptr_t)clear_bytes) & 3) == 0;
+    const bool dal4 = depth && ((((uintptr_t)depth) | (uintptr_t)depth_bytes) & 3) == 0;
+    const int flags = (al4 ? DS_WIDE_U8 : 0) | (dal4 ? DS_WIDE_U16 : 0) |
+                      (((((uintptr_t)out_nchw) & 15) == 0 && (CW & 3) == 0) ? DS_WIDE_F32 : 0);
+    const uint8_t* dbytes = reinterpret_cast<const uint8_t*>(depth);
+    const dim3 grid((unsigned)adh_ceil_div(CW, 64 * DS_QUAD), (unsigned)adh_min_i(adh_ceil_div(CH, DS_ROWS), 65535), (unsigned)N);
+#define NH_LAUNCH(D)                                                                                                              \
+    if (params) {                                                                                                                 \
+        hipLaunchKernelGGL((nhhaze_gray_partial_kernel<D>), dim3(nblk, N), dim3(256), 0, (hipStream_t)stream, clear, dbytes,      \
+                           geom, fog, field, depth_near, depth_far, params, CH, CW, HW, flags, partial);                          \
+        hipLaunchKernelGGL((nhhaze_gather_kernel<true, D>), grid, dim3(256), 0, (hipStream_t)stream, clear, dbytes, geom, fog,    \
+                           field, depth_near, depth_far, params, partial, nblk, CH, CW, out_nchw, flags);                         \
+    } else {                                                                                                                      \
+        hipLaunchKernelGGL((nhhaze_gather_kernel<false, D>), grid, dim3(256), 0, (hipStream_t)stream, clear, dbytes, geom, fog,   \
+                           field, depth_near, depth_far, params, partial, nblk, CH, CW, out_nchw, flags);                         \
+    }
+    if (depth) {
+        NH_LAUNCH(true)
+    } else {
+        NH_LAUNCH(false)
+    }
+#undef NH_LAUNCH
+    return adh_check_launch();
+}

@@ -20,10 +20,13 @@ in half of the free device memory is refused.
 Clear images plus depth maps (`dataset.synthetic_haze`, the RESIDE recipe): `haze_index` lists `<split>/clear/<name>` with
 `depth/<stem>.png`, `HazeSynthDataset` keeps the clear bytes and a uint16 depth cache on the device, and `batch_haze_from_windows`
 renders the hazy role of every batch from them (`adh_batch_haze_from_u8`: the scattering model at source pixels, then the paired
-transform), under a fresh (label, beta, A) per sample and epoch from `draw_haze_params`.
+transform), under a fresh (label, beta, A) per sample and epoch from `draw_haze_params`.  With `nonuniform` / `chromatic` in that
+section the renderer is `batch_nhhaze_from_windows` (`adh_batch_nhhaze_from_u8`): patchy haze from a noise field anchored to the
+image and beta, A per channel, drawn by `draw_nh_params` after the former.
 """
 from __future__ import annotations
 
+import copy
 import os
 from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Dict, Iterator, List, Mapping, Optional, Sequence, Union
@@ -492,6 +495,20 @@ def fixed_haze_params(seed: int, samples):
     return torch.cat([d[0] for d in drawn]), torch.cat([d[1] for d in drawn])
 
 
+def fixed_nh_params(seed: int, samples, nonuniform, chromatic, sizes, origins):
+    """`fixed_haze_params` plus the extras of `draw_nh_params`, drawn from the same RandomState((seed, g)) after the sample's
+    (label, beta, A): -> (labels, fog [n,2], fog6 [n,6], field [n,6]), the same in every epoch, on every rank, for every world"""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    origins = np.zeros_like(sizes) if origins is None else np.asarray(origins, dtype=np.int64).reshape(-1, 2)
+    labels, fog, fog6, field = [], [], [], []
+    for i, g in enumerate(samples):
+        rng = np.random.RandomState((int(seed) % 2 ** 32, int(g)))
+        lab, f2 = draw_haze_params(1, rng)
+        f6, fld = draw_nh_params(1, rng, nonuniform, chromatic, sizes[i:i + 1], origins[i:i + 1], f2)
+        labels.append(lab), fog.append(f2), fog6.append(f6), field.append(fld)
+    return torch.cat(labels), torch.cat(fog), torch.cat(fog6), torch.cat(field)
+
+
 def batch_haze_from_windows(clear: torch.Tensor, depth: Optional[torch.Tensor], geom: torch.Tensor, fog: torch.Tensor, crop,
                             params: Optional[torch.Tensor] = None, depth_range=DEFAULT_DEPTH_RANGE) -> torch.Tensor:
     """The hazy role of a batch rendered from clear pixels: float32 [N,3,CH,CW] = augment(fog(window)) by `adh_batch_haze_from_u8`.
@@ -547,6 +564,181 @@ def batch_haze_from_windows(clear: torch.Tensor, depth: Optional[torch.Tensor], 
     return out
 
 
+# patchy, wavelength-dependent haze: `nonuniform` / `chromatic` of dataset.synthetic_haze
+NH_DEFAULTS = {"nonuniform": {"amplitude": (0.2, 0.8), "cell": (0.15, 0.5), "octaves": 3},
+               "chromatic": {"angstrom": (0.0, 1.3), "tint": 0.05}}
+NH_MAX_OCTAVES = 4
+NH_WAVELENGTHS_NM = (610.0, 550.0, 465.0)      # r, g, b; green keeps the drawn beta
+
+
+def _nh_settings(which: str, value, where: str = "dataset.synthetic_haze") -> Optional[Dict]:
+    """`nonuniform` / `chromatic` as given (None: off; True or {}: the defaults; a mapping: defaults overridden) -> a checked dict
+    of plain floats / ints, or None.  ValueError names the key."""
+    if value is None or value is False:
+        return None
+    defaults = NH_DEFAULTS[which]
+    if value is True:
+        value = {}
+    if not isinstance(value, Mapping):
+        raise ValueError(f"{where}.{which} must be a mapping with keys {sorted(defaults)}, got {value!r}")
+    unknown = sorted(set(value) - set(defaults))
+    if unknown:
+        raise ValueError(f"{where}.{which}: unknown keys {unknown} (known: {', '.join(sorted(defaults))})")
+
+    def pair(key, lo_min, hi_max, hi_open=False):
+        v = value.get(key, defaults[key])
+        ok = isinstance(v, (list, tuple)) and len(v) == 2 and all(isinstance(t, (int, float)) and not isinstance(t, bool) for t in v)
+        if ok:
+            lo, hi = float(v[0]), float(v[1])
+            ok = np.isfinite(lo) and np.isfinite(hi) and lo_min <= lo <= hi and (hi < hi_max if hi_open else hi <= hi_max)
+        if not ok:
+            raise ValueError(f"{where}.{which}.{key} must be [lo, hi] with {lo_min} <= lo <= hi {'<' if hi_open else '<='} "
+                             f"{hi_max}, got {v!r}")
+        return (lo, hi)
+    if which == "nonuniform":
+        amplitude = pair("amplitude", 0.0, 1.0, hi_open=True)
+        cell = pair("cell", 2.0 ** -20, 2.0 ** 20)
+        if cell[0] <= 0:
+            raise ValueError(f"{where}.{which}.cell must be [lo, hi] with 0 < lo <= hi, got {value.get('cell')!r}")
+        K = value.get("octaves", defaults["octaves"])
+        if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= NH_MAX_OCTAVES:
+            raise ValueError(f"{where}.{which}.octaves must be an integer in 1..{NH_MAX_OCTAVES}, got {K!r}")
+        return {"amplitude": amplitude, "cell": cell, "octaves": int(K)}
+    angstrom = pair("angstrom", -4.0, 4.0)
+    tint = value.get("tint", defaults["tint"])
+    if isinstance(tint, bool) or not isinstance(tint, (int, float)) or not (np.isfinite(tint) and 0.0 <= tint <= 1.0):
+        raise ValueError(f"{where}.{which}.tint must be a number in [0, 1], got {tint!r}")
+    return {"angstrom": angstrom, "tint": float(tint)}
+
+
+def check_haze_field(field: torch.Tensor, N: int, crop, who: str = "batch_nhhaze_from_windows") -> None:
+    """the rows {seed, oy, ox, K, s, f0} of a CPU float64 [N,6] tensor against what the kernel takes for granted; ValueError names
+    the row"""
+    if not isinstance(field, torch.Tensor) or field.is_cuda or field.dtype != torch.float64 or tuple(field.shape) != (N, 6):
+        raise TypeError(f"{who}: field must be a float64 [{N},6] tensor on the CPU")
+    CH, CW = crop
+    a = field.numpy()
+    with np.errstate(all="ignore"):                 # every step calls this: all rows at once, the loop below only names a bad one
+        seed, oy, ox, K, s, f0 = a.T
+        fine = f0 * 2.0 ** (K - 1)
+        whole = a[:, :4] == np.floor(a[:, :4])
+        ok = (np.isfinite(a).all() and whole.all() and (seed >= 0).all() and (seed < 2 ** 32).all() and (oy >= 0).all()
+              and (ox >= 0).all() and (K >= 1).all() and (K <= NH_MAX_OCTAVES).all() and (s >= 0).all() and (s < 1).all()
+              and (f0 > 0).all() and (fine <= 0.5).all() and ((oy + CH) * fine < 2.0 ** 31).all()
+              and ((ox + CW) * fine < 2.0 ** 31).all())
+    if ok:
+        return
+    for n, (seed, oy, ox, K, s, f0) in enumerate(field.tolist()):
+        def bad(what):
+            return ValueError(f"{who}: field row {n}: {what}: {[seed, oy, ox, K, s, f0]}")
+        if not (np.isfinite(seed) and seed == int(seed) and 0 <= seed < 2 ** 32):
+            raise bad("seed must be an integer in [0, 2^32)")
+        for name, o in (("oy", oy), ("ox", ox)):
+            if not (np.isfinite(o) and o == int(o) and o >= 0):
+                raise bad(f"{name} must be an integer >= 0")
+        if not (np.isfinite(K) and K == int(K) and 1 <= K <= NH_MAX_OCTAVES):
+            raise bad(f"K must be an integer in 1..{NH_MAX_OCTAVES}")
+        if not 0.0 <= s < 1.0:
+            raise bad("s must satisfy 0 <= s < 1")
+        if not (np.isfinite(f0) and f0 > 0.0):
+            raise bad("f0 must be finite and positive")
+        fine = f0 * 2.0 ** (int(K) - 1)
+        if fine > 0.5:
+            raise bad(f"f0 * 2^(K-1) = {fine} > 0.5 (the finest cell is under 2 pixels)")
+        if (oy + CH) * fine >= 2.0 ** 31 or (ox + CW) * fine >= 2.0 ** 31:
+            raise bad("(origin + crop) * f0 * 2^(K-1) must stay below 2^31")
+
+
+def batch_nhhaze_from_windows(clear: torch.Tensor, depth: Optional[torch.Tensor], geom: torch.Tensor, fog6: torch.Tensor,
+                              field: torch.Tensor, crop, params: Optional[torch.Tensor] = None,
+                              depth_range=DEFAULT_DEPTH_RANGE) -> torch.Tensor:
+    """`batch_haze_from_windows` under patchy, wavelength-dependent haze (`adh_batch_nhhaze_from_u8`): `fog6` float32 [N,6] =
+    {beta_r, beta_g, beta_b, A_r, A_g, A_b} and `field` (CPU float64 [N,6]) = {seed, oy, ox, K, s, f0}, both from `draw_nh_params`.
+    Per source pixel the optical depth is scaled by m = 1 + s (2 f - 1), f in [0, 1] a K-octave value-noise field of coarsest
+    frequency f0 (cells per pixel) anchored to the image: (oy, ox) is the window's origin in its image, so two crops of one image
+    see the same cloud, and the field flips with the pixels.  t_c = exp(-beta_c m d), hazy_c = clamp(J_c t_c + A_c (1 - t_c)).
+    The checks are `batch_haze_from_windows`' plus, before anything touches the device, `check_haze_field` (ValueError, naming
+    the row): seed an integer in [0, 2^32), oy / ox integers >= 0, K an integer in 1..4, 0 <= s < 1, f0 finite and positive,
+    f0 2^(K-1) <= 0.5, (origin + crop) f0 2^(K-1) < 2^31."""
+    who = "batch_nhhaze_from_windows"
+    if not isinstance(geom, torch.Tensor) or geom.is_cuda or geom.dtype != torch.int64 or geom.dim() != 2 or geom.shape[1] != 4:
+        raise TypeError(f"{who}: geom must be an int64 [N,4] tensor on the CPU")
+    if not isinstance(clear, torch.Tensor) or (depth is not None and not isinstance(depth, torch.Tensor)):
+        raise TypeError(f"{who}: the caches must be tensors")
+    CH, CW = _size2(crop)
+    if CH < 1 or CW < 1:
+        raise ValueError(f"{who}: crop must be at least 1 x 1, got {(CH, CW)}")
+    N = geom.shape[0]
+    if N < 1:
+        raise ValueError(f"{who}: no windows")
+    if not isinstance(fog6, torch.Tensor) or tuple(fog6.shape) != (N, 6):
+        raise ValueError(f"{who}: fog6 must be a [{N},6] tensor of (beta_r, beta_g, beta_b, A_r, A_g, A_b)")
+    check_haze_field(field, N, (CH, CW), who)
+    if params is not None and tuple(params.shape) != (N, 5):
+        raise ValueError(f"{who}: params must be [{N},5], got {tuple(params.shape)}")
+    near, far = (float(v) for v in depth_range)
+    if not (np.isfinite(near) and np.isfinite(far)):
+        raise ValueError(f"{who}: depth_range must be finite, got {depth_range}")
+    rows = geom.tolist()                                                                                    # Python ints: no wrap
+    if depth is not None and any(do % 2 or dp % 2 or dp < CW * 2 for _, _, do, dp in rows):
+        raise ValueError(f"{who}: depth offsets and pitches must be even and a pitch at least {CW * 2} bytes: {rows}")
+    cbytes = clear.numel() * clear.element_size()
+    if any(o < 0 or p < CW * 3 or o + (CH - 1) * p + CW * 3 > cbytes for o, p, _, _ in rows):
+        raise IndexError(f"{who}: a {CH}x{CW} window leaves a clear cache of {cbytes} bytes: {rows}")
+    dbytes = 0 if depth is None else depth.numel() * depth.element_size()
+    if depth is not None and any(do < 0 or do + (CH - 1) * dp + CW * 2 > dbytes for _, _, do, dp in rows):
+        raise IndexError(f"{who}: a {CH}x{CW} window leaves a depth cache of {dbytes} bytes: {rows}")
+    for c, dt in ((clear, torch.uint8), (depth, torch.uint16)):
+        if c is not None and (not c.is_cuda or c.dtype != dt or not c.is_contiguous() or c.device != clear.device):
+            raise RuntimeError(f"adam-dehaze_amd: the cache must be a dense {dt} tensor on one cuda device, got {c.dtype} on "
+                               f"{c.device} (no CPU fallback)")
+    nblk = H.value("adh_batch_num_blocks", CH * CW)
+    with torch.cuda.device(clear.device):
+        gd = geom.contiguous().to(clear.device)
+        fd = fog6.to(device=clear.device, dtype=torch.float32).contiguous()
+        qd = field.contiguous().to(clear.device)
+        pd = None if params is None else params.to(device=clear.device, dtype=torch.float32).contiguous()
+        partial = None if pd is None else torch.empty(N * nblk, device=clear.device, dtype=torch.float64)
+        out = torch.empty((N, 3, CH, CW), device=clear.device, dtype=torch.float32)
+        H.call("adh_batch_nhhaze_from_u8", clear.data_ptr(), cbytes, H.ptr(depth), dbytes, gd.data_ptr(), fd.data_ptr(),
+               qd.data_ptr(), near, far, H.ptr(pd), N, CH, CW, H.ptr(partial), nblk, out.data_ptr())
+    return out
+
+
+def draw_nh_params(n: int, rng, nonuniform: Optional[Dict], chromatic: Optional[Dict], sizes, origins, fog: torch.Tensor):
+    """(fog6 float32 [n,6], field float64 [n,6]) for the n samples whose (beta, A) `fog` [n,2] `draw_haze_params` has drawn from
+    `rng` before: these draws come after it, so a seed's (label, beta, A) do not depend on the settings.  `sizes` [n,2]: the cached
+    images' (h, w) -- not the crop's; `origins` [n,2]: the windows' (y0, x0) in them (None: 0, 0).  Per sample, in order:
+    nonuniform: s ~ U(amplitude), the coarsest cell ~ U(cell) as a fraction of min(h, w), f0 = 1 / (cell min(h, w)) as a float32
+    value (capped at what keeps the finest cell 2 pixels wide), seed = rng.randint(0, 2**32), K = octaves; chromatic:
+    alpha ~ U(angstrom), beta_c = beta (lambda_c / lambda_g)^-alpha with lambda = (610, 550, 465) nm and green keeping beta,
+    A_c = clip(A + U(-tint, tint), 0, 1) in r, g, b order.  A setting that is None degenerates: s = 0 (K = 1, f0 = 0.5, seed 0),
+    or beta_c = beta and A_c = A."""
+    fog = torch.as_tensor(fog, dtype=torch.float32).reshape(n, 2).cpu()
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(n, 2)
+    origins = np.zeros((n, 2), np.int64) if origins is None else np.asarray(origins, dtype=np.int64).reshape(n, 2)
+    fog6, field = np.zeros((n, 6), np.float32), np.zeros((n, 6), np.float64)
+    ratio = np.array(NH_WAVELENGTHS_NM, dtype=np.float64) / NH_WAVELENGTHS_NM[1]
+    for i in range(n):
+        beta, A = float(fog[i, 0]), float(fog[i, 1])
+        s, K, f0, seed = 0.0, 1, 0.5, 0
+        if nonuniform is not None:
+            s = float(rng.uniform(*nonuniform["amplitude"]))
+            cell = float(rng.uniform(*nonuniform["cell"]))
+            K = int(nonuniform["octaves"])
+            f0 = min(float(np.float32(1.0 / (cell * float(sizes[i].min())))), 0.5 / 2.0 ** (K - 1))
+            seed = int(rng.randint(0, 2 ** 32))
+        b3, A3 = np.full(3, beta), np.full(3, A)
+        if chromatic is not None:
+            alpha = float(rng.uniform(*chromatic["angstrom"]))
+            b3 = beta * ratio ** (-alpha)
+            b3[1] = beta
+            A3 = np.clip(A + rng.uniform(-chromatic["tint"], chromatic["tint"], 3), 0.0, 1.0)
+        fog6[i, :3], fog6[i, 3:] = b3, A3
+        field[i] = (seed, origins[i, 0], origins[i, 1], K, s, f0)
+    return torch.from_numpy(fog6), torch.from_numpy(field)
+
+
 def _haze_dir(root: str, split: str) -> Optional[str]:
     """the directory that holds clear/ for `split`: <root>/<split>, else <root> itself, else None"""
     if not root:
@@ -599,11 +791,15 @@ class HazeSynthDataset:
     `img_size` ([L,H,W,3] and [L,H,W]; clear files through `adh_u8_resize_bilinear`, depth files through
     `adh_u16_resize_bilinear`), or with `crop_size` flat at the files' own sizes (`upscaled_size` where a crop does not fit), image
     k's pixels at byte `offsets[k]` and its depth at byte `depth_offsets[k]`, both multiples of 4.  The memory check counts 5 bytes
-    per pixel, 3 without depth maps.  `depth_range` = (near, far): the scene depth of levels 0 and 65535."""
+    per pixel, 3 without depth maps.  `depth_range` = (near, far): the scene depth of levels 0 and 65535.  `nonuniform` /
+    `chromatic` (None: off; True: `NH_DEFAULTS`; or a mapping) render patchy / wavelength-dependent haze through
+    `adh_batch_nhhaze_from_u8` instead; they change what is drawn per step, not what is cached."""
 
     def __init__(self, records: Sequence[Dict], img_size, device, rank: int = 0, world: int = 1, threads: int = 4,
-                 split: str = "train", crop_size=None, depth: str = "folder", depth_range=DEFAULT_DEPTH_RANGE):
+                 split: str = "train", crop_size=None, depth: str = "folder", depth_range=DEFAULT_DEPTH_RANGE,
+                 nonuniform=None, chromatic=None):
         from .image_io import image_size, load_depth, load_image
+        self.nonuniform, self.chromatic = _nh_settings("nonuniform", nonuniform), _nh_settings("chromatic", chromatic)
         if depth not in DEPTH_SOURCES:
             raise ValueError(f"dataset.synthetic_haze.depth must be one of {DEPTH_SOURCES}, got {depth!r}")
         self.H, self.W = _size2(img_size)
@@ -703,7 +899,11 @@ class HazeSynthDataset:
         'intensity' is the drawn density label.  train: from this loader's RandomState(seed + 1000 * rank + epoch), per batch, the
         augment rows (when `augment`), the crop origins (crop mode), then `draw_haze_params`: every epoch re-renders every image
         under fresh haze.  Otherwise: the centre crop, no rows, and `fixed_haze_params(seed, sample numbers)`, the same in every
-        epoch and for every world size.  The clear role comes from `batch_from_cache` / `batch_from_windows` with the same rows."""
+        epoch and for every world size.  The clear role comes from `batch_from_cache` / `batch_from_windows` with the same rows.
+        With `nonuniform` or `chromatic`: `draw_nh_params` draws after `draw_haze_params` (train: from the loader's stream, for the
+        batch; otherwise per sample from its own RandomState, `fixed_nh_params`), the field's origin is the crop origin, and the
+        dict gains 'beta_rgb', 'airlight_rgb' (float32 [n,3], device) and 'haze_field' (float64 [n,6], CPU); 'beta' and
+        'airlight' stay the drawn ones."""
         if self.total == 0 or (not train and len(self) == 0):
             return
         rng = np.random.RandomState(seed + 1000 * self.rank + epoch)
@@ -714,31 +914,53 @@ class HazeSynthDataset:
             if self.crop is not None:
                 sizes = self.sizes[index.numpy()]
                 origins = draw_crop_origins(sizes, self.crop, rng) if train else centre_origins(sizes, self.crop)
-            labels, fog = draw_haze_params(index.numel(), rng) if train else fixed_haze_params(seed, samples)
+            nh = self.nonuniform is not None or self.chromatic is not None
             geom = self.geometry(index.numpy(), origins)
-            fog = fog.to(self.device)
-            hazy = batch_haze_from_windows(self.clear, self.depth, geom, fog, self.crop or (self.H, self.W), params,
-                                           self.depth_range)
+            if nh:
+                n = index.numel()
+                sizes = self.sizes[index.numpy()] if self.crop is not None else np.tile([self.H, self.W], (n, 1))
+                if train:
+                    labels, fog = draw_haze_params(n, rng)
+                    fog6, field = draw_nh_params(n, rng, self.nonuniform, self.chromatic, sizes, origins, fog)
+                else:
+                    labels, fog, fog6, field = fixed_nh_params(seed, samples, self.nonuniform, self.chromatic, sizes, origins)
+                fog, fog6 = fog.to(self.device), fog6.to(self.device)
+                hazy = batch_nhhaze_from_windows(self.clear, self.depth, geom, fog6, field, self.crop or (self.H, self.W), params,
+                                                 self.depth_range)
+            else:
+                labels, fog = draw_haze_params(index.numel(), rng) if train else fixed_haze_params(seed, samples)
+                fog = fog.to(self.device)
+                hazy = batch_haze_from_windows(self.clear, self.depth, geom, fog, self.crop or (self.H, self.W), params,
+                                               self.depth_range)
             if self.crop is None:
                 clear = batch_from_cache(self.clear, index, params)
             else:
                 clear = batch_from_windows(self.clear, geom[:, :2].contiguous(), self.crop, params)
-            yield {"hazy": hazy, "clear": clear, "intensity": labels.to(self.device), "beta": fog[:, 0].contiguous(),
-                   "airlight": fog[:, 1].contiguous(), "name": [self.names[i] for i in index.tolist()]}
+            batch = {"hazy": hazy, "clear": clear, "intensity": labels.to(self.device), "beta": fog[:, 0].contiguous(),
+                     "airlight": fog[:, 1].contiguous(), "name": [self.names[i] for i in index.tolist()]}
+            if nh:
+                batch.update(beta_rgb=fog6[:, :3].contiguous(), airlight_rgb=fog6[:, 3:].contiguous(), haze_field=field)
+            yield batch
 
 
 def synthesize_tree(input_dir: str, output_dir: str, depth_dir: Optional[str] = None, seed: int = 0, device="cuda",
-                    depth_range=DEFAULT_DEPTH_RANGE) -> List[Dict]:
+                    depth_range=DEFAULT_DEPTH_RANGE, nonuniform=None, chromatic=None) -> List[Dict]:
     """`main.py --mode synthesize`: every `.jpg` / `.png` file of `input_dir` (sorted) rendered once per density level at its own
     size, as `<output_dir>/{low,medium,high}/{hazy,clear}/<stem>.png` -- the layout `folder_index` reads -- plus
     `<output_dir>/synthesize.json` with each file's beta and A.  The hazy bytes are `image_io.image_to_u8` of what
     `batch_haze_from_windows` gives for the whole image (no rows), i.e. what training with `dataset.synthetic_haze` sees for that
     (beta, A); the clear file holds the cached RGB bytes.  `depth_dir`: `<stem>.png` per clear file (a missing or differently
     sized one raises); None: the reference's radial depth map.  Per file, in order, from RandomState(seed): (beta, A) of low, of
-    medium, of high (`draw_fog_params`).  Returns the records written to the json."""
+    medium, of high (`draw_fog_params`).  `nonuniform` / `chromatic` (None: off; True: `NH_DEFAULTS`; or a mapping, checked before
+    a file is read): the three levels are rendered by `batch_nhhaze_from_windows` with what `draw_nh_params` draws from the same
+    stream after the file's (beta, A), origin (0, 0), and every record gains `beta_rgb`, `airlight_rgb` and `haze_field`
+    ({seed, oy, ox, K, s, f0}); without either the files and the json are what they were.  Returns the records written to the
+    json."""
     import json
     from .image_io import image_size, image_to_u8, load_depth, load_image, save_image
     device = torch.device(device)
+    nonuniform, chromatic = _nh_settings("nonuniform", nonuniform, "synthesize"), _nh_settings("chromatic", chromatic, "synthesize")
+    nh = nonuniform is not None or chromatic is not None
     if device.type != "cuda":
         raise RuntimeError(f"adam-dehaze_amd: haze is synthesized on a cuda device, got {device} (no CPU fallback)")
     if not os.path.isdir(input_dir):
@@ -776,24 +998,36 @@ def synthesize_tree(input_dir: str, output_dir: str, depth_dir: Optional[str] = 
             beta, A = draw_fog_params(LEVEL_NAMES, rng)
             fog = torch.stack([beta, A], dim=1).to(torch.float32)
             geom = torch.tensor([[0, w * 3, 0, w * 2]] * len(LEVEL_NAMES), dtype=torch.int64)
-            hazy = image_to_u8(batch_haze_from_windows(clear, depth, geom, fog, (h, w), None, depth_range)).cpu()
+            if nh:
+                fog6, field = draw_nh_params(len(LEVEL_NAMES), rng, nonuniform, chromatic, [(h, w)] * len(LEVEL_NAMES), None, fog)
+                hazy = image_to_u8(batch_nhhaze_from_windows(clear, depth, geom, fog6, field, (h, w), None, depth_range)).cpu()
+            else:
+                hazy = image_to_u8(batch_haze_from_windows(clear, depth, geom, fog, (h, w), None, depth_range)).cpu()
             clear_host = clear[:h * w * 3].reshape(h, w, 3).cpu()
             for k, level in enumerate(LEVEL_NAMES):
                 save_image(os.path.join(output_dir, level, "hazy", stem + ".png"), hazy[k])
                 save_image(os.path.join(output_dir, level, "clear", stem + ".png"), clear_host)
                 records.append({"file": path, "depth": dpath, "level": level, "name": stem + ".png", "height": h, "width": w,
                                 "beta": float(fog[k, 0]), "airlight": float(fog[k, 1])})
+                if nh:
+                    records[-1].update(beta_rgb=[float(v) for v in fog6[k, :3]], airlight_rgb=[float(v) for v in fog6[k, 3:]],
+                                       haze_field=[float(v) for v in field[k]])
+    head = {"seed": int(seed), "depth_range": [float(v) for v in depth_range]}
+    if nh:
+        head.update(nonuniform=nonuniform, chromatic=chromatic)
     with open(os.path.join(output_dir, "synthesize.json"), "w") as f:
-        json.dump({"seed": int(seed), "depth_range": [float(v) for v in depth_range], "files": records}, f, indent=2)
+        json.dump({**head, "files": records}, f, indent=2)
     print(f"synthesized {len(names)} clear files at 3 levels into {output_dir}")
     return records
 
 
 def _haze_loader(config, ds, settings, split: str, device, rank: Optional[int], world: Optional[int]) -> Callable:
     """`folder_loader` for `dataset.synthetic_haze` = `settings`"""
-    unknown = sorted(set(settings) - {"depth", "depth_range"})
+    unknown = sorted(set(settings) - {"depth", "depth_range", "nonuniform", "chromatic"})
     if unknown:
-        raise ValueError(f"dataset.synthetic_haze: unknown keys {unknown} (known: depth, depth_range)")
+        raise ValueError(f"dataset.synthetic_haze: unknown keys {unknown} (known: depth, depth_range, nonuniform, chromatic)")
+    nonuniform = _nh_settings("nonuniform", settings.get("nonuniform"))
+    chromatic = _nh_settings("chromatic", settings.get("chromatic"))
     depth = settings.get("depth", "folder")
     if depth not in DEPTH_SOURCES:
         raise ValueError(f"dataset.synthetic_haze.depth must be one of {DEPTH_SOURCES}, got {depth!r}")
@@ -822,6 +1056,9 @@ def _haze_loader(config, ds, settings, split: str, device, rank: Optional[int], 
         _CACHES[key] = HazeSynthDataset(records, ds["img_size"], device, rank, world, threads=int(ds.get("num_workers", 4)),
                                         split=split, crop_size=crop, depth=depth, depth_range=depth_range)
     cache = _CACHES[key]
+    if (nonuniform, chromatic) != (cache.nonuniform, cache.chromatic):
+        cache = copy.copy(cache)        # the caches are shared (the settings change no cached byte); the draws are this loader's
+        cache.nonuniform, cache.chromatic = nonuniform, chromatic
     batch_size, seed, train = int(ds["batch_size"]), int(config.get("seed", 0)), split == "train"
     augment = bool(ds.get("augmentation", True))
 
@@ -844,7 +1081,12 @@ def folder_loader(config, split: str, device, rank: Optional[int] = None, world:
     `dataset.synthetic_haze` (a mapping; absent: off) trains from clear images instead: `<root>/<split>/clear/<name>` (else
     `<root>/clear/<name>`) with `depth/<stem>.png` beside it, the hazy role rendered on the device every step
     (`HazeSynthDataset`).  Keys: `depth: folder | radial` (default folder) and `depth_range: [near, far]` (default [0.3, 1.0]); both
-    join the cache key.  A configured `synthetic_haze` whose split has no `clear/` folder raises."""
+    join the cache key.  `nonuniform: {amplitude: [lo, hi], cell: [lo, hi], octaves: K}` (patchy haze: the optical depth scaled by
+    1 + s (2 f - 1), s ~ U(amplitude), f a K-octave noise field whose coarsest cell is ~ U(cell) of the image's shorter side;
+    defaults [0.2, 0.8], [0.15, 0.5], 3) and `chromatic: {angstrom: [lo, hi], tint: x}` (beta_c = beta (lambda_c / 550 nm)^-alpha,
+    A_c = A + U(-x, x); defaults [0.0, 1.3], 0.05) switch the renderer to `adh_batch_nhhaze_from_u8`; an empty mapping takes the
+    defaults; they change no cached byte and do not join the cache key.  A configured `synthetic_haze` whose split has no
+    `clear/` folder raises."""
     ds = config.get("dataset", {})
     if isinstance(ds.get("synthetic_haze"), Mapping):
         return _haze_loader(config, ds, ds["synthetic_haze"], split, device, rank, world)

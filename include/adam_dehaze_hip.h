@@ -804,6 +804,30 @@ int adh_batch_haze_from_u8(void* stream, const uint8_t* clear, int64_t clear_byt
                            const int64_t* geom, const float* fog, double depth_near, double depth_far, const float* params, int N,
                            int CH, int CW, double* partial, int nblk, float* out_nchw);
 
+/* ---- patchy, wavelength-dependent haze (csrc/dataset.hip): adh_batch_haze_from_u8 with beta and A per channel and the optical
+ * depth scaled per source pixel by a density field that belongs to the image.
+ *   adh_batch_nhhaze_from_u8   everything as adh_batch_haze_from_u8 (windows, geom, depth, params, partial, nblk, access paths,
+ *       grid, launches) but the model.  fog: device float[N, 6] = {beta_r, beta_g, beta_b, A_r, A_g, A_b}.  field: device
+ *       double[N, 6] = {seed, oy, ox, K, s, f0}: seed an integer in [0, 2^32), (oy, ox) >= 0 the image coordinates of the window's
+ *       first pixel, K in 1..4 octaves, 0 <= s < 1 the amplitude, f0 > 0 the coarsest frequency in cells per pixel with
+ *       f0 * 2^(K-1) <= 0.5 and (oy + CH) * f0 * 2^(K-1), (ox + CW) * f0 * 2^(K-1) < 2^31.  Per source pixel (y, x), in float64:
+ *       Y = y + oy, X = x + ox;  for k < K: fk = f0 * 2^k; py = (double)Y * fk, px = (double)X * fk (one multiplication each);
+ *       iy = floor(py), uy = py - iy, wy = uy * uy * (3 - 2 * uy), likewise x;  v(ix, iy) = hash(ix, iy, k, seed) / 2^32;
+ *       n_k = lerp(lerp(v00, v01, wx), lerp(v10, v11, wx), wy) with lerp(a, b, w) = a + w * (b - a);
+ *       f = (sum_k 2^-k n_k) / (sum_k 2^-k);  m = 1 + s * (2 * f - 1);  t_c = exp(-((beta_c * m) * d));
+ *       h_c = min(max((float)(J_c * t_c + A_c * (1 - t_c)), 0), 1).  hash, on uint32 with wrapping products:
+ *       h = (ix * 0x9E3779B1) ^ (iy * 0x85EBCA77) ^ (k * 0xC2B2AE3D) ^ seed;  h ^= h >> 16;  h *= 0x7FEB352D;  h ^= h >> 15;
+ *       h *= 0x846CA68B;  h ^= h >> 16.  The field's arithmetic is not contracted, so a host restatement lands in the same
+ *       lattice cells.  s == 0 with equal channels gives the bits of adh_batch_haze_from_u8 with (beta, A); s == 0 gives plane c
+ *       of adh_batch_haze_from_u8 with (beta_c, A_c) when params == NULL; a window at (y0, x0) of an image with origin (y0, x0)
+ *       gives the same pixels as the whole image with origin (0, 0) when params == NULL and a depth cache is given (the radial
+ *       map belongs to the window); beta_c == 0 gives the bits of adh_batch_window_from_u8.  Neither geom nor field is validated
+ *       on the device (data.batch_nhhaze_from_windows checks both on the host).  ADH_E_ARG (nothing is launched) for everything
+ *       adh_batch_haze_from_u8 refuses and for a null field. */
+int adh_batch_nhhaze_from_u8(void* stream, const uint8_t* clear, int64_t clear_bytes, const void* depth, int64_t depth_bytes,
+                             const int64_t* geom, const float* fog, const double* field, double depth_near, double depth_far,
+                             const float* params, int N, int CH, int CW, double* partial, int nblk, float* out_nchw);
+
 /* ---- CIEDE2000 (csrc/ciede2000.hip): the per-pixel colour difference dE00 of Sharma, Wu and Dalal (2005), kL = kC = kH = 1,
  * between two dense fp32 [N,3,H,W] batches, and its mean per image.  lab_input == 0: the planes are sRGB in [0,1] (clamped as
  * adh_image_to_u8 clamps, NaN = 0) and go through skimage's rgb2lab constants (sRGB decoding, the 0.412453... matrix, the D65

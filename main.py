@@ -13,6 +13,7 @@ the hot path run on the HIP engine; dataset preprocessing is outside this build'
     python main.py --mode demo --input CLEAR --fit-niqe niqe.npz   # fit a NIQE model from clean files
     python main.py --mode demo --input DIR --niqe niqe.npz         # ... and score without ground truth: NIQE per file
     python main.py --mode synthesize --input CLEAR --depth DEPTH --output OUT   # render {low,medium,high}/{hazy,clear} pairs
+    python main.py --mode synthesize --input CLEAR --nonuniform --chromatic     # ... under patchy, tinted haze
 
 `--resume` is the reference's flag (main.py:50-51 parses it and never reads it); here it restores model, optimiser,
 scheduler, epoch and best-PSNR from the latest checkpoint of the mode's checkpoint directory (or from the file given
@@ -77,6 +78,12 @@ def parse_args():
     p.add_argument("--depth", type=str, default=None, metavar="DEPTH_DIR",
                    help="--mode synthesize --input CLEAR_DIR: the directory of depth maps, <stem>.png (8-bit or 16-bit grey) per "
                         "clear file; without it the reference's radial depth map is used")
+    p.add_argument("--nonuniform", action="store_true",
+                   help="--mode synthesize: patchy haze, the optical depth scaled per pixel by a multi-octave noise field; the "
+                        "values come from dataset.synthetic_haze.nonuniform in the config, else the defaults")
+    p.add_argument("--chromatic", action="store_true",
+                   help="--mode synthesize: wavelength-dependent beta and a tinted airlight per channel; the values come from "
+                        "dataset.synthetic_haze.chromatic in the config, else the defaults")
     return p.parse_args()
 
 
@@ -111,6 +118,8 @@ def main():
         raise SystemExit("--brisque-range needs --brisque-model: it is the range file of that model's features.")
     if args.depth and args.mode != "synthesize":
         raise SystemExit("--depth needs --mode synthesize --input CLEAR_DIR: it names the depth maps of the clear files.")
+    if (args.nonuniform or args.chromatic) and args.mode != "synthesize":
+        raise SystemExit("--nonuniform / --chromatic need --mode synthesize (training reads dataset.synthetic_haze in the config).")
     if args.mode == "synthesize" and not args.input:
         raise SystemExit("--mode synthesize needs --input CLEAR_DIR (and takes --depth DEPTH_DIR, --output OUT, --seed S).")
     if args.fit_niqe:
@@ -210,7 +219,10 @@ def main():
         T.run_comprehensive_evaluation(config)   # baseline branches, routed system, detector on hazy vs dehazed frames
     elif args.mode == "synthesize":
         from adam_dehaze_amd.data import synthesize_tree
-        synthesize_tree(args.input, args.output, depth_dir=args.depth, seed=config["seed"], device=config.get("device", "cuda"))
+        section = (config.get("dataset") or {}).get("synthetic_haze") or {}
+        synthesize_tree(args.input, args.output, depth_dir=args.depth, seed=config["seed"], device=config.get("device", "cuda"),
+                        nonuniform=(section.get("nonuniform") or True) if args.nonuniform else None,
+                        chromatic=(section.get("chromatic") or True) if args.chromatic else None)
     elif args.mode == "demo" and args.input and args.fit_niqe:
         T.fit_niqe_model(config, args.input, args.fit_niqe)
     elif args.mode == "demo" and args.input:

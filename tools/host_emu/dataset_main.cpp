@@ -8,6 +8,8 @@
 //   4 adh_u16_resize_bilinear  i: src_pitch_bytes h w bytes_per_px OH OW    b: src dst
 //   5 adh_batch_haze_from_u8   i: clear_bytes depth_bytes N CH CW nblk      d: depth_near depth_far
 //                                                                           b: clear depth geom fog params partial out
+//   6 adh_batch_nhhaze_from_u8 i: clear_bytes depth_bytes N CH CW nblk      d: depth_near depth_far
+//                                                                           b: clear depth geom fog field params partial out
 #include "common.h"
 #include "stream_rt.h"
 
@@ -26,6 +28,10 @@ static int64_t dispatch(const emu_call& c) {
         case 5:
             return adh_batch_haze_from_u8(nullptr, c.p<uint8_t>(0), c.i[0], c.p<void>(1), c.i[1], c.p<int64_t>(2), c.f(3), c.d[0],
                                           c.d[1], c.f(4), c.I(2), c.I(3), c.I(4), c.p<double>(5), c.I(5), c.f(6));
+        case 6:
+            return adh_batch_nhhaze_from_u8(nullptr, c.p<uint8_t>(0), c.i[0], c.p<void>(1), c.i[1], c.p<int64_t>(2), c.f(3),
+                                            c.p<double>(4), c.d[0], c.d[1], c.f(5), c.I(2), c.I(3), c.I(4), c.p<double>(6), c.I(5),
+                                            c.f(7));
     }
     return -1000;
 }
